@@ -24,11 +24,14 @@ import os
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")     # launcher duty, before the HIP runtime starts (see controllable_xgating_amd/__init__.py)
 import torch  # noqa: E402
+
+DUMP_SAMPLE = 1 << 17          # --dump-outputs: arrays larger than this many elements are written as a fixed sample of this size
 
 
 def synth_inputs(B, K, L, V, R, F1, F2, C_, seed, device):
@@ -330,8 +333,72 @@ def scst_parity(model, cfg, x, reward_b):
     return {"oracle_loss": loss_o, "hip_loss": loss_h, "delta": abs(loss_h - loss_o), "rollout_width": n_s}
 
 
-def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pmc=True, comm_diag=True, drop=None):
-    """One timed workload on this rank; returns (json-able dict | None on ranks != 0, parity failure text | None)."""
+def _state_tensors(model, optim):
+    hyper = getattr(optim, "_hyper", None)
+    return [model.flat_parameters(), optim.exp_avg, optim.exp_avg_sq, model.flat_grads()] + ([hyper] if hyper is not None else []) + \
+        list(model.buffers())
+
+
+def save_start(model, optim, dev):
+    """--dump-outputs: the seeded starting state of model and optimizer (weights, Adam moments and step, gradient buffer,
+    BatchNorm buffers, the dropout-seed counter, the RNG streams), taken before the first iteration."""
+    return dict(tensors=[t.clone() for t in _state_tensors(model, optim)], step=optim.step_count, call=getattr(model, "_call", None),
+                rng=torch.get_rng_state(), cuda_rng=torch.cuda.get_rng_state(dev), dev=dev)
+
+
+def restore_start(model, optim, st):
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        for t, c in zip(_state_tensors(model, optim), st["tensors"]):
+            t.copy_(c)
+    optim.step_count = st["step"]
+    if st["call"] is not None:
+        model._call = st["call"]
+    torch.set_rng_state(st["rng"])
+    torch.cuda.set_rng_state(st["cuda_rng"], st["dev"])
+    model.mark_params_changed()
+    model._packed_ptr()                          # (the packed shadow of the restored weights, as train.GraphedXEStep does)
+    torch.cuda.synchronize()
+
+
+def snapshot_outputs(model, loss):
+    """What a caller of the training step holds after it: the loss of the step and the model's state after the update
+    (parameters and BatchNorm buffers), as float32 / float64 host arrays keyed by file name.  A tensor of more than DUMP_SAMPLE
+    elements is represented by DUMP_SAMPLE of its elements (flat indices drawn once from a generator seeded with the tensor's
+    name, sorted), so the same elements are written by every run and every build."""
+    import zlib
+    out = {"loss": loss.detach().double().cpu().numpy()}
+    for kind, named in (("param", model.named_parameters()), ("buffer", model.named_buffers())):
+        for name, t in named:
+            flat = t.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+                idx = torch.randperm(flat.numel(), generator=g)[:DUMP_SAMPLE].sort().values
+                flat = flat[idx.to(flat.device)]
+            a = flat.cpu().numpy()
+            out["%s.%s" % (kind, name)] = a.astype(np.float64 if a.dtype.kind in "iu" or a.dtype == np.float64 else np.float32)
+    return out
+
+
+def write_outputs(path, arrays, limit=64 << 20):
+    """--dump-outputs: one DIR/<name>.npy per array; refuses to write more than `limit` bytes in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, limit))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "arrays": len(arrays), "bytes": int(total), "sample_per_array": DUMP_SAMPLE,
+            "what": "one more iteration of the timed path from the seeded starting state, after the timed steps"}
+
+
+def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pmc=True, comm_diag=True, drop=None, dump=None):
+    """One timed workload on this rank; returns (json-able dict | None on ranks != 0, parity failure text | None).
+    dump: a directory.  After the timed steps the model and optimizer are put back into their seeded starting state and the
+    timed step runs once more; what it computed is written there (snapshot_outputs).  The timed steps themselves cannot serve:
+    each one starts from the weights its predecessors produced, and those differ from run to run -- the kernels accumulate with
+    float atomics, so sums come out in varying order, and Adam turns that rounding in gradients of (near) zero, such as the
+    Linear bias ahead of BatchNorm, into steps of +-lr that compound over the iterations."""
     world, rank, dev, use_dist = ctx["world"], ctx["rank"], ctx["dev"], ctx["use_dist"]
     drop = args.drop if drop is None else drop
     if use_dist:
@@ -349,6 +416,7 @@ def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pm
     T = cfg["L"] + 1
     opt = make_opt(None, vocab_size=cfg["V"], seq_length=cfg["L"], drop_prob_lm=drop, precision=precision,
                    rnn_size=cfg["R"], att_size=cfg["A"], input_encoding_size=cfg["E"], feat_size=cfg["F1"], feat_size2=cfg["F2"])
+    torch.manual_seed(0)                         # the same initial weights in every run (--dump-outputs compares runs)
     model = SAModel(opt).to(dev)
     model.train()
     broadcast_parameters(model)
@@ -401,6 +469,7 @@ def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pm
         optim.step()
         return loss
 
+    start = save_start(model, optim, dev) if dump else None
     eager_step = step
     if use_graph:
         try:
@@ -449,6 +518,13 @@ def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pm
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     final_loss = float(loss.item())
+    dumped = None
+    if dump:                                     # (every rank: the step may contain the gradient all-reduce)
+        restore_start(model, optim, start)
+        loss_d = step()
+        torch.cuda.synchronize()
+        dumped = snapshot_outputs(model, loss_d) if rank == 0 else None
+        del start
     # ---- data-parallel diagnosis: the same iterations with the collective switched off (same streams, events and update
     # segments; only the RCCL kernels are missing) -> what the all-reduce costs each rank, i.e. its EXPOSED part
     comm = None
@@ -570,8 +646,7 @@ def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pm
                                    + ((" + gloo grad all-reduce" if os.environ.get("XG_FORCE_DIST") == "3" else " + RCCL grad all-reduce") if world > 1 else "") + " + clip + Adam",
                    # (zero_grad is fused into the update: train.ClipAdam(fused_zero=True) leaves .grad at zero)
                    "zero_grad": "fused into the update",
-                   "launch": "one HIP graph replay per iteration (train.GraphedXEStep)" if use_graph else "eager kernel launches",
-                   "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")},
+                   "launch": "one HIP graph replay per iteration (train.GraphedXEStep)" if use_graph else "eager kernel launches"},
         "final_loss": round(final_loss, 5),
         **({"NOT_A_MEASUREMENT": "XG_FORCE_DIST=3: %d ranks time-slicing ONE GPU, all-reduce over gloo -- control-flow exercise only" % world}
            if os.environ.get("XG_FORCE_DIST") == "3" else {}),
@@ -603,6 +678,8 @@ def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pm
                                                 "ms_per_step, against the dense MFMA peak of the products' arithmetic"}
     if comm is not None:
         out["comm"] = comm
+    if dumped is not None:
+        out["dump_outputs"] = write_outputs(dump, dumped)
     parity_fail = None
     if world == 1 and cpu_leg and not args.no_cpu_baseline:
         tol = 1e-2 if precision == "bf16" else 1e-4        # north_star: 1e-4 on the training loss in fp32, 1e-2 for the bf16 config
@@ -654,7 +731,7 @@ def main():
     os.dup2(2, 1)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed iterations (ms_per_step = their wall time / steps)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--path", choices=["fused", "surface"], default="fused",
                     help="fused: model.xe_loss (no (m,T,V) gradient tensor); surface: model() + criterion, reference call sequence")
@@ -671,7 +748,13 @@ def main():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the configs[2] (SCST) and configs[4] (hidden-1024 bf16) lines that the default single-GPU run appends")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed iteration once more from the seeded starting state and write what it "
+                         "computed (its loss, the updated parameters and BatchNorm buffers; a fixed sample of each large tensor) as "
+                         "DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU, RCCL over xGMI) -- never
@@ -684,8 +767,10 @@ def main():
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         os.dup2(json_fd, 1)                      # (the launched ranks do their own redirection)
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        import subprocess                        # a child process: this one may already hold the HIP runtime
+        r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+                            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        raise SystemExit(r.returncode)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -731,7 +816,7 @@ def main():
     if use_dist:
         dist.barrier()
 
-    out, fail = run_workload(args, args.workload, args.precision, args.steps, args.warmup, ctx)
+    out, fail = run_workload(args, args.workload, args.precision, args.steps, args.warmup, ctx, dump=args.dump_outputs)
     fails = [fail] if fail else []
     # the default single-GPU run also carries BASELINE.json's other single-GPU configurations (5 warm-up + 10 timed
     # iterations each, own roofline and parity self-check): configs[2] (SCST) and configs[4] (hidden 1024 / 40 frames, bf16)

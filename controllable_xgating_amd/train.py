@@ -34,7 +34,7 @@ def dist_diagnosis():
     Printed by bench.py --gpus N and tests/test_gpu_dp2.py when the process group does not come up or the first collective fails."""
     import os
     env = {k: os.environ.get(k) for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "HIP_VISIBLE_DEVICES",
-                                          "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES", "GPU_MAX_HW_QUEUES", "HSA_ENABLE_IPC_MODE_LEGACY",
+                                          "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES", "HSA_ENABLE_IPC_MODE_LEGACY",
                                           "NCCL_MAX_NCHANNELS", "NCCL_DEBUG")}
     try:
         rccl = ".".join(str(v) for v in torch.cuda.nccl.version())

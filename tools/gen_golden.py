@@ -9,6 +9,7 @@ contains no reference code; it only references the path.  Nothing here runs on
 the GPU box.
 
     python tools/gen_golden.py            # writes tests/golden/*.npz
+    python tools/gen_golden.py --data-io-only   # only data_io.npz (tests/test_data_cpu.py)
 """
 from __future__ import annotations
 
@@ -390,6 +391,51 @@ def gen_decode():
     print("wrote decode_seq.json", want[:4])
 
 
+def gen_data_io():
+    """caption_src/data_io.py on the inputs of tests/test_data_cpu.py (regenerated there from the same seeds): get_sub_frames,
+    collate_fn, custom_dset_train / custom_dset_test item by item and filt_word_category tag by tag.  Fixture: data_io.npz."""
+    import argparse
+    import pickle
+    import tempfile
+    from tests import test_data_cpu as td
+    sys.modules.setdefault("h5py", types.ModuleType("h5py"))
+    sys.path.insert(0, REF)
+    argv, sys.argv = sys.argv, ["x"]                       # (myopts parses the command line at import)
+    import data_io as ref
+    sys.argv = argv
+    g = {}
+    rng = np.random.default_rng(2)
+    for n in td.SUB_FRAME_LENGTHS:
+        g["sub_frames_%d" % n] = ref.get_sub_frames(rng.random((n, 8)).astype(np.float32), 26)
+    items = td._items(rng)
+    batch = [("vid%d_0" % i, it["cap"], it["cap_class"], it["class_mask"], it["feat1"], it["feat2"], it["feat_mask"],
+              it["pos_feat"], np.zeros((1, 3))) for i, it in enumerate(items)]
+    for i, t in enumerate(ref.collate_fn(batch)[1:9]):
+        g["collate_%d" % i] = t.numpy()
+    split, caps, worddict, category, f1, f2, pos = td._corpus(np.random.default_rng(4))
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = {}
+        for name, obj in (("split", split), ("caps", caps), ("wd", worddict), ("cate", category)):
+            paths[name] = os.path.join(tmp, name + ".pkl")
+            with open(paths[name], "wb") as f:
+                pickle.dump(obj, f)
+        for kind, Ref in (("train", ref.custom_dset_train), ("test", ref.custom_dset_test)):
+            r = Ref(paths["split"], paths["caps"], paths["cate"], f1, f2, pos, paths["wd"], K=10, opt=argparse.Namespace(seq_length=6))
+            g["%s_ids" % kind] = np.array(r.data_list)
+            for i in range(len(r)):
+                for key, v in zip(td.ITEM_KEYS, r[i]):
+                    g["%s_%d_%s" % (kind, i, key)] = np.asarray(v.numpy() if torch.is_tensor(v) else v)
+        cate = os.path.join(tmp, "cate.pkl")
+        with open(cate, "wb") as f:
+            pickle.dump({t: ["w%d" % i] for i, t in enumerate(td.POS_TAGS)}, f)
+        words = ["w%d" % i for i in range(len(td.POS_TAGS))] + ["untagged"]
+        theirs = ref.filt_word_category(cate, {w: i + 2 for i, w in enumerate(words)})[0]
+    g["pos_tag_category"] = np.array([theirs["w%d" % i] for i in range(len(td.POS_TAGS))], np.int64)
+    g["pos_untagged_category"] = np.int64(theirs.get("untagged", 1))
+    np.savez_compressed(os.path.join(GOLD, "data_io.npz"), **g)
+    print("wrote data_io.npz", len(g), "arrays")
+
+
 def main():
     if not os.path.isdir(REF):
         print("reference not present; nothing to do")
@@ -398,6 +444,9 @@ def main():
     torch.set_num_threads(8)
     if "--decode-only" in sys.argv:
         gen_decode()
+        return 0
+    if "--data-io-only" in sys.argv:
+        gen_data_io()
         return 0
     round2_only = "--round2-only" in sys.argv          # (import_reference() resets sys.argv for the reference's argparse)
     greedy_only = "--greedy-only" in sys.argv
@@ -433,6 +482,7 @@ def main():
     gen_traj(ref, "tiny")
     gen_traj(ref, "mid")
     gen_decode()
+    gen_data_io()
     return 0
 
 

@@ -12,14 +12,13 @@ processes time-slice one GPU: the 43-76 ms maxima of round 5) and with the -DXG_
 the same call sequence with no GPU time behind it = the host's own cost; build it first:
 python -c "import __graft_entry__ as g; g.build_variant('null', ['-DXG_NULL_LAUNCH'])").
 
-usage: host8_enqueue.py [nproc (8)] [iterations (6)]"""
+usage: host8_enqueue.py [nproc (6, at most 6)] [iterations (6)]"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
 def worker(rank, world, iters, q):
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch
     import bench
     cores = bench.pin_host_thread(rank, world)
@@ -60,7 +59,9 @@ def worker(rank, world, iters, q):
 def main():
     import multiprocessing as mp
     import tempfile
-    nproc = int(sys.argv[1]) if len(sys.argv) > 1 else 8
+    nproc = int(sys.argv[1]) if len(sys.argv) > 1 else 6
+    if not 1 <= nproc <= 6:
+        raise SystemExit("host8_enqueue.py: at most 6 processes may hold the GPU at once")
     iters = int(sys.argv[2]) if len(sys.argv) > 2 else 6
     ctx = mp.get_context("spawn")
     out = {}
