@@ -482,7 +482,8 @@ class SAModel(nn.Module):
         reference's early-exit lengths of the two rollouts -- trim with them, or hand n[:1] to RewardCriterion).
         In train mode the BatchNorm running statistics end up exactly where the reference's TWO sample() calls leave
         them (two momentum updates with the unbiased N/(N-1) variance of the un-repeated batch).  With train-mode dropout
-        (drop_prob_lm > 0) the two rollouts run as two calls with independent masks, like the reference's."""
+        (drop_prob_lm > 0) the two rollouts run as two calls with independent masks, like the reference's -- unless
+        self.dropout_seed is set: then both calls take that one seed and so the same masks (a checker regenerates both from it)."""
         temperature = float(opt.get("temperature", 1.0))
         params = self._param_list()
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)

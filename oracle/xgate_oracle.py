@@ -11,6 +11,10 @@ Dropout (train mode, p>0) uses the integer hash in oracle/paramgen.py so the HIP
 kernels can reproduce the very same masks.  Site ids:
   0 emb_rgb  1 emb_opfl  2 gate_rgb(step=frame)  3 gate_opfl(step=frame)  4 fusion
   5 decoder gate(step=t)  6 lstm_1 h(step=t)  7 lstm_2 h(step=t)  8 classifier(step=t)
+
+``relu_trace`` (optional list, test hook): every ReLU appends (site, detached pre-activation, tokens or None) in
+evaluation order; it changes no value.  Sites: enc.rgb / enc.opfl (BatchNorm output, (B*K,R)), gate_rgb / gate_opfl
+(per frame), fusion ((B,K,R)), pos_gate (per step, with the tokens whose embedding it read), classifer (per step).
 """
 from __future__ import annotations
 
@@ -44,7 +48,7 @@ def batchnorm_train(x, gamma, beta, eps=1e-5):
 
 
 def encoder_fwd(P, feats_rgb, feats_opfl, mask, train=True, p=0.0, seed=0,
-                running=None, momentum=0.1, eps=1e-5):
+                running=None, momentum=0.1, eps=1e-5, relu_trace=None):
     """EncoderLstm_two_fc.forward (sub_modules.py:118-159) with Gate (:42-47) and
     Fusion (:68-72).  ``running``: optional dict with running_mean/var tensors
     (names as in the state_dict) -- updated in place in train mode (unbiased
@@ -66,6 +70,8 @@ def encoder_fwd(P, feats_rgb, feats_opfl, mask, train=True, p=0.0, seed=0,
         else:
             rm, rv = running[pre + "1.running_mean"], running[pre + "1.running_var"]
             y = (z - rm) / torch.sqrt(rv + eps) * P[pre + "1.weight"] + P[pre + "1.bias"]
+        if relu_trace is not None:
+            relu_trace.append(("enc." + mod, y.detach().clone(), None))
         y = torch.relu(y).reshape(B, K, R)
         y = _drop(y, seed, site, 0, p, train) * mask.unsqueeze(-1)                    # :123,:128
         embs.append(y)
@@ -83,14 +89,22 @@ def encoder_fwd(P, feats_rgb, feats_opfl, mask, train=True, p=0.0, seed=0,
             hn = torch.sigmoid(og) * torch.tanh(cn)
             h[j] = hn * mk                                                            # :139-140 zeroing
             c[j] = cn * mk
-        g_r = _drop(torch.relu(_lin(h[1], P, ENC + "gate_rgb.gate.0")), seed, 2, i, p, train)
-        g_o = _drop(torch.relu(_lin(h[0], P, ENC + "gate_opfl.gate.0")), seed, 3, i, p, train)
+        pre_r = _lin(h[1], P, ENC + "gate_rgb.gate.0")
+        pre_o = _lin(h[0], P, ENC + "gate_opfl.gate.0")
+        if relu_trace is not None:
+            relu_trace.append(("gate_rgb", pre_r.detach().clone(), None))
+            relu_trace.append(("gate_opfl", pre_o.detach().clone(), None))
+        g_r = _drop(torch.relu(pre_r), seed, 2, i, p, train)
+        g_o = _drop(torch.relu(pre_o), seed, 3, i, p, train)
         outs[0].append(g_r * h[0] + h[0])                                             # :151, :45
         outs[1].append(g_o * h[1] + h[1])                                             # :152
     y_r = torch.stack(outs[0], dim=1)
     y_o = torch.stack(outs[1], dim=1)
     cat = torch.cat([y_r, y_o], dim=-1)                                               # :69
-    V = torch.relu(_lin(cat, P, ENC + "fusion.late_fusion.0"))
+    pre = _lin(cat, P, ENC + "fusion.late_fusion.0")
+    if relu_trace is not None:
+        relu_trace.append(("fusion", pre.detach().clone(), None))
+    V = torch.relu(pre)
     V = _drop(V, seed, 4, 0, p, train)                                                # :155-158
     return V
 
@@ -131,21 +145,27 @@ def attention(P, V, h1, h2, vproj=None):
     return af, alpha.squeeze(-1)
 
 
-def core_step(P, xt, mk, V, pos, state, p=0.0, seed=0, t=0, train=True, vproj=None):
-    """LSTMCore_two_layer_gate.forward (sub_modules.py:671-687)."""
+def core_step(P, xt, mk, V, pos, state, p=0.0, seed=0, t=0, train=True, vproj=None, relu_trace=None, tokens=None):
+    """LSTMCore_two_layer_gate.forward (sub_modules.py:671-687).  ``tokens``: the ids xt was read from (relu_trace only)."""
     (h1, c1), (h2, c2) = state
     af, alpha = attention(P, V, h1, h2, vproj)
-    g = _drop(torch.relu(_lin(xt, P, "lstmcore.gate.gate.0")), seed, 5, t, p, train)
+    pre = _lin(xt, P, "lstmcore.gate.gate.0")
+    if relu_trace is not None:
+        relu_trace.append(("pos_gate", pre.detach().clone(), None if tokens is None else tokens.clone()))
+    g = _drop(torch.relu(pre), seed, 5, t, p, train)
     posg = g * pos + pos                                                              # :682
     h1n, c1n = _cell(P, "lstmcore.lstm_1", xt, posg, h1, c1, mk, p, seed, 6, t, train)
     h2n, c2n = _cell(P, "lstmcore.lstm_2", h1n, af, h2, c2, mk, p, seed, 7, t, train)
     return h2n, [(h1n, c1n), (h2n, c2n)], alpha
 
 
-def heads(P, out, p=0.0, seed=0, t=0, train=True):
+def heads(P, out, p=0.0, seed=0, t=0, train=True, relu_trace=None):
     """SAModel.py:109-110."""
     logp = torch.log_softmax(_lin(out, P, "logit"), dim=1)
-    hcls = _drop(torch.relu(_lin(out, P, "classifer.0")), seed, 8, t, p, train)
+    pre = _lin(out, P, "classifer.0")
+    if relu_trace is not None:
+        relu_trace.append(("classifer", pre.detach().clone(), None))
+    hcls = _drop(torch.relu(pre), seed, 8, t, p, train)
     cat = torch.log_softmax(_lin(hcls, P, "classifer.3"), dim=1)
     return logp, cat
 
@@ -153,12 +173,12 @@ def heads(P, out, p=0.0, seed=0, t=0, train=True):
 # ------------------------------------------------------------------ teacher-forced forward
 def forward_xe(P, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask,
                train=True, p=0.0, seed=0, running=None, hoist=True, trace=None,
-               ss_prob=0.0, u_sel=None, u_tok=None, forced_it=None, it_trace=None):
+               ss_prob=0.0, u_sel=None, u_tok=None, forced_it=None, it_trace=None, relu_trace=None):
     """SAModel.forward (SAModel.py:67-115).  ``hoist=False`` recomputes v2a(V) every step exactly as the
     reference does (:677).  Scheduled sampling (:89-99): at steps i >= 1 in train mode, rows with
     u_sel[i,b] < ss_prob feed a token drawn (inverse CDF with u_tok[i,b]) from exp(previous step's log-probs)
     instead of seq[b,i]; ``forced_it`` (T,B) replays recorded input tokens instead (golden test)."""
-    V = encoder_fwd(P, feats_rgb, feats_opfl, feat_mask, train, p, seed, running)
+    V = encoder_fwd(P, feats_rgb, feats_opfl, feat_mask, train, p, seed, running, relu_trace=relu_trace)
     state = init_hidden(P, V, feat_mask)
     vproj = _lin(V, P, "lstmcore.v2a") if hoist else None
     outs, cats = [], []
@@ -177,8 +197,8 @@ def forward_xe(P, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask,
             it_trace.append(it.clone())
         xt = P["embed.weight"][it]
         mk = seq_mask[:, i].unsqueeze(1)
-        out, state, alpha = core_step(P, xt, mk, V, pos_feats, state, p, seed, i, train, vproj)
-        logp, cat = heads(P, out, p, seed, i, train)
+        out, state, alpha = core_step(P, xt, mk, V, pos_feats, state, p, seed, i, train, vproj, relu_trace, it)
+        logp, cat = heads(P, out, p, seed, i, train, relu_trace)
         outs.append(logp)
         cats.append(cat)
         if trace is not None:
@@ -200,12 +220,12 @@ def sample_token(logp_row: np.ndarray, u: float, temperature: float = 1.0) -> in
 
 def sample(P, feats_rgb, feats_opfl, feat_mask, pos_feats, L, mode="greedy",
            uniforms=None, forced=None, temperature=1.0, train=False, p=0.0, seed=0,
-           running=None, return_logp=False):
+           running=None, return_logp=False, relu_trace=None):
     """SAModel.sample (SAModel.py:163-219).  mode: 'greedy' (:186), 'sample'
     (inverse-CDF with supplied uniforms (L+1,B)), 'replay' (forced tokens (B,n)).
     Returns seq (B,n) int64, seqLogprobs (B,n) (torch, differentiable), and
     optionally the per-step logp list."""
-    V = encoder_fwd(P, feats_rgb, feats_opfl, feat_mask, train, p, seed, running)
+    V = encoder_fwd(P, feats_rgb, feats_opfl, feat_mask, train, p, seed, running, relu_trace=relu_trace)
     B = V.shape[0]
     state = init_hidden(P, V, feat_mask)
     vproj = _lin(V, P, "lstmcore.v2a")
@@ -228,6 +248,7 @@ def sample(P, feats_rgb, feats_opfl, feat_mask, pos_feats, L, mode="greedy",
                                    for b in range(B)], dtype=torch.int64)
             slp = logp.gather(1, it.unsqueeze(1)).squeeze(1)                          # :195
         xt = P["embed.weight"][it]                                                    # :198
+        fed = it
         if t >= 1:
             unfinished = (it > 0) if t == 1 else unfinished & (it > 0)                # :200-204
             if mode != "replay" and int(unfinished.sum()) == 0:
@@ -237,7 +258,7 @@ def sample(P, feats_rgb, feats_opfl, feat_mask, pos_feats, L, mode="greedy",
             seqs.append(it)
             slps.append(slp)
         mk = torch.ones(B, 1) if t == 0 else unfinished.float().unsqueeze(1)          # :212-215
-        out, state, _ = core_step(P, xt, mk, V, pos_feats, state, p, seed, t, train, vproj)
+        out, state, _ = core_step(P, xt, mk, V, pos_feats, state, p, seed, t, train, vproj, relu_trace, fed)
         logp = torch.log_softmax(_lin(out, P, "logit"), dim=1)                        # :217
         logps.append(logp)
     if not seqs:                      # every row finished at t = 1 (the reference's torch.cat would raise here)

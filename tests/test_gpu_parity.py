@@ -348,10 +348,10 @@ def test_dropout_masks_match_oracle_hash():
     assert_grads_close(model, oracle_grads(P), rtol=3e-3)
 
 
-def test_eval_mode_batchnorm_vs_golden():
+def test_eval_mode_batchnorm_vs_golden(p_drop=0.0):
     g = load_golden("evalbn_c1.npz")
     d = pg.make_dims(**CFG["c1"])
-    model = make_model(d, train=False)
+    model = make_model(d, train=False, p_drop=p_drop)
     enc = model.two_spatial_encoder
     for mod in ("rgb", "opfl"):
         bn = getattr(enc, f"visual_emb_{mod}")[1]
@@ -410,11 +410,11 @@ def test_init_hidden_and_encoder_surface():
 # ---------------------------------------------------------------- rollouts
 @pytest.mark.parametrize("name,tag,ragged", [("greedy_tiny.npz", "tiny", False), ("greedy_c1.npz", "c1", False),
                                               ("greedy_c1_ragged.npz", "c1", True)])
-def test_greedy_token_for_token_vs_reference(name, tag, ragged):
+def test_greedy_token_for_token_vs_reference(name, tag, ragged, p_drop=0.0):
     g = load_golden(name)
     d = pg.make_dims(**CFG[tag])
     assert float(g["min_margin"]) >= 1e-3                  # the reference's own top-2 margins, recorded in the fixture
-    model = make_model(d, P=pg.make_params(d, logit_gain=float(g["logit_gain"])), train=False)
+    model = make_model(d, P=pg.make_params(d, logit_gain=float(g["logit_gain"])), train=False, p_drop=p_drop)
     x = to_dev(pg.make_inputs(d, seed=0, ragged=ragged))
     with torch.no_grad():
         seq, slp = model.sample(x["feats_rgb"], x["feats_opfl"], x["feat_mask"], x["pos_feats"], {"sample_max": 1})
@@ -730,11 +730,11 @@ def test_fused_zero_grad_update_equals_plain_update():
 
 # ---------------------------------------------------------------- beam search
 @pytest.mark.parametrize("tag", ["tiny", "c1"])
-def test_beam_search_vs_reference_golden(tag):
+def test_beam_search_vs_reference_golden(tag, p_drop=0.0):
     g = load_golden(f"beam_{tag}.npz")
     cfg = dict(CFG[tag]); cfg["B"] = min(cfg["B"], 3)
     d = pg.make_dims(**cfg)
-    model = make_model(d, train=False)
+    model = make_model(d, train=False, p_drop=p_drop)
     x = to_dev(pg.make_inputs(d, seed=0))
     with torch.no_grad():
         seq, slp = model.sample(x["feats_rgb"], x["feats_opfl"], x["feat_mask"], x["pos_feats"],
@@ -746,7 +746,7 @@ def test_beam_search_vs_reference_golden(tag):
 
 # ---------------------------------------------------------------- driver counterpart
 @pytest.mark.parametrize("beam", [1, 3])
-def test_eval_split_vs_oracle_and_beam_golden(beam):
+def test_eval_split_vs_oracle_and_beam_golden(beam, p_drop=0.0):
     """eval_utils.eval_split (eval_utils.py:18-84): eval-mode loss = language + weight_class * category loss per batch,
     averaged over batches; captions = decoded greedy tokens (oracle) or beam-search tokens (reference golden); the model
     is back in train mode afterwards."""
@@ -754,7 +754,7 @@ def test_eval_split_vs_oracle_and_beam_golden(beam):
     from controllable_xgating_amd.driver import decode_sequence, eval_split
     cfg = dict(CFG["tiny"]); cfg["B"] = 3
     d = pg.make_dims(**cfg)
-    model = make_model(d, train=True)
+    model = make_model(d, train=True, p_drop=p_drop)
     itow = {i: "w%d" % i for i in range(1, d.V)}
     batches = []
     for seed in (0, 1):
@@ -1438,13 +1438,13 @@ def test_kernel_variant_edges_xe_vs_oracle(cfg):
 
 
 # ---------------------------------------------------------------- round 2: fixtures that pin what round 1 left unpinned
-def test_greedy_with_natural_eos_token_for_token_vs_reference():
+def test_greedy_with_natural_eos_token_for_token_vs_reference(p_drop=0.0):
     """greedy_c1_eos.npz: 44 distinct words, rows finish at steps 3..13 (two never do), live top-2 margins >= 2.4e-3 in the
     reference itself -> EOS / `unfinished` / zeroing of finished rows (SAModel.py:200-215) checked against the reference."""
     from tests.util import EOS_CASE, eos_params
     g = load_golden("greedy_c1_eos.npz")
     d = pg.make_dims(**CFG["c1"])
-    model = make_model(d, P=eos_params(d), train=False)
+    model = make_model(d, P=eos_params(d), train=False, p_drop=p_drop)
     x = to_dev(pg.make_inputs(d, seed=EOS_CASE["input_seed"]))
     with torch.no_grad():
         seq, slp = model.sample(x["feats_rgb"], x["feats_opfl"], x["feat_mask"], x["pos_feats"], {"sample_max": 1})
@@ -1895,3 +1895,30 @@ def test_greedy_rollout_is_reproducible(precision):
         else:
             assert torch.equal(seq, first[0]), (precision, rep)
             np.testing.assert_allclose(lp.cpu().numpy(), first[1].cpu().numpy(), atol=2e-5, rtol=0)
+
+
+# ---------------------------------------------------------------- the eval-mode goldens with a model built with drop_prob_lm = 0.5
+# The reference evaluates a model built from the saved options (drop_prob_lm = 0.5) and switched to eval() (eval.py:57-73):
+# XgRun then carries train = 0, drop_p = 0.5, and no dropout site may act.  The same assertions as the p = 0 tests above.
+@pytest.mark.parametrize("name,tag,ragged", [("greedy_tiny.npz", "tiny", False), ("greedy_c1.npz", "c1", False),
+                                              ("greedy_c1_ragged.npz", "c1", True)])
+def test_eval_dropout_half_greedy_token_for_token_vs_reference(name, tag, ragged):
+    test_greedy_token_for_token_vs_reference(name, tag, ragged, p_drop=0.5)
+
+
+def test_eval_dropout_half_greedy_with_natural_eos_vs_reference():
+    test_greedy_with_natural_eos_token_for_token_vs_reference(p_drop=0.5)
+
+
+def test_eval_dropout_half_batchnorm_vs_golden():
+    test_eval_mode_batchnorm_vs_golden(p_drop=0.5)
+
+
+@pytest.mark.parametrize("tag", ["tiny", "c1"])
+def test_eval_dropout_half_beam_search_vs_reference_golden(tag):
+    test_beam_search_vs_reference_golden(tag, p_drop=0.5)
+
+
+@pytest.mark.parametrize("beam", [1, 3])
+def test_eval_dropout_half_eval_split_vs_oracle_and_beam_golden(beam):
+    test_eval_split_vs_oracle_and_beam_golden(beam, p_drop=0.5)
