@@ -1,0 +1,562 @@
+// POS sequence generator (reference pos_src/SAModel.py, pos_src/sub_modules.py): eval-mode inference behind include/xgate_pos.h.
+//
+// The model is a strict subset of the captioner: the same Linear -> BN -> ReLU embeddings, two masked LSTMCell encoders and the
+// late fusion (no cross gates), a ONE-layer attention decoder and a C-way category head.  The encoder and every product reuse the
+// captioner's launchers (xg_kernels.h) unchanged; what is new here is the decoder step:
+//   1. p = h2a(h)                        xgk_skinny, one job               (B, A)
+//   2. attention over the hoisted v2a(V)   pos_attn_kernel                 af -> X[:, 0:R]
+//   3. af a2h^T + h h2h^T                 xgk_skinny, one job of two segments (B, 4R)
+//   4. cell epilogue + category head      pos_cell_head_kernel: i2h(embed[tok]) is a row of the (C, 4R) table embed i2h^T + b
+//      hoisted once per call; the cell writes h' into X[:, R:2R] (the next step's input) and the state row of the step, then the
+//      same workgroup computes the C logits, log_softmax, the greedy choice and the `unfinished` / mask bookkeeping of its video.
+// All steps run on the device; the reference's early exits (teacher forcing: an all-zero category column; greedy: every row
+// finished) are computed afterwards by pos_first_zero_col_kernel into a device word, so a call never synchronises with the host.
+#include "xg_kernels.h"
+#include "../../include/xgate_pos.h"
+
+namespace {
+
+constexpr int POS_TPB = 256;
+// the two per-video kernels of the step run 16 waves per workgroup: the step has only B workgroups, and each of them is bound by
+// the latency of its loads (the hoisted v2a(V) rows, V, the weight rows of the head), so more waves keep more loads in flight
+// (256-thread versions took 34 and 15 us per step at B = 64, K = 20)
+constexpr int STEP_TPB = 1024;
+constexpr int STEP_WAVES = STEP_TPB / 64;
+__device__ __forceinline__ int xg_cdiv_d(int a, int b) { return (a + b - 1) / b; }
+
+// one workgroup per video: e_k = w . tanh(p + q_k) (one wave per frame at a time), alpha = softmax_k(e) over ALL K frames
+// (pos_src/sub_modules.py:701-708: the softmax is not masked; a2w.bias cancels in it), af = sum_k alpha_k V_k into X[b, 0:R].
+// The context sums run in `nsplit` interleaved parts over the frames, added in part order: every element has one fixed order.
+template <bool V4>
+__global__ void __launch_bounds__(STEP_TPB) pos_attn_kernel(const float* __restrict__ P, const float* __restrict__ Q,
+                                                            const float* __restrict__ V, const float* __restrict__ w, float* X, int K,
+                                                            int R, int A, int nsplit) {
+    extern __shared__ float lds[];
+    float* ps = lds;              // A
+    float* wsh = lds + A;         // A
+    float* al = lds + 2 * A;      // K
+    float* red = al + K;          // nsplit * R
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* vb = V + (size_t)b * K * R;
+    // the context's V operands are requested first (they do not depend on the scores): one latency round instead of two
+    constexpr int VREG = 16;
+    const bool vpre = nsplit * R <= STEP_TPB && xg_cdiv_d(K, nsplit) <= VREG;
+    const int vr = tid % R, vpart = tid / R;
+    float vreg[VREG];
+    if (vpre && tid < nsplit * R) {
+#pragma unroll
+        for (int i = 0; i < VREG; ++i) {
+            const int k = vpart + i * nsplit;
+            vreg[i] = k < K ? vb[(size_t)k * R + vr] : 0.f;
+        }
+    }
+    for (int a = tid; a < A; a += STEP_TPB) {
+        ps[a] = P[(size_t)b * A + a];
+        wsh[a] = w[a];
+    }
+    __syncthreads();
+    // frames k0 and k0 + 16 of a wave together, so that both rows of v2a(V) are in flight at once
+    for (int k0 = wave; k0 < K; k0 += 2 * STEP_WAVES) {
+        const int k1 = k0 + STEP_WAVES;
+        const bool two = k1 < K;                                // wave-uniform
+        const float* q0 = Q + ((size_t)b * K + k0) * A;
+        const float* q1 = Q + ((size_t)b * K + (two ? k1 : k0)) * A;
+        float acc0 = 0.f, acc1 = 0.f;
+        if (V4) {
+            const float4* q04 = reinterpret_cast<const float4*>(q0);
+            const float4* q14 = reinterpret_cast<const float4*>(q1);
+#pragma unroll 6
+            for (int a4 = lane; a4 < A / 4; a4 += 64) {
+                const float4 u = q04[a4];
+                const float4 v = q14[a4];
+                const int a = 4 * a4;
+                const float p0 = ps[a], p1 = ps[a + 1], p2 = ps[a + 2], p3 = ps[a + 3];
+                const float w0 = wsh[a], w1 = wsh[a + 1], w2 = wsh[a + 2], w3 = wsh[a + 3];
+                acc0 += w0 * xg_tanh(p0 + u.x) + w1 * xg_tanh(p1 + u.y) + w2 * xg_tanh(p2 + u.z) + w3 * xg_tanh(p3 + u.w);
+                acc1 += w0 * xg_tanh(p0 + v.x) + w1 * xg_tanh(p1 + v.y) + w2 * xg_tanh(p2 + v.z) + w3 * xg_tanh(p3 + v.w);
+            }
+        } else {
+#pragma unroll 4
+            for (int a = lane; a < A; a += 64) {
+                const float u = q0[a], v = q1[a];
+                acc0 += wsh[a] * xg_tanh(ps[a] + u);
+                acc1 += wsh[a] * xg_tanh(ps[a] + v);
+            }
+        }
+        acc0 = wave_sum(acc0);
+        acc1 = wave_sum(acc1);
+        if (lane == 0) {
+            al[k0] = acc0;
+            if (two) al[k1] = acc1;
+        }
+    }
+    __syncthreads();
+    float mx = al[0];
+    for (int k = 1; k < K; ++k) mx = fmaxf(mx, al[k]);
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s += __expf(al[k] - mx);
+    __syncthreads();                                           // (every thread has read the scores)
+    for (int k = tid; k < K; k += STEP_TPB) al[k] = __expf(al[k] - mx) / s;
+    __syncthreads();
+    if (vpre) {
+        if (tid < nsplit * R) {
+            float acc = 0.f;
+#pragma unroll
+            for (int i = 0; i < VREG; ++i) {
+                const int k = vpart + i * nsplit;
+                if (k < K) acc += al[k] * vreg[i];
+            }
+            red[tid] = acc;
+        }
+    } else {
+        for (int i = tid; i < nsplit * R; i += STEP_TPB) {
+            const int r = i % R, part = i / R;
+            float acc = 0.f;
+#pragma unroll 4
+            for (int k = part; k < K; k += nsplit) acc += al[k] * vb[(size_t)k * R + r];
+            red[i] = acc;
+        }
+    }
+    __syncthreads();
+    for (int r = tid; r < R; r += STEP_TPB) {
+        float acc = red[r];
+        for (int part = 1; part < nsplit; ++part) acc += red[part * R + r];
+        X[(size_t)b * 2 * R + r] = acc;
+    }
+}
+
+// A (N,K) row-major weight re-tiled for the skinny launcher's fast kernel (SkSeg.Bp: 32 x 32 tiles, nck = ceil(K/32) tiles per 32-row
+// slice, each tile in the MFMA-fragment order [i(4)][h(2)][n(32)][q(4)] -> element (n, 16 h + 4 i + q) that xg_pack.hip writes for
+// its fp32 shadow).  One workgroup per tile; zero padding past N and K.
+__global__ void __launch_bounds__(POS_TPB) pos_pack_kernel(const float* __restrict__ src, int N, int K, float* __restrict__ dst) {
+    __shared__ float t[32][33];
+    const int nck = (K + 31) >> 5;
+    const int tile = blockIdx.x, tn = tile / nck, kc = tile - tn * nck;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int nn = ty + 8 * r, n = tn * 32 + nn, k = kc * 32 + tx;
+        t[nn][tx] = (n < N && k < K) ? src[(size_t)n * K + k] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int o = threadIdx.x + POS_TPB * r;
+        const int q = o & 3, nn = (o >> 2) & 31, h = (o >> 7) & 1, i = o >> 8;
+        dst[(size_t)tile * 1024 + o] = t[nn][16 * h + 4 * i + q];
+    }
+}
+
+inline size_t packed_floats(int N, int K) { return (size_t)xg_cdiv(N, 32) * xg_cdiv(K, 32) * 1024; }
+
+// tab (C,4R) += a2h.bias + h2h.bias: the per-step cell then adds ONE hoisted row per video
+__global__ void __launch_bounds__(POS_TPB) pos_fold_bias_kernel(float* tab, const float* b1, const float* b2, int C, int N) {
+    const int64_t i = (int64_t)blockIdx.x * POS_TPB + threadIdx.x;
+    if (i >= (int64_t)C * N) return;
+    const int n = (int)(i % N);
+    tab[i] += b1[n] + b2[n];
+}
+
+struct CellHeadArgs {
+    const float* S;              // (B,4R) af a2h^T + h h2h^T, no bias
+    const float* tab;            // (C,4R) embed i2h^T + i2h.bias + a2h.bias + h2h.bias
+    const float *logit_w, *logit_b;
+    float* X;                    // (B,2R): h read from and h' written to columns R..2R
+    float* c;                    // (B,R) cell state, in place
+    int B, R, C, T, t;
+    // teacher forcing: tokens and masks of the step from the (B,T) inputs, logp (B,T,C) out
+    const int64_t* cap; const float* new_mask; float* logp;
+    // greedy: tok (B) = the previous step's choice, masks (B,T), seq / seq_logp (B,T-1), states (B,T,R)
+    int64_t* tok; float* masks; int64_t* seq; float* seq_logp; float* states;
+};
+
+// the greedy choice of step t + 1 from the log-probabilities of step t (SAModel.py:142-166): torch.max's first maximum, then
+// `unfinished`, the masked token, its log-prob and the next step's mask
+__device__ __forceinline__ void pos_choose(const CellHeadArgs& a, int b, int best, float bv) {
+    const size_t T = a.T;
+    const float unf_prev = a.t == 0 ? 1.0f : a.masks[b * T + a.t];
+    const float unf = best > 0 ? unf_prev : 0.0f;
+    a.seq[b * (T - 1) + a.t] = unf != 0.0f ? best : 0;
+    a.seq_logp[b * (T - 1) + a.t] = bv;
+    a.masks[b * T + a.t + 1] = unf;
+    a.tok[b] = best;
+}
+
+// one workgroup per video: the two_inputs_lstmcell epilogue (pos_src/sub_modules.py:871-889: order i,f,o,g, the mask holds c and
+// h, dropout is the identity in eval mode), then logit + log_softmax (SAModel.py:79-80 / :178) and, for greedy, the choice
+__global__ void __launch_bounds__(STEP_TPB) pos_cell_head_kernel(CellHeadArgs a) {
+    extern __shared__ float lds[];
+    float* hs = lds;             // R
+    float* lg = lds + a.R;       // C
+    __shared__ float s_lse;
+    const int b = blockIdx.x, tid = threadIdx.x, R = a.R, C = a.C, T = a.T, t = a.t;
+    const bool tf = a.cap != nullptr;
+    int64_t tk;
+    float m;
+    if (tf) {
+        tk = a.cap[(size_t)b * T + t];
+        m = a.new_mask[(size_t)b * T + t];
+    } else {
+        tk = t == 0 ? 0 : a.tok[b];
+        m = t == 0 ? 1.0f : a.masks[(size_t)b * T + t];
+    }
+    tk = tk < 0 ? 0 : (tk >= C ? C - 1 : tk);                   // (the reference would raise on an out-of-range category)
+    const float* s = a.S + (size_t)b * 4 * R;
+    const float* tb = a.tab + (size_t)tk * 4 * R;
+    float* xh = a.X + (size_t)b * 2 * R + R;
+    float* cb = a.c + (size_t)b * R;
+    for (int j = tid; j < R; j += STEP_TPB) {
+        const float ig = xg_sigmoid(s[j] + tb[j]), fg = xg_sigmoid(s[R + j] + tb[R + j]);
+        const float og = xg_sigmoid(s[2 * R + j] + tb[2 * R + j]), gg = xg_tanh(s[3 * R + j] + tb[3 * R + j]);
+        const float cp = cb[j], hp = xh[j];
+        float cn = fg * cp + ig * gg;
+        cn = cn * m + cp * (1.0f - m);
+        float hn = og * xg_tanh(cn);
+        hn = hn * m + hp * (1.0f - m);
+        cb[j] = cn;
+        xh[j] = hn;
+        hs[j] = hn;
+        if (!tf) a.states[((size_t)b * T + t) * R + j] = hn;
+    }
+    if (!tf && t == 0 && tid == 0) a.masks[(size_t)b * T] = 1.0f;
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int cc = wave; cc < C; cc += STEP_WAVES) {
+        const float* wr = a.logit_w + (size_t)cc * R;
+        float acc = 0.f;
+#pragma unroll 8
+        for (int j = lane; j < R; j += 64) acc += wr[j] * hs[j];
+        acc = wave_sum(acc);
+        if (lane == 0) lg[cc] = acc + a.logit_b[cc];
+    }
+    __syncthreads();
+    const bool choose = !tf && t + 1 < T;
+    if (C <= 64) {                                              // one lane per category
+        if (wave == 0) {
+            const float v = lane < C ? lg[lane] : -INFINITY;
+            const float mx = wave_max(v);
+            const float lse = mx + logf(wave_sum(lane < C ? expf(v - mx) : 0.f));
+            if (lane == 0) s_lse = lse;
+            if (choose) {
+                const float lp = lane < C ? v - lse : -INFINITY;
+                const float bv = wave_max(lp);
+                const int best = __ffsll((unsigned long long)__ballot(lane < C && lp == bv)) - 1;
+                if (lane == 0) pos_choose(a, b, best, bv);
+            }
+        }
+    } else if (tid == 0) {
+        float mx = lg[0];
+        for (int cc = 1; cc < C; ++cc) mx = fmaxf(mx, lg[cc]);
+        float se = 0.f;
+        for (int cc = 0; cc < C; ++cc) se += expf(lg[cc] - mx);
+        const float lse = mx + logf(se);
+        s_lse = lse;
+        if (choose) {
+            int best = 0;
+            float bv = lg[0] - lse;
+            for (int cc = 1; cc < C; ++cc) {
+                const float v = lg[cc] - lse;
+                if (v > bv) { bv = v; best = cc; }
+            }
+            pos_choose(a, b, best, bv);
+        }
+    }
+    if (tf) {
+        __syncthreads();
+        for (int cc = tid; cc < C; cc += STEP_TPB) a.logp[((size_t)b * T + t) * C + cc] = lg[cc] - s_lse;
+    }
+}
+
+// out = the first column i >= 1 of the (B,T) matrix that is all zero, minus `sub` (T - sub when there is none): T' of the teacher-
+// forced forward (int64 categories, sub 0) or n of the greedy rollout (float masks, sub 1)
+__global__ void __launch_bounds__(POS_TPB) pos_first_zero_col_kernel(const int64_t* tokm, const float* maskm, int B, int T, int sub,
+                                                                     int32_t* out) {
+    int res = T - sub;
+    for (int i = 1; i < T; ++i) {
+        int nz = 0;
+        for (int b = threadIdx.x; b < B; b += POS_TPB) nz |= tokm ? (tokm[(size_t)b * T + i] != 0) : (maskm[(size_t)b * T + i] != 0.0f);
+        if (!__syncthreads_or(nz)) { res = i - sub; break; }
+    }
+    if (threadIdx.x == 0) out[0] = res;
+}
+
+const char* const kNames[] = {
+    "two_fc_encoder.visual_emb_rgb.0.weight", "two_fc_encoder.visual_emb_rgb.0.bias",
+    "two_fc_encoder.visual_emb_rgb.1.weight", "two_fc_encoder.visual_emb_rgb.1.bias",
+    "two_fc_encoder.visual_emb_opfl.0.weight", "two_fc_encoder.visual_emb_opfl.0.bias",
+    "two_fc_encoder.visual_emb_opfl.1.weight", "two_fc_encoder.visual_emb_opfl.1.bias",
+    "two_fc_encoder.lstmcell_rgb.weight_ih", "two_fc_encoder.lstmcell_rgb.weight_hh",
+    "two_fc_encoder.lstmcell_rgb.bias_ih", "two_fc_encoder.lstmcell_rgb.bias_hh",
+    "two_fc_encoder.lstmcell_opfl.weight_ih", "two_fc_encoder.lstmcell_opfl.weight_hh",
+    "two_fc_encoder.lstmcell_opfl.bias_ih", "two_fc_encoder.lstmcell_opfl.bias_hh",
+    "two_fc_encoder.fusion.late_fusion.0.weight", "two_fc_encoder.fusion.late_fusion.0.bias",
+    "img_embed_h_1.weight", "img_embed_h_1.bias", "img_embed_c_1.weight", "img_embed_c_1.bias",
+    "lstmcore.lstmcell.i2h.weight", "lstmcore.lstmcell.i2h.bias", "lstmcore.lstmcell.a2h.weight", "lstmcore.lstmcell.a2h.bias",
+    "lstmcore.lstmcell.h2h.weight", "lstmcore.lstmcell.h2h.bias",
+    "lstmcore.v2a.weight", "lstmcore.v2a.bias", "lstmcore.h2a.weight", "lstmcore.h2a.bias", "lstmcore.a2w.weight", "lstmcore.a2w.bias",
+    "embed.weight", "logit.weight", "logit.bias"};
+constexpr int kNParams = (int)(sizeof(kNames) / sizeof(kNames[0]));
+static_assert(kNParams * sizeof(float*) == sizeof(XgpParams), "one XgpParams field per name");
+
+bool dims_ok(const XgpDims* d, bool need_t) {
+    if (!d) return false;
+    if (d->B <= 0 || d->K <= 0 || d->R <= 0 || d->A <= 0 || d->E <= 0 || d->C <= 0 || d->F1 <= 0 || d->F2 <= 0) return false;
+    if (need_t && d->T <= 0) return false;
+    // the workgroup-per-video kernels keep p, w (A each), the context parts and h (R) in LDS (under 64 KiB); 32-bit offsets
+    if (d->A > 4096 || d->R > 4096 || d->C > 4096 || d->K > 1024) return false;
+    return (int64_t)d->B * d->K * 4 * d->R < (1LL << 31) && (int64_t)d->B * (d->T > 0 ? d->T : 1) * d->R < (1LL << 31);
+}
+
+int64_t numel_of(const XgpDims* d, int i) {
+    const int64_t R = d->R, A = d->A, E = d->E, C = d->C, F1 = d->F1, F2 = d->F2;
+    switch (i) {
+        case 0: return R * F1;
+        case 4: return R * F2;
+        case 1: case 2: case 3: case 5: case 6: case 7: return R;
+        case 8: case 9: case 12: case 13: return 4 * R * R;
+        case 10: case 11: case 14: case 15: return 4 * R;
+        case 16: return R * 2 * R;
+        case 17: return R;
+        case 18: case 20: return R * R;
+        case 19: case 21: return R;
+        case 22: return 4 * R * E;
+        case 24: case 26: return 4 * R * R;
+        case 23: case 25: case 27: return 4 * R;
+        case 28: case 30: return A * R;
+        case 29: case 31: return A;
+        case 32: return A;
+        case 33: return 1;
+        case 34: return C * E;
+        case 35: return C * R;
+        case 36: return C;
+    }
+    return -1;
+}
+
+// workspace regions in floats, each rounded up to 64 floats (256 bytes)
+struct Ws {
+    float *Z, *Xe, *Pre, *S2, *c2, *hz, *Hcat, *V, *vbar, *Q, *tab, *X, *P, *S, *c;
+    int64_t* tok;
+    float *pk_h2a, *pk_a2h, *pk_h2h;   // the decoder step's weights packed for the fast skinny kernel
+    size_t floats;
+};
+
+Ws ws_layout(const XgpDims* d, void* base) {
+    const size_t B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, BK = B * K;
+    float* p = (float*)base;
+    size_t off = 0;
+    auto take = [&](size_t n) { float* r = p ? p + off : nullptr; off += (n + 63) / 64 * 64; return r; };
+    Ws w;
+    w.Z = take(2 * BK * R);          // visual embeddings (rgb, opfl)
+    w.Xe = take(2 * BK * R);         // after BatchNorm + ReLU + frame mask
+    w.Pre = take(2 * BK * 4 * R);    // hoisted input side of the two encoder cells
+    w.S2 = take(2 * B * 4 * R);      // recurrent side of one frame
+    w.c2 = take(2 * B * R);
+    w.hz = take(B * R);              // zero state
+    w.Hcat = take(BK * 2 * R);       // [h_rgb ; h_opfl] of every frame
+    w.V = take(BK * R);
+    w.vbar = take(B * R);
+    w.Q = take(BK * A);              // v2a(V)
+    w.tab = take(C * 4 * R);         // embed i2h^T + i2h.bias
+    w.X = take(B * 2 * R);           // [af ; h]
+    w.P = take(B * A);
+    w.S = take(B * 4 * R);
+    w.c = take(B * R);
+    w.tok = (int64_t*)take(2 * B);
+    w.pk_h2a = take(packed_floats(A, R));
+    w.pk_a2h = take(packed_floats(4 * R, R));
+    w.pk_h2h = take(packed_floats(4 * R, R));
+    w.floats = off;
+    return w;
+}
+
+// Y (M,N) = [A0 | A1] [W0 | W1]^T + bias (optionally ReLU'd): every product of the model, as ONE job of the captioner's skinny
+// product launcher (xg_step.hip: xgk_skinny), over packed tiles (Bp0 / Bp1: the fast kernel) or the plain row-major weights (the
+// LDS-staged kernel).  The job does not allow a cross-workgroup split (ksplit_ok = 0), so every output element has one fixed
+// summation order and a call is bit-reproducible (xgk_gemm adds split-K partial tiles with atomics in arrival order on the
+// skinny shapes of the decoder step).
+int product(hipStream_t st, int M, int N, const float* A0, int lda0, const float* W0, int K0, const float* A1, int lda1,
+            const float* W1, int K1, const float* bias, float* Y, int ldy, bool relu = false, const float* Bp0 = nullptr,
+            const float* Bp1 = nullptr) {
+    SkArgs a{};
+    a.njobs = 1;
+    SkJob& j = a.job[0];
+    j.epi = SK_EPI_STORE;
+    j.M = M; j.N = N; j.R = N;
+    j.nseg = A1 ? 2 : 1;
+    j.C = Y; j.ldc = ldy;
+    j.relu = relu ? 1 : 0;
+    const float* As[2] = {A0, A1};
+    const float* Ws[2] = {W0, W1};
+    const float* Bps[2] = {Bp0, Bp1};
+    const int ld[2] = {lda0, lda1}, Ks[2] = {K0, K1};
+    for (int q = 0; q < j.nseg; ++q) {
+        SkSeg& sg = j.seg[q];
+        sg.A = As[q]; sg.lda = ld[q]; sg.K = Ks[q]; sg.nck = xg_cdiv(Ks[q], 32);
+        sg.B = Ws[q]; sg.ldb = Ks[q];
+        sg.Bp = Bps[q];
+    }
+    j.bias[0] = bias;
+    return xgk_skinny(st, a, 0);
+}
+
+bool params_ok(const XgpParams* p) {
+    if (!p) return false;
+    float* const* f = (float* const*)p;
+    for (int i = 0; i < kNParams; ++i)
+        if (!f[i]) return false;
+    return true;
+}
+
+bool bn_ok(const XgBnState* bn) { return bn && bn->rgb_mean && bn->rgb_var && bn->opfl_mean && bn->opfl_var; }
+
+// eval-mode encoder (pos_src/sub_modules.py:199-239) into V (B*K rows of R)
+int encoder(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
+            const float* fm, float* V, const Ws& w) {
+    const int B = d->B, K = d->K, R = d->R, BK = B * K;
+    const size_t BKR = (size_t)BK * R;
+    XgDrop nodrop;
+    nodrop.seed = 0; nodrop.site = 0; nodrop.step = 0; nodrop.thresh = 0u; nodrop.scale = 1.0f;
+    const float* feats[2] = {fr, fo};
+    const int F[2] = {d->F1, d->F2};
+    const float* ew[2] = {p->emb_rgb_w, p->emb_opfl_w};
+    const float* eb[2] = {p->emb_rgb_b, p->emb_opfl_b};
+    const float* bg[2] = {p->bn_rgb_g, p->bn_opfl_g};
+    const float* bb[2] = {p->bn_rgb_b, p->bn_opfl_b};
+    const float* rm[2] = {bn->rgb_mean, bn->opfl_mean};
+    const float* rv[2] = {bn->rgb_var, bn->opfl_var};
+    const float* wih[2] = {p->lstm_rgb_wih, p->lstm_opfl_wih};
+    const float* whh[2] = {p->lstm_rgb_whh, p->lstm_opfl_whh};
+    const float* bih[2] = {p->lstm_rgb_bih, p->lstm_opfl_bih};
+    const float* bhh[2] = {p->lstm_rgb_bhh, p->lstm_opfl_bhh};
+    for (int m = 0; m < 2; ++m) {
+        float* Z = w.Z + m * BKR;
+        float* Xe = w.Xe + m * BKR;
+        XG_TRY(product(st, BK, R, feats[m], F[m], ew[m], F[m], nullptr, 0, nullptr, 0, eb[m], Z, R));
+        // eval BatchNorm with the running statistics, ReLU, then the frame mask (the dropout is the identity)
+        XG_TRY(xgk_bn_apply(st, Z, rm[m], rv[m], bg[m], bb[m], fm, Xe, BK, R, 1e-5f, nodrop));
+        XG_TRY(product(st, BK, 4 * R, Xe, R, wih[m], R, nullptr, 0, nullptr, 0, bih[m], w.Pre + m * BKR * 4, 4 * R));
+        XG_TRY(xgk_fill(st, w.c2 + (size_t)m * B * R, 0.f, (int64_t)B * R));
+    }
+    XG_TRY(xgk_fill(st, w.hz, 0.f, (int64_t)B * R));
+    for (int k = 0; k < K; ++k) {
+        for (int m = 0; m < 2; ++m) {
+            const float* hp = k == 0 ? w.hz : w.Hcat + (size_t)(k - 1) * 2 * R + m * R;
+            const int ldh = k == 0 ? R : K * 2 * R;
+            float* S = w.S2 + (size_t)m * B * 4 * R;
+            XG_TRY(product(st, B, 4 * R, hp, ldh, whh[m], R, nullptr, 0, nullptr, 0, bhh[m], S, 4 * R));
+            LstmFwdArgs a{};
+            a.s = S; a.lds_ = 4 * R;
+            a.add = w.Pre + m * BKR * 4 + (size_t)k * 4 * R; a.ldadd = K * 4 * R;
+            a.c_prev = w.c2 + (size_t)m * B * R; a.ldcp = R;
+            a.h_prev = nullptr; a.ldhp = 0;
+            a.mask = fm + k; a.ldm = K;
+            a.gates = nullptr; a.ldg = 0;
+            a.c_out = w.c2 + (size_t)m * B * R; a.ldco = R;
+            a.h_out = w.Hcat + (size_t)k * 2 * R + m * R; a.ldho = K * 2 * R;
+            a.B = B; a.R = R; a.order = XG_ORDER_IFGO; a.mask_mode = XG_MASK_ZERO;
+            a.drop = nodrop;
+            XG_TRY(xgk_lstm_fwd(st, a));
+        }
+    }
+    // late fusion: relu(W [h_rgb ; h_opfl] + b); masked frames carry relu(b)
+    return product(st, BK, R, w.Hcat, 2 * R, p->fusion_w, 2 * R, nullptr, 0, nullptr, 0, p->fusion_b, V, R, true);
+}
+
+// encoder, init_hidden (SAModel.py:54-60: the sum of V over all K rows over the mask count) and the per-call hoisted operands, then
+// the T decoder steps
+int decode(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo, const float* fm,
+           CellHeadArgs ca, const Ws& w) {
+    const int B = d->B, K = d->K, R = d->R, A = d->A, E = d->E, C = d->C, T = d->T;
+    XG_TRY(encoder(st, d, p, bn, fr, fo, fm, w.V, w));
+    XG_TRY(xgk_masked_mean(st, w.V, fm, w.vbar, B, K, R));
+    XG_TRY(product(st, B, R, w.vbar, R, p->ih1_w, R, nullptr, 0, nullptr, 0, p->ih1_b, w.X + R, 2 * R));
+    XG_TRY(product(st, B, R, w.vbar, R, p->ic1_w, R, nullptr, 0, nullptr, 0, p->ic1_b, w.c, R));
+    XG_TRY(product(st, B * K, A, w.V, R, p->v2a_w, R, nullptr, 0, nullptr, 0, p->v2a_b, w.Q, A));
+    XG_TRY(product(st, C, 4 * R, p->embed_w, E, p->i2h_w, E, nullptr, 0, nullptr, 0, p->i2h_b, w.tab, 4 * R));
+    hipLaunchKernelGGL(pos_pack_kernel, dim3(xg_cdiv(A, 32) * xg_cdiv(R, 32)), dim3(POS_TPB), 0, st, p->h2a_w, A, R, w.pk_h2a);
+    hipLaunchKernelGGL(pos_pack_kernel, dim3(xg_cdiv(4 * R, 32) * xg_cdiv(R, 32)), dim3(POS_TPB), 0, st, p->a2h_w, 4 * R, R, w.pk_a2h);
+    hipLaunchKernelGGL(pos_pack_kernel, dim3(xg_cdiv(4 * R, 32) * xg_cdiv(R, 32)), dim3(POS_TPB), 0, st, p->h2h_w, 4 * R, R, w.pk_h2h);
+    XG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(pos_fold_bias_kernel, dim3(xg_cdiv(C * 4 * R, POS_TPB)), dim3(POS_TPB), 0, st, w.tab, p->a2h_b, p->h2h_b, C,
+                       4 * R);
+    XG_CHECK_LAUNCH();
+    ca.S = w.S; ca.tab = w.tab; ca.logit_w = p->logit_w; ca.logit_b = p->logit_b;
+    ca.X = w.X; ca.c = w.c; ca.B = B; ca.R = R; ca.C = C; ca.T = T;
+    int nsplit = STEP_TPB / R;
+    nsplit = nsplit < 1 ? 1 : (nsplit > K ? K : nsplit);
+    const size_t lds_attn = (size_t)(2 * A + K + nsplit * R) * sizeof(float), lds_cell = (size_t)(R + C) * sizeof(float);
+    const bool v4 = A % 4 == 0;
+    for (int t = 0; t < T; ++t) {
+        XG_TRY(product(st, B, A, w.X + R, 2 * R, p->h2a_w, R, nullptr, 0, nullptr, 0, p->h2a_b, w.P, A, false, w.pk_h2a));
+        if (v4) hipLaunchKernelGGL(pos_attn_kernel<true>, dim3(B), dim3(STEP_TPB), lds_attn, st, w.P, w.Q, w.V, p->a2w_w, w.X, K, R, A, nsplit);
+        else    hipLaunchKernelGGL(pos_attn_kernel<false>, dim3(B), dim3(STEP_TPB), lds_attn, st, w.P, w.Q, w.V, p->a2w_w, w.X, K, R, A, nsplit);
+        XG_CHECK_LAUNCH();
+        XG_TRY(product(st, B, 4 * R, w.X, 2 * R, p->a2h_w, R, w.X + R, 2 * R, p->h2h_w, R, nullptr, w.S, 4 * R, false, w.pk_a2h,
+                       w.pk_h2h));
+        ca.t = t;
+        hipLaunchKernelGGL(pos_cell_head_kernel, dim3(B), dim3(STEP_TPB), lds_cell, st, ca);
+        XG_CHECK_LAUNCH();
+    }
+    return XG_OK;
+}
+
+int common_checks(const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo, const float* fm,
+                  void* ws, size_t ws_bytes, bool need_t) {
+    if (!dims_ok(d, need_t) || !params_ok(p) || !bn_ok(bn) || !fr || !fo || !fm || !ws) return XG_EINVAL;
+    if (ws_bytes < ws_layout(d, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
+    return XG_OK;
+}
+
+}  // namespace
+
+extern "C" int xgp_version(void) { return XGP_VERSION; }
+extern "C" int xgp_param_count(void) { return kNParams; }
+extern "C" const char* xgp_param_name(int i) { return i >= 0 && i < kNParams ? kNames[i] : nullptr; }
+
+extern "C" int xgp_param_numel(const XgpDims* d, int i, int64_t* numel) {
+    if (!dims_ok(d, false) || i < 0 || i >= kNParams || !numel) return XG_EINVAL;
+    *numel = numel_of(d, i);
+    return XG_OK;
+}
+
+extern "C" size_t xgp_workspace_bytes(const XgpDims* d) {
+    if (!dims_ok(d, false)) return 0;
+    return ws_layout(d, nullptr).floats * sizeof(float);
+}
+
+extern "C" int xgp_encoder_fwd(void* stream, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* feats_rgb,
+                               const float* feats_opfl, const float* feat_mask, float* V, void* ws, size_t ws_bytes) {
+    XG_TRY(common_checks(d, p, bn, feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, false));
+    if (!V) return XG_EINVAL;
+    return encoder((hipStream_t)stream, d, p, bn, feats_rgb, feats_opfl, feat_mask, V, ws_layout(d, ws));
+}
+
+extern "C" int xgp_forward_tf(void* stream, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* feats_rgb,
+                              const float* feats_opfl, const float* feat_mask, const int64_t* cap_classes, const float* new_mask,
+                              float* logp, int32_t* t_out, void* ws, size_t ws_bytes) {
+    XG_TRY(common_checks(d, p, bn, feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, true));
+    if (!cap_classes || !new_mask || !logp || !t_out) return XG_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    CellHeadArgs ca{};
+    ca.cap = cap_classes; ca.new_mask = new_mask; ca.logp = logp;
+    XG_TRY(decode(st, d, p, bn, feats_rgb, feats_opfl, feat_mask, ca, ws_layout(d, ws)));
+    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, cap_classes, nullptr, d->B, d->T, 0, t_out);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+
+extern "C" int xgp_sample_greedy(void* stream, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* feats_rgb,
+                                 const float* feats_opfl, const float* feat_mask, int64_t* seq, float* seq_logp, float* states,
+                                 float* masks, int32_t* n_out, void* ws, size_t ws_bytes) {
+    XG_TRY(common_checks(d, p, bn, feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, true));
+    if (d->T < 2 || !seq || !seq_logp || !states || !masks || !n_out) return XG_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const Ws w = ws_layout(d, ws);
+    CellHeadArgs ca{};
+    ca.tok = w.tok; ca.masks = masks; ca.seq = seq; ca.seq_logp = seq_logp; ca.states = states;
+    XG_TRY(decode(st, d, p, bn, feats_rgb, feats_opfl, feat_mask, ca, w));
+    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, nullptr, masks, d->B, d->T, 1, n_out);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}

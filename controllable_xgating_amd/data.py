@@ -5,7 +5,7 @@ tensors ``SAModel.forward`` receives.  Restated from caption_src/data_io.py:27-3
 files and the per-video HDF5 feature stores (data_io.py:51-126 word -> category ids, :128-219 and :222-328 the train / test
 datasets).  Host-side numpy/torch only.  ``h5py`` is optional: ``open_feature_store`` imports it lazily; every reader takes
 any mapping ``vid -> array-like`` (an ``h5py.File`` is one), so the logic is testable without it.  The POS generator that
-writes ``postagsequence.hdf5`` (``pos_src/``) stays out of scope."""
+writes ``postagsequence.hdf5`` (``pos_src/``) is ``pos.py``: ``extract_pos_features`` fills any such mapping."""
 from __future__ import annotations
 
 import numpy as np

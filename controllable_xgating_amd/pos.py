@@ -1,0 +1,262 @@
+"""The POS sequence generator (reference pos_src/SAModel.py): the model whose greedy rollout states become the captioner's global
+POS feature (pos_src/eval_utils.py:36-75 writes them, caption_src/data_io.py:215-217 reads the last row).
+
+Inference only, in eval mode, with fp32 products.  ``PosModel`` keeps the reference's class surface and state_dict (43 entries: a
+reference checkpoint loads with ``strict=True``); its forward and greedy ``sample`` run the HIP entry points of
+include/xgate_pos.h, one host synchronisation per call (the reference's data-dependent lengths T' and n are computed on the device).
+Training (backward, train-mode BatchNorm / dropout), beam search and sampled rollouts are not implemented and raise.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _native as nv
+from . import _native_pos as npos
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class _Holder(nn.Module):
+    """Bare container so parameter names nest like the reference's sub-modules."""
+
+
+class PosModel(nn.Module):
+    """reference pos_src/SAModel.py:13-184 (eval-mode inference)."""
+
+    def __init__(self, opt):
+        super().__init__()
+        self.category_size = opt.category_size
+        self.input_encoding_size = opt.input_encoding_size
+        self.rnn_size = opt.rnn_size
+        self.att_size = opt.att_size
+        self.num_layers = getattr(opt, "num_layers", 1)
+        self.drop_prob_lm = opt.drop_prob_lm
+        self.seq_length = opt.seq_length
+        self.feat_size, self.feat_size2 = opt.feat_size, opt.feat_size2
+        R, E, A, Cn = self.rnn_size, self.input_encoding_size, self.att_size, self.category_size
+        enc = _Holder()
+        enc.visual_emb_rgb = nn.Sequential(nn.Linear(opt.feat_size, R), nn.BatchNorm1d(R), nn.ReLU(True))
+        enc.visual_emb_opfl = nn.Sequential(nn.Linear(opt.feat_size2, R), nn.BatchNorm1d(R), nn.ReLU(True))
+        enc.lstmcell_rgb = nn.LSTMCell(R, R)
+        enc.lstmcell_opfl = nn.LSTMCell(R, R)
+        enc.fusion = _Holder()
+        enc.fusion.late_fusion = nn.Sequential(nn.Linear(2 * R, R), nn.ReLU(), nn.Dropout(self.drop_prob_lm))
+        self.two_fc_encoder = enc
+        self.img_embed_h_1 = nn.Linear(R, R)
+        self.img_embed_c_1 = nn.Linear(R, R)
+        core = _Holder()
+        core.lstmcell = _Holder()
+        core.lstmcell.i2h = nn.Linear(E, 4 * R)
+        core.lstmcell.a2h = nn.Linear(R, 4 * R)
+        core.lstmcell.h2h = nn.Linear(R, 4 * R)
+        core.v2a = nn.Linear(R, A)
+        core.h2a = nn.Linear(R, A)
+        core.a2w = nn.Linear(A, 1)
+        self.lstmcore = core
+        self.embed = nn.Embedding(Cn, E)
+        self.logit = nn.Linear(R, Cn)
+        with torch.no_grad():                       # SAModel.py:37-42
+            self.embed.weight.uniform_(-0.1, 0.1)
+            self.logit.bias.fill_(0)
+            self.logit.weight.uniform_(-0.1, 0.1)
+        self._ws = {}
+
+    # ---- native plumbing
+    def _check_eval(self, *tensors):
+        if self.training:
+            raise NotImplementedError("PosModel runs in eval mode only (call .eval()): training the POS generator -- backward, "
+                                      "train-mode BatchNorm and dropout -- is not implemented")
+        for t in tensors:
+            if not t.is_cuda:
+                raise nv.XgError("PosModel needs CUDA (HIP) tensors: there is no CPU / PyTorch fallback")
+        for p in self.parameters():
+            if not p.is_cuda or p.dtype != torch.float32:
+                raise nv.XgError("PosModel parameters must be fp32 on the GPU (model.cuda())")
+
+    def _params(self):
+        L = npos.lib()
+        named = dict(self.named_parameters())
+        ptrs = []
+        for n in npos.PARAM_NAMES:
+            p = named[n]
+            if not p.is_contiguous():
+                raise nv.XgError("parameter %s is not contiguous" % n)
+            ptrs.append(p.data_ptr())
+        assert L is not None
+        return npos.XgpParams(*ptrs)
+
+    def _bn(self):
+        e = self.two_fc_encoder
+        return nv.XgBnState(e.visual_emb_rgb[1].running_mean.data_ptr(), e.visual_emb_rgb[1].running_var.data_ptr(),
+                            e.visual_emb_opfl[1].running_mean.data_ptr(), e.visual_emb_opfl[1].running_var.data_ptr())
+
+    def _dims(self, B, K, T):
+        return npos.XgpDims(B, K, self.rnn_size, self.att_size, self.input_encoding_size, self.category_size, self.feat_size,
+                            self.feat_size2, T)
+
+    def _workspace(self, dims, device):
+        L = npos.lib()
+        n = L.xgp_workspace_bytes(C.byref(dims))
+        if n == 0:
+            raise nv.XgError("xgp_workspace_bytes: invalid dims")
+        key = (device.index, n)
+        ws = self._ws.get(key)
+        if ws is None:
+            self._ws.clear()
+            ws = torch.zeros(n, dtype=torch.uint8, device=device)
+            self._ws[key] = ws
+        return ws
+
+    @staticmethod
+    def _feats(feats_rgb, feats_opfl, feat_mask):
+        f = [t.float().contiguous() for t in (feats_rgb, feats_opfl, feat_mask)]
+        if f[0].dim() != 3 or f[1].shape[:2] != f[0].shape[:2] or tuple(f[2].shape) != tuple(f[0].shape[:2]):
+            raise nv.XgError("feats_rgb (B,K,F1), feats_opfl (B,K,F2), feat_mask (B,K) expected")
+        return f
+
+    # ---- the reference's surface
+    def init_hidden(self, feat, feat_mask):
+        """SAModel.py:54-60: the encoder output summed over ALL K rows, over the mask count, through img_embed_{h,c}_1 (detached).
+        ((1,B,R), (1,B,R)); the native forward / sample compute the same thing on the device."""
+        with torch.no_grad():
+            mean = (feat.float().sum(1) / feat_mask.float().sum(1, keepdim=True)).unsqueeze(0)
+            return self.img_embed_h_1(mean), self.img_embed_c_1(mean)
+
+    def encode(self, feats_rgb, feats_opfl, feat_mask):
+        """two_fc_encoder (sub_modules.py:199-239): V (B,K,R)."""
+        self._check_eval(feats_rgb, feats_opfl, feat_mask)
+        fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
+        B, K = fm.shape
+        dims = self._dims(B, K, 1)
+        ws = self._workspace(dims, fr.device)
+        V = torch.empty(B, K, self.rnn_size, device=fr.device)
+        P, bn = self._params(), self._bn()
+        nv.check(npos.lib().xgp_encoder_fwd(_stream(), C.byref(dims), C.byref(P), C.byref(bn), fr.data_ptr(), fo.data_ptr(),
+                                            fm.data_ptr(), V.data_ptr(), ws.data_ptr(), ws.numel()), "xgp_encoder_fwd")
+        return V
+
+    def forward(self, feats_rgb, feats_opfl, feat_mask, seq, seq_mask, cap_classes, new_mask):
+        """SAModel.py:62-90: teacher-forced log-probabilities (B, T', C) over the already rolled `cap_classes` / `new_mask`
+        (prepare_pos_targets); the loop stops at the first i >= 1 whose category column is all zero.  `seq` / `seq_mask` are
+        unused, as in the reference."""
+        self._check_eval(feats_rgb, feats_opfl, feat_mask, cap_classes, new_mask)
+        fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
+        cap = cap_classes.long().contiguous()
+        nm = new_mask.float().contiguous()
+        B, K = fm.shape
+        T = cap.shape[1]
+        if cap.shape[0] != B or tuple(nm.shape) != tuple(cap.shape):
+            raise nv.XgError("cap_classes / new_mask (B,T) expected")
+        dims = self._dims(B, K, T)
+        ws = self._workspace(dims, fr.device)
+        logp = torch.empty(B, T, self.category_size, device=fr.device)
+        t_out = torch.empty(1, dtype=torch.int32, device=fr.device)
+        P, bn = self._params(), self._bn()
+        nv.check(npos.lib().xgp_forward_tf(_stream(), C.byref(dims), C.byref(P), C.byref(bn), fr.data_ptr(), fo.data_ptr(),
+                                           fm.data_ptr(), cap.data_ptr(), nm.data_ptr(), logp.data_ptr(), t_out.data_ptr(),
+                                           ws.data_ptr(), ws.numel()), "xgp_forward_tf")
+        Tp = int(t_out.item())                      # the one host synchronisation of the call
+        return logp if Tp == T else logp[:, :Tp].contiguous()
+
+    def sample(self, feats_rgb, feats_opfl, feat_mask, opt={}):
+        """SAModel.py:136-184, greedy: (seq (B,n), seqLogprobs (B,n), collect_states (B,n+1,R), collect_masks (B,n+1)).  All
+        seq_length + 1 steps run on the device (finished rows hold their state exactly), then the outputs are trimmed to the
+        reference's n."""
+        if opt.get("beam_size", 1) > 1:
+            raise NotImplementedError("POS beam search is not implemented (the reference's extraction runs --beam_size 1: "
+                                      "its sample_beam returns 2 values where eval_utils.py unpacks 4)")
+        if not opt.get("sample_max", 1):
+            raise NotImplementedError("sampled POS rollouts (sample_max = 0) are not implemented (nor are they in the reference)")
+        self._check_eval(feats_rgb, feats_opfl, feat_mask)
+        fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
+        B, K = fm.shape
+        T = self.seq_length + 1
+        dims = self._dims(B, K, T)
+        ws = self._workspace(dims, fr.device)
+        dev = fr.device
+        seq = torch.empty(B, T - 1, dtype=torch.int64, device=dev)
+        slp = torch.empty(B, T - 1, device=dev)
+        states = torch.empty(B, T, self.rnn_size, device=dev)
+        masks = torch.empty(B, T, device=dev)
+        n_out = torch.empty(1, dtype=torch.int32, device=dev)
+        P, bn = self._params(), self._bn()
+        nv.check(npos.lib().xgp_sample_greedy(_stream(), C.byref(dims), C.byref(P), C.byref(bn), fr.data_ptr(), fo.data_ptr(),
+                                              fm.data_ptr(), seq.data_ptr(), slp.data_ptr(), states.data_ptr(), masks.data_ptr(),
+                                              n_out.data_ptr(), ws.data_ptr(), ws.numel()), "xgp_sample_greedy")
+        n = int(n_out.item())                       # the one host synchronisation of the rollout
+        return seq[:, :n], slp[:, :n], states[:, :n + 1], masks[:, :n + 1]
+
+
+class ClassiferCriterion(nn.Module):
+    """pos_src/SAModel.py:201-218: masked NLL with the target rolled LEFT by one and an optional class mask (unlike the
+    captioner's criterion of the same name).  A forward that stopped early (T' < T) is scored on the first T' columns of the rolled
+    target and masks.  Inference only: the loss carries no gradient."""
+
+    def forward(self, input, target, mask, class_mask=None):
+        if not input.is_cuda:
+            raise nv.XgError("ClassiferCriterion needs CUDA (HIP) tensors")
+        B, Tp, Cn = input.shape
+        target = target.long()
+        if Tp == target.shape[1]:
+            tgt, roll = target.contiguous(), 1
+        else:
+            tgt, roll = torch.cat([target[:, 1:], target[:, :1]], 1)[:, :Tp].contiguous(), 0
+        m = mask[:, :Tp].float().contiguous()
+        m2 = None if class_mask is None else class_mask[:, :Tp].float().contiguous()
+        logp = input.detach().float().contiguous()
+        out = torch.empty(2, device=input.device)
+        nv.check(nv.lib().xg_nll_fwd(_stream(), logp.data_ptr(), tgt.data_ptr(), m.data_ptr(),
+                                     None if m2 is None else m2.data_ptr(), B, Tp, Cn, roll, out.data_ptr()), "xg_nll_fwd")
+        return out[0] / out[1]
+
+
+def prepare_pos_targets(cap_classes, class_mask):
+    """starttrain_trainpos.py:132-136 / eval_utils.py:46-50: the categories rolled RIGHT by one (the last column becomes the BOS
+    column) and new_mask = 1 up to and including the last non-zero of each row's class_mask."""
+    cap_classes = torch.as_tensor(cap_classes)
+    class_mask = torch.as_tensor(class_mask)
+    rolled = torch.cat([cap_classes[:, -1:], cap_classes[:, :-1]], dim=-1)
+    T = class_mask.shape[1]
+    nz = class_mask != 0
+    if not bool(nz.any(1).all()):
+        raise ValueError("every row of class_mask needs a non-zero entry (the reference indexes its last one)")
+    last = (T - 1) - torch.flip(nz, dims=[1]).int().argmax(1)
+    new_mask = (torch.arange(T, device=class_mask.device).unsqueeze(0) <= last.unsqueeze(1)).to(class_mask.dtype)
+    return rolled, new_mask
+
+
+def extract_pos_features(model, batches, writer, opt=None):
+    """pos_src/eval_utils.py:36-75: for every batch (feats_rgb, feats_opfl, feat_mask, cap_classes, class_mask, video_ids) -- the
+    raw, un-rolled categories as the collate_fn yields them -- the validation loss of the teacher-forced forward and the greedy
+    rollout, whose states go to `writer` (any mapping, e.g. an h5py.File): writer[vid]['states'] (n+1, R), ['masks'] (1, n+1),
+    ['tokens'] (1, n).  The first occurrence of a video id wins.  Returns the mean loss over the batches."""
+    opt = dict({"sample_max": 1, "beam_size": 1}, **(opt or {}))
+    crit = ClassiferCriterion()
+    loss_sum, n_batches = 0.0, 0
+    for feats_rgb, feats_opfl, feat_mask, cap_classes, class_mask, vids in batches:
+        cap_r, new_mask = prepare_pos_targets(cap_classes, class_mask)
+        dev = feats_rgb.device
+        cap_r, new_mask, class_mask = cap_r.to(dev), new_mask.to(dev), torch.as_tensor(class_mask).to(dev)
+        out = model(feats_rgb, feats_opfl, feat_mask, None, None, cap_r, new_mask)
+        # eval_utils.py:51 passes cap_mask as the mask; the captions' mask and new_mask cover the same positions (BOS + words)
+        loss_sum += float(crit(out, cap_r, new_mask, class_mask))
+        n_batches += 1
+        seq, _, states, masks = model.sample(feats_rgb, feats_opfl, feat_mask, opt)
+        states, masks, seq = states.cpu().numpy(), masks.cpu().numpy(), seq.cpu().numpy()
+        for i, vid in enumerate(vids):
+            if vid in writer:
+                continue
+            grp = {"states": np.ascontiguousarray(states[i]), "masks": masks[i:i + 1].copy(), "tokens": seq[i:i + 1].copy()}
+            if hasattr(writer, "create_group"):
+                g = writer.create_group(vid)
+                for k, v in grp.items():
+                    g[k] = v
+            else:
+                writer[vid] = grp
+    return loss_sum / max(n_batches, 1)
