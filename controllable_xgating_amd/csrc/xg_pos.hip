@@ -560,3 +560,537 @@ extern "C" int xgp_sample_greedy(void* stream, const XgpDims* d, const XgpParams
     XG_CHECK_LAUNCH();
     return XG_OK;
 }
+
+// ==================================================================================================================================
+// Training (include/xgate_pos_train.h): the teacher-forced iteration of pos_src/starttrain_trainpos.py:138-152.
+//
+// Forward, train mode: the eval forward's launch structure with BatchNorm over the batch statistics (running statistics updated in
+// the same launch), hash dropout at sites 0 / 1 (embeddings), 4 (fusion) and 6 (decoder cell, step t), and every activation the
+// backward needs kept in the workspace: per step p = h2a(h), alpha, af, the activated gates, h and c (before and after) and the
+// log-probabilities.  The attention of a step is the captioner's xgk_attn_fwd (it keeps alpha); the cell epilogue and the head are
+// pos_cell_head_train_kernel.
+// Backward, per step in reverse: pos_cell_head_bwd_kernel (log_softmax backward, dlogits logit_w into dh, then the cell backward with
+// the HOLD mask and the site-6 dropout), daf = ds a2h_w, xgk_attn_bwd, and dh_prev += ds h2h_w + dp h2a_w as one two-segment
+// skinny job.  After the loop every weight gradient is one batched product over the T' B rows; then the encoder in reverse.
+// ==================================================================================================================================
+#include "../../include/xgate_pos_train.h"
+
+namespace {
+
+constexpr float POS_BN_EPS = 1e-5f;
+
+XgDrop pos_drop(const XgptRun* run, uint32_t site, uint32_t step) {
+    XgDrop d;
+    d.seed = run->seed; d.site = site; d.step = step;
+    if (run->train && run->drop_p > 0.f) {
+        const double t = (double)run->drop_p * 4294967296.0;
+        d.thresh = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+        d.scale = 1.0f / (1.0f - run->drop_p);
+    } else {
+        d.thresh = 0u;
+        d.scale = 1.0f;
+    }
+    return d;
+}
+
+// pos_pack_kernel for a (K,N) row-major source: the tiles of its transpose, i.e. the B operand of Y = A W for the backward's
+// data-gradient products dX = dY W
+__global__ void __launch_bounds__(POS_TPB) pos_pack_t_kernel(const float* __restrict__ src, int N, int K, float* __restrict__ dst) {
+    __shared__ float t[32][33];
+    const int nck = (K + 31) >> 5;
+    const int tile = blockIdx.x, tn = tile / nck, kc = tile - tn * nck;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int kk = ty + 8 * r, k = kc * 32 + kk, n = tn * 32 + tx;
+        t[tx][kk] = (n < N && k < K) ? src[(size_t)k * N + n] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int o = threadIdx.x + POS_TPB * r;
+        const int q = o & 3, nn = (o >> 2) & 31, h = (o >> 7) & 1, i = o >> 8;
+        dst[(size_t)tile * 1024 + o] = t[nn][16 * h + 4 * i + q];
+    }
+}
+
+struct CellTrainArgs {
+    const float* S;              // (B,4R) af a2h^T + h h2h^T, no bias
+    const float* tab;            // (C,4R) embed i2h^T + the three biases
+    const float *logit_w, *logit_b;
+    const int64_t* cap; const float* new_mask;     // (B,T)
+    const float *h_prev, *c_prev;                   // (B,R) state before the step
+    float *h_out, *c_out;                           // (B,R) state after the step (h: after the dropout)
+    float* gates;                                   // (B,4R) activated gates, order i,f,o,g
+    float* lp;                                      // (B,C) log-probabilities of the step (saved)
+    float* logp;                                    // (B,T,C) output
+    int B, R, C, T, t;
+    XgDrop drop;
+};
+
+// one workgroup per video: pos_cell_head_kernel's teacher-forced path plus the dropout of h after the mask hold
+// (sub_modules.py:884-887: the dropped h is the state AND the head's input) and the saved gates
+__global__ void __launch_bounds__(STEP_TPB) pos_cell_head_train_kernel(CellTrainArgs a) {
+    extern __shared__ float lds[];
+    float* hs = lds;             // R
+    float* lg = lds + a.R;       // C
+    __shared__ float s_lse;
+    const int b = blockIdx.x, tid = threadIdx.x, R = a.R, C = a.C, T = a.T, t = a.t;
+    int64_t tk = a.cap[(size_t)b * T + t];
+    const float m = a.new_mask[(size_t)b * T + t];
+    tk = tk < 0 ? 0 : (tk >= C ? C - 1 : tk);
+    const float* s = a.S + (size_t)b * 4 * R;
+    const float* tb = a.tab + (size_t)tk * 4 * R;
+    float* gb = a.gates + (size_t)b * 4 * R;
+    for (int j = tid; j < R; j += STEP_TPB) {
+        const float ig = xg_sigmoid(s[j] + tb[j]), fg = xg_sigmoid(s[R + j] + tb[R + j]);
+        const float og = xg_sigmoid(s[2 * R + j] + tb[2 * R + j]), gg = xg_tanh(s[3 * R + j] + tb[3 * R + j]);
+        const float cp = a.c_prev[(size_t)b * R + j], hp = a.h_prev[(size_t)b * R + j];
+        float cn = fg * cp + ig * gg;
+        cn = cn * m + cp * (1.0f - m);
+        float hn = og * xg_tanh(cn);
+        hn = (hn * m + hp * (1.0f - m)) * xg_keep(a.drop, (uint32_t)(b * R + j));
+        gb[j] = ig; gb[R + j] = fg; gb[2 * R + j] = og; gb[3 * R + j] = gg;
+        a.c_out[(size_t)b * R + j] = cn;
+        a.h_out[(size_t)b * R + j] = hn;
+        hs[j] = hn;
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int cc = wave; cc < C; cc += STEP_WAVES) {
+        const float* wr = a.logit_w + (size_t)cc * R;
+        float acc = 0.f;
+#pragma unroll 8
+        for (int j = lane; j < R; j += 64) acc += wr[j] * hs[j];
+        acc = wave_sum(acc);
+        if (lane == 0) lg[cc] = acc + a.logit_b[cc];
+    }
+    __syncthreads();
+    if (wave == 0) {
+        float mx = -INFINITY;
+        for (int c0 = 0; c0 < C; c0 += 64) mx = fmaxf(mx, wave_max(c0 + lane < C ? lg[c0 + lane] : -INFINITY));
+        float se = 0.f;
+        for (int c0 = 0; c0 < C; c0 += 64) se += wave_sum(c0 + lane < C ? expf(lg[c0 + lane] - mx) : 0.f);
+        if (lane == 0) s_lse = mx + logf(se);
+    }
+    __syncthreads();
+    for (int cc = tid; cc < C; cc += STEP_TPB) {
+        const float v = lg[cc] - s_lse;
+        a.lp[(size_t)b * C + cc] = v;
+        a.logp[((size_t)b * T + t) * C + cc] = v;
+    }
+}
+
+struct CellBwdArgs {
+    const float* lp;             // (B,C) saved log-probabilities of the step
+    const float* dlogp;          // (B,Tp,C) incoming gradient
+    const float* logit_w;        // (C,R)
+    const float* gates;          // (B,4R) i,f,o,g
+    const float *c_prev, *c_out; // (B,R)
+    const float* new_mask;       // (B,T)
+    const float* dh_in;          // (B,R) dh of the step's output from the later steps
+    float* dh_out;               // (B,R) overwritten with (1 - m) du: the products of the step then add into it
+    float* dc;                   // (B,R) in: dc of the step's cell state, out: dc of the previous one
+    float* ds;                   // (B,4R)
+    float* dlogits;              // (B,C)
+    int B, R, C, T, Tp, t;
+    XgDrop drop;
+};
+
+// one workgroup per video, the mirror of pos_cell_head_train_kernel: dlogits = dlogp - exp(lp) sum(dlogp), dh = dlogits logit_w +
+// the carried dh, then the two_inputs_lstmcell backward (HOLD mask, dropout after the hold)
+__global__ void __launch_bounds__(STEP_TPB) pos_cell_head_bwd_kernel(CellBwdArgs a) {
+    extern __shared__ float lds[];
+    float* dl = lds;             // C
+    const int b = blockIdx.x, tid = threadIdx.x, R = a.R, C = a.C, t = a.t;
+    const int lane = tid & 63, wave = tid >> 6;
+    const float* lpb = a.lp + (size_t)b * C;
+    const float* dlp = a.dlogp + ((size_t)b * a.Tp + t) * C;
+    if (wave == 0) {
+        float sd = 0.f;
+        for (int c0 = 0; c0 < C; c0 += 64) sd += wave_sum(c0 + lane < C ? dlp[c0 + lane] : 0.f);
+        for (int cc = lane; cc < C; cc += 64) {
+            const float v = dlp[cc] - __expf(lpb[cc]) * sd;
+            dl[cc] = v;
+            a.dlogits[(size_t)b * C + cc] = v;
+        }
+    }
+    __syncthreads();
+    const float m = a.new_mask[(size_t)b * a.T + t];
+    const float* g = a.gates + (size_t)b * 4 * R;
+    float* ds = a.ds + (size_t)b * 4 * R;
+    for (int j = tid; j < R; j += STEP_TPB) {
+        float head = 0.f;
+        for (int cc = 0; cc < C; ++cc) head += dl[cc] * a.logit_w[(size_t)cc * R + j];
+        const size_t e = (size_t)b * R + j;
+        const float du = (a.dh_in[e] + head) * xg_keep(a.drop, (uint32_t)e);
+        const float ig = g[j], fg = g[R + j], og = g[2 * R + j], gg = g[3 * R + j];
+        const float cp = a.c_prev[e], tc = xg_tanh(a.c_out[e]);
+        const float dht = m * du;
+        const float dcs = a.dc[e] + dht * og * (1.0f - tc * tc);
+        const float dct = m * dcs;
+        a.dh_out[e] = (1.0f - m) * du;
+        a.dc[e] = (1.0f - m) * dcs + dct * fg;
+        ds[j] = dct * gg * ig * (1.0f - ig);
+        ds[R + j] = dct * cp * fg * (1.0f - fg);
+        ds[2 * R + j] = dht * tc * og * (1.0f - og);
+        ds[3 * R + j] = dct * ig * (1.0f - gg * gg);
+    }
+}
+
+// Hprev (B,K,R): row (b, k) = h of frame k - 1 of modality m (zero at k = 0), from Hcat (B,K,2R)
+__global__ void __launch_bounds__(POS_TPB) pos_shift_h_kernel(const float* __restrict__ Hcat, int m, int K, int R, int64_t n,
+                                                              float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * POS_TPB + threadIdx.x;
+    if (i >= n) return;
+    const int64_t row = i / R;
+    const int r = (int)(i - row * R), k = (int)(row % K);
+    out[i] = k == 0 ? 0.f : Hcat[(row - 1) * 2 * R + (size_t)m * R + r];
+}
+
+struct TWs {
+    // forward (saved)
+    float *Z[2], *Xe[2], *mean[2], *var[2], *Pre[2], *G[2], *Cs[2];
+    float *S2, *zero, *Hcat, *V, *vbar, *Q, *tab;
+    float *Hst, *Cst, *P, *ALPHA, *AF, *GD, *LP, *S, *nm;
+    int64_t* cap;
+    float *pk_h2a, *pk_a2h, *pk_h2h, *pkt_a2h, *pkt_h2h, *pkt_h2a;
+    // backward
+    float *dH[2], *dC, *DS, *DP, *DAF, *DE, *DLOG, *Xemb, *DXemb, *DVPROJ, *DV, *dVw, *dHcat, *dHrec[2], *dCrec[2][2], *dS[2],
+        *Hprev, *dX, *bn_s1, *bn_s2;
+    size_t floats;
+};
+
+TWs tws_layout(const XgpDims* d, void* base) {
+    const size_t B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, E = d->E, T = d->T, BK = B * K;
+    float* p = (float*)base;
+    size_t off = 0;
+    auto take = [&](size_t n) { float* r = p ? p + off : nullptr; off += (n + 63) / 64 * 64; return r; };
+    TWs w;
+    for (int m = 0; m < 2; ++m) {
+        w.Z[m] = take(BK * R); w.Xe[m] = take(BK * R); w.mean[m] = take(R); w.var[m] = take(R);
+        w.Pre[m] = take(BK * 4 * R); w.G[m] = take(BK * 4 * R); w.Cs[m] = take(BK * R);
+    }
+    w.S2 = take(2 * B * 4 * R); w.zero = take(B * R); w.Hcat = take(BK * 2 * R); w.V = take(BK * R); w.vbar = take(B * R);
+    w.Q = take(BK * A); w.tab = take(C * 4 * R);
+    w.Hst = take((T + 1) * B * R); w.Cst = take((T + 1) * B * R); w.P = take(T * B * A); w.ALPHA = take(T * B * K);
+    w.AF = take(T * B * R); w.GD = take(T * B * 4 * R); w.LP = take(T * B * C); w.S = take(B * 4 * R); w.nm = take(B * T);
+    w.cap = (int64_t*)take(2 * B * T);
+    w.pk_h2a = take(packed_floats(A, R)); w.pk_a2h = take(packed_floats(4 * R, R)); w.pk_h2h = take(packed_floats(4 * R, R));
+    w.pkt_a2h = take(packed_floats(R, 4 * R)); w.pkt_h2h = take(packed_floats(R, 4 * R)); w.pkt_h2a = take(packed_floats(R, A));
+    w.dH[0] = take(B * R); w.dH[1] = take(B * R); w.dC = take(B * R);
+    w.DS = take(T * B * 4 * R); w.DP = take(T * B * A); w.DAF = take(T * B * R); w.DE = take(T * B * K); w.DLOG = take(T * B * C);
+    w.Xemb = take(T * B * E); w.DXemb = take(T * B * E); w.DVPROJ = take(BK * A); w.DV = take(BK * R); w.dVw = take(BK * R);
+    w.dHcat = take(BK * 2 * R);
+    for (int m = 0; m < 2; ++m) {
+        w.dHrec[m] = take(B * R); w.dCrec[m][0] = take(B * R); w.dCrec[m][1] = take(B * R); w.dS[m] = take(BK * 4 * R);
+    }
+    w.Hprev = take(BK * R); w.dX = take(BK * R); w.bn_s1 = take(R); w.bn_s2 = take(R);
+    w.floats = off;
+    return w;
+}
+
+// Y (M,N) (+)= A0 W0 (+ A1 W1) with W_q (K_q, N) row-major: the data-gradient products of the backward as ONE skinny job (packed
+// transposed tiles Bp_q: the fast kernel; none: the LDS-staged kernel)
+int product_nn(hipStream_t st, int M, int N, float* Y, int ldy, bool acc, const float* A0, int lda0, const float* W0, int K0,
+               const float* Bp0, const float* A1 = nullptr, int lda1 = 0, const float* W1 = nullptr, int K1 = 0,
+               const float* Bp1 = nullptr) {
+    SkArgs a{};
+    a.njobs = 1;
+    SkJob& j = a.job[0];
+    j.epi = SK_EPI_STORE;
+    j.M = M; j.N = N; j.R = N;
+    j.nseg = A1 ? 2 : 1;
+    j.C = Y; j.ldc = ldy;
+    j.accumulate = acc ? 1 : 0;
+    const float* As[2] = {A0, A1};
+    const float* Ws[2] = {W0, W1};
+    const float* Bps[2] = {Bp0, Bp1};
+    const int ld[2] = {lda0, lda1}, Ks[2] = {K0, K1};
+    for (int q = 0; q < j.nseg; ++q) {
+        SkSeg& sg = j.seg[q];
+        sg.A = As[q]; sg.lda = ld[q]; sg.K = Ks[q]; sg.nck = xg_cdiv(Ks[q], 32);
+        sg.B = Ws[q]; sg.ldb = N; sg.b_ncontig = 1;
+        sg.Bp = Bps[q];
+    }
+    return xgk_skinny(st, a, 0);
+}
+
+// dW (N,K) += dY (M,N)^T X (M,K) and the bias gradient(s) of dY
+int wgrad(hipStream_t st, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx, float* dW, float* b1,
+          float* b2 = nullptr, float* b3 = nullptr) {
+    return xgk_gemm_cs(st, 0, true, false, N, K, M, dY, lddy, X, ldx, dW, K, nullptr, false, true, b1, b2, b3);
+}
+// dX (M,N) (+)= dY (M,K) W (K,N)
+int dgrad(hipStream_t st, int M, int N, int K, const float* dY, int lddy, const float* W, float* dX, int lddx, bool acc) {
+    return xgk_gemm(st, 0, false, false, M, N, K, dY, lddy, W, N, dX, lddx, nullptr, false, acc);
+}
+
+void pack(hipStream_t st, const float* W, int N, int K, float* dst, bool transposed) {
+    const dim3 grid(xg_cdiv(N, 32) * xg_cdiv(K, 32));
+    if (transposed) hipLaunchKernelGGL(pos_pack_t_kernel, grid, dim3(POS_TPB), 0, st, W, N, K, dst);
+    else hipLaunchKernelGGL(pos_pack_kernel, grid, dim3(POS_TPB), 0, st, W, N, K, dst);
+}
+
+int encoder_train(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const XgptRun* run, const float* fr,
+                  const float* fo, const float* fm, const TWs& w) {
+    const int B = d->B, K = d->K, R = d->R, BK = B * K;
+    const float* feats[2] = {fr, fo};
+    const int F[2] = {d->F1, d->F2};
+    const float* ew[2] = {p->emb_rgb_w, p->emb_opfl_w};
+    const float* eb[2] = {p->emb_rgb_b, p->emb_opfl_b};
+    const float* bg[2] = {p->bn_rgb_g, p->bn_opfl_g};
+    const float* bb[2] = {p->bn_rgb_b, p->bn_opfl_b};
+    float* rm[2] = {bn->rgb_mean, bn->opfl_mean};
+    float* rv[2] = {bn->rgb_var, bn->opfl_var};
+    const float* wih[2] = {p->lstm_rgb_wih, p->lstm_opfl_wih};
+    const float* whh[2] = {p->lstm_rgb_whh, p->lstm_opfl_whh};
+    const float* bih[2] = {p->lstm_rgb_bih, p->lstm_opfl_bih};
+    const float* bhh[2] = {p->lstm_rgb_bhh, p->lstm_opfl_bhh};
+    XgptRun nd = *run;
+    nd.drop_p = 0.f;
+    for (int m = 0; m < 2; ++m) {
+        XG_TRY(product(st, BK, R, feats[m], F[m], ew[m], F[m], nullptr, 0, nullptr, 0, eb[m], w.Z[m], R));
+        const XgDrop drop = pos_drop(run, m == 0 ? XG_SITE_EMB_RGB : XG_SITE_EMB_OPFL, 0);
+        if (run->train) {
+            // batch statistics over all B K rows (masked frames included, as nn.BatchNorm1d sees them) + the running update
+            const int rc = xgk_bn_train_fwd(st, w.Z[m], BK, R, w.mean[m], w.var[m], rm[m], rv[m], run->bn_momentum, bg[m], bb[m], fm,
+                                            w.Xe[m], POS_BN_EPS, drop);
+            if (rc == 1) {
+                XG_TRY(xgk_bn_stats(st, w.Z[m], BK, R, w.mean[m], w.var[m], rm[m], rv[m], run->bn_momentum));
+                XG_TRY(xgk_bn_apply(st, w.Z[m], w.mean[m], w.var[m], bg[m], bb[m], fm, w.Xe[m], BK, R, POS_BN_EPS, drop));
+            } else if (rc != XG_OK) {
+                return rc;
+            }
+        } else {
+            if (hipMemcpyAsync(w.mean[m], rm[m], sizeof(float) * R, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+            if (hipMemcpyAsync(w.var[m], rv[m], sizeof(float) * R, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+            XG_TRY(xgk_bn_apply(st, w.Z[m], w.mean[m], w.var[m], bg[m], bb[m], fm, w.Xe[m], BK, R, POS_BN_EPS, drop));
+        }
+        XG_TRY(product(st, BK, 4 * R, w.Xe[m], R, wih[m], R, nullptr, 0, nullptr, 0, bih[m], w.Pre[m], 4 * R));
+    }
+    XG_TRY(xgk_fill(st, w.zero, 0.f, (int64_t)B * R));
+    for (int k = 0; k < K; ++k) {
+        for (int m = 0; m < 2; ++m) {
+            const float* hp = k == 0 ? w.zero : w.Hcat + (size_t)(k - 1) * 2 * R + m * R;
+            float* S = w.S2 + (size_t)m * B * 4 * R;
+            XG_TRY(product(st, B, 4 * R, hp, k == 0 ? R : K * 2 * R, whh[m], R, nullptr, 0, nullptr, 0, bhh[m], S, 4 * R));
+            LstmFwdArgs a{};
+            a.s = S; a.lds_ = 4 * R;
+            a.add = w.Pre[m] + (size_t)k * 4 * R; a.ldadd = K * 4 * R;
+            a.c_prev = k == 0 ? w.zero : w.Cs[m] + (size_t)(k - 1) * R; a.ldcp = k == 0 ? R : K * R;
+            a.h_prev = nullptr; a.ldhp = 0;
+            a.mask = fm + k; a.ldm = K;
+            a.gates = w.G[m] + (size_t)k * 4 * R; a.ldg = K * 4 * R;
+            a.c_out = w.Cs[m] + (size_t)k * R; a.ldco = K * R;
+            a.h_out = w.Hcat + (size_t)k * 2 * R + m * R; a.ldho = K * 2 * R;
+            a.B = B; a.R = R; a.order = XG_ORDER_IFGO; a.mask_mode = XG_MASK_ZERO;
+            a.drop = pos_drop(&nd, 0, 0);
+            XG_TRY(xgk_lstm_fwd(st, a));
+        }
+    }
+    // late fusion: dropout(relu(W [h_rgb ; h_opfl] + b)) (sub_modules.py:63-66)
+    XG_TRY(product(st, BK, R, w.Hcat, 2 * R, p->fusion_w, 2 * R, nullptr, 0, nullptr, 0, p->fusion_b, w.V, R, true));
+    return xgk_relu_drop_fwd(st, w.V, (int64_t)BK * R, pos_drop(run, XG_SITE_FUSION, 0));
+}
+
+int forward_train(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const XgptRun* run, const float* fr,
+                  const float* fo, const float* fm, const int64_t* cap, const float* nm, float* logp, const TWs& w) {
+    const int B = d->B, K = d->K, R = d->R, A = d->A, E = d->E, C = d->C, T = d->T;
+    const size_t BR = (size_t)B * R;
+    if (hipMemcpyAsync(w.cap, cap, sizeof(int64_t) * B * T, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+    if (hipMemcpyAsync(w.nm, nm, sizeof(float) * B * T, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+    XG_TRY(encoder_train(st, d, p, bn, run, fr, fo, fm, w));
+    XG_TRY(xgk_masked_mean(st, w.V, fm, w.vbar, B, K, R));                 // (detached: SAModel.py:54-60)
+    XG_TRY(product(st, B, R, w.vbar, R, p->ih1_w, R, nullptr, 0, nullptr, 0, p->ih1_b, w.Hst, R));
+    XG_TRY(product(st, B, R, w.vbar, R, p->ic1_w, R, nullptr, 0, nullptr, 0, p->ic1_b, w.Cst, R));
+    XG_TRY(product(st, B * K, A, w.V, R, p->v2a_w, R, nullptr, 0, nullptr, 0, p->v2a_b, w.Q, A));
+    XG_TRY(product(st, C, 4 * R, p->embed_w, E, p->i2h_w, E, nullptr, 0, nullptr, 0, p->i2h_b, w.tab, 4 * R));
+    pack(st, p->h2a_w, A, R, w.pk_h2a, false);
+    pack(st, p->a2h_w, 4 * R, R, w.pk_a2h, false);
+    pack(st, p->h2h_w, 4 * R, R, w.pk_h2h, false);
+    XG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(pos_fold_bias_kernel, dim3(xg_cdiv(C * 4 * R, POS_TPB)), dim3(POS_TPB), 0, st, w.tab, p->a2h_b, p->h2h_b, C,
+                       4 * R);
+    XG_CHECK_LAUNCH();
+    CellTrainArgs ca{};
+    ca.S = w.S; ca.tab = w.tab; ca.logit_w = p->logit_w; ca.logit_b = p->logit_b;
+    ca.cap = w.cap; ca.new_mask = w.nm; ca.logp = logp;
+    ca.B = B; ca.R = R; ca.C = C; ca.T = T;
+    const size_t lds_cell = (size_t)(R + C) * sizeof(float);
+    for (int t = 0; t < T; ++t) {
+        const float* h = w.Hst + t * BR;
+        float* P = w.P + (size_t)t * B * A;
+        float* af = w.AF + t * BR;
+        XG_TRY(product(st, B, A, h, R, p->h2a_w, R, nullptr, 0, nullptr, 0, p->h2a_b, P, A, false, w.pk_h2a));
+        XG_TRY(xgk_attn_fwd(st, P, w.Q, w.V, p->a2w_w, w.ALPHA + (size_t)t * B * K, af, B, K, R, A));
+        XG_TRY(product(st, B, 4 * R, af, R, p->a2h_w, R, h, R, p->h2h_w, R, nullptr, w.S, 4 * R, false, w.pk_a2h, w.pk_h2h));
+        ca.t = t;
+        ca.h_prev = h; ca.c_prev = w.Cst + t * BR;
+        ca.h_out = w.Hst + (t + 1) * BR; ca.c_out = w.Cst + (t + 1) * BR;
+        ca.gates = w.GD + (size_t)t * B * 4 * R;
+        ca.lp = w.LP + (size_t)t * B * C;
+        ca.drop = pos_drop(run, XG_SITE_L1, (uint32_t)t);
+        hipLaunchKernelGGL(pos_cell_head_train_kernel, dim3(B), dim3(STEP_TPB), lds_cell, st, ca);
+        XG_CHECK_LAUNCH();
+    }
+    return XG_OK;
+}
+
+int encoder_bwd(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgpParams* g, const XgptRun* run, const float* fr,
+                const float* fo, const float* fm, const TWs& w) {
+    const int B = d->B, K = d->K, R = d->R, BK = B * K;
+    const float* feats[2] = {fr, fo};
+    const int F[2] = {d->F1, d->F2};
+    const float* wih[2] = {p->lstm_rgb_wih, p->lstm_opfl_wih};
+    const float* whh[2] = {p->lstm_rgb_whh, p->lstm_opfl_whh};
+    const float* bg[2] = {p->bn_rgb_g, p->bn_opfl_g};
+    float* g_wih[2] = {g->lstm_rgb_wih, g->lstm_opfl_wih};
+    float* g_whh[2] = {g->lstm_rgb_whh, g->lstm_opfl_whh};
+    float* g_bih[2] = {g->lstm_rgb_bih, g->lstm_opfl_bih};
+    float* g_bhh[2] = {g->lstm_rgb_bhh, g->lstm_opfl_bhh};
+    float* g_bg[2] = {g->bn_rgb_g, g->bn_opfl_g};
+    float* g_bb[2] = {g->bn_rgb_b, g->bn_opfl_b};
+    float* g_ew[2] = {g->emb_rgb_w, g->emb_opfl_w};
+    float* g_eb[2] = {g->emb_rgb_b, g->emb_opfl_b};
+    XgptRun nd = *run;
+    nd.drop_p = 0.f;
+    // fusion: dVw = dV keep (V > 0), then its weight gradient and dHcat
+    XG_TRY(xgk_relu_drop_bwd(st, w.dVw, w.V, (int64_t)BK * R, pos_drop(run, XG_SITE_FUSION, 0), w.DV));
+    XG_TRY(wgrad(st, BK, R, 2 * R, w.dVw, R, w.Hcat, 2 * R, g->fusion_w, g->fusion_b));
+    XG_TRY(dgrad(st, BK, 2 * R, R, w.dVw, R, p->fusion_w, w.dHcat, 2 * R, false));
+    for (int m = 0; m < 2; ++m) {
+        XG_TRY(xgk_fill(st, w.dHrec[m], 0.f, (int64_t)B * R));
+        XG_TRY(xgk_fill(st, w.dCrec[m][0], 0.f, (int64_t)B * R));
+    }
+    int c = 0;
+    auto cell = [&](int m, int i) {
+        LstmBwdArgs a{};
+        a.gates = w.G[m] + (size_t)i * 4 * R; a.ldg = K * 4 * R;
+        a.c_prev = i == 0 ? w.zero : w.Cs[m] + (size_t)(i - 1) * R; a.ldcp = i == 0 ? R : K * R;
+        a.c_out = w.Cs[m] + (size_t)i * R; a.ldco = K * R;
+        a.mask = fm + i; a.ldm = K;
+        a.dh_out = w.dHcat + (size_t)i * 2 * R + m * R; a.lddh = K * 2 * R;
+        a.dh_add = w.dHrec[m]; a.lddha = R;
+        a.dc_out = w.dCrec[m][c]; a.lddc = R;
+        a.ds = w.dS[m] + (size_t)i * 4 * R; a.ldds = K * 4 * R;
+        a.dc_prev = w.dCrec[m][c ^ 1]; a.lddcp = R;
+        a.dh_prev = nullptr; a.lddhp = 0;
+        a.B = B; a.R = R; a.order = XG_ORDER_IFGO; a.mask_mode = XG_MASK_ZERO;
+        a.drop = pos_drop(&nd, 0, 0);
+        return a;
+    };
+    for (int i = K - 1; i >= 0; --i) {
+        XG_TRY(xgk_lstm_bwd2(st, cell(0, i), cell(1, i)));
+        c ^= 1;
+        if (i > 0)
+            for (int m = 0; m < 2; ++m)
+                XG_TRY(product_nn(st, B, R, w.dHrec[m], R, false, w.dS[m] + (size_t)i * 4 * R, K * 4 * R, whh[m], 4 * R, nullptr));
+    }
+    for (int m = 0; m < 2; ++m) {
+        const int64_t n = (int64_t)BK * R;
+        hipLaunchKernelGGL(pos_shift_h_kernel, dim3((unsigned)xg_cdiv64(n, POS_TPB)), dim3(POS_TPB), 0, st, w.Hcat, m, K, R, n, w.Hprev);
+        XG_CHECK_LAUNCH();
+        XG_TRY(wgrad(st, BK, 4 * R, R, w.dS[m], 4 * R, w.Hprev, R, g_whh[m], g_bih[m], g_bhh[m]));
+        XG_TRY(wgrad(st, BK, 4 * R, R, w.dS[m], 4 * R, w.Xe[m], R, g_wih[m], nullptr));
+        XG_TRY(dgrad(st, BK, R, 4 * R, w.dS[m], 4 * R, wih[m], w.dX, R, false));
+        // BatchNorm + ReLU + dropout + frame mask backward (sub_modules.py:121-123, :204)
+        XG_TRY(xgk_fill(st, w.bn_s1, 0.f, R));
+        XG_TRY(xgk_fill(st, w.bn_s2, 0.f, R));
+        XG_TRY(xgk_bn_bwd_reduce(st, w.dX, w.Xe[m], w.Z[m], w.mean[m], w.var[m], fm, BK, R, POS_BN_EPS,
+                                 pos_drop(run, m == 0 ? XG_SITE_EMB_RGB : XG_SITE_EMB_OPFL, 0), w.bn_s1, w.bn_s2));
+        XG_TRY(xgk_bn_bwd_apply(st, w.dX, w.Z[m], w.mean[m], w.var[m], bg[m], w.bn_s1, w.bn_s2, BK, R, POS_BN_EPS, run->train != 0,
+                                g_bb[m], g_bg[m]));
+        XG_TRY(wgrad(st, BK, R, F[m], w.dX, R, feats[m], F[m], g_ew[m], g_eb[m]));
+    }
+    return XG_OK;
+}
+
+int backward(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgpParams* g, const XgptRun* run, const float* fr,
+             const float* fo, const float* fm, int Tp, const float* dlogp, const TWs& w) {
+    const int B = d->B, K = d->K, R = d->R, A = d->A, E = d->E, C = d->C, T = d->T, BK = B * K, TB = Tp * B;
+    const size_t BR = (size_t)B * R;
+    pack(st, p->a2h_w, R, 4 * R, w.pkt_a2h, true);
+    pack(st, p->h2h_w, R, 4 * R, w.pkt_h2h, true);
+    pack(st, p->h2a_w, R, A, w.pkt_h2a, true);
+    XG_CHECK_LAUNCH();
+    XG_TRY(xgk_fill(st, w.dH[0], 0.f, (int64_t)BR));
+    XG_TRY(xgk_fill(st, w.dC, 0.f, (int64_t)BR));
+    CellBwdArgs cb{};
+    cb.dlogp = dlogp; cb.logit_w = p->logit_w; cb.new_mask = w.nm; cb.dc = w.dC;
+    cb.B = B; cb.R = R; cb.C = C; cb.T = T; cb.Tp = Tp;
+    int cur = 0;
+    for (int t = Tp - 1; t >= 0; --t) {
+        float* ds = w.DS + (size_t)t * B * 4 * R;
+        float* dp = w.DP + (size_t)t * B * A;
+        float* daf = w.DAF + t * BR;
+        cb.t = t;
+        cb.lp = w.LP + (size_t)t * B * C;
+        cb.gates = w.GD + (size_t)t * B * 4 * R;
+        cb.c_prev = w.Cst + t * BR; cb.c_out = w.Cst + (t + 1) * BR;
+        cb.dh_in = w.dH[cur]; cb.dh_out = w.dH[cur ^ 1];
+        cb.ds = ds; cb.dlogits = w.DLOG + (size_t)t * B * C;
+        cb.drop = pos_drop(run, XG_SITE_L1, (uint32_t)t);
+        hipLaunchKernelGGL(pos_cell_head_bwd_kernel, dim3(B), dim3(STEP_TPB), (size_t)C * sizeof(float), st, cb);
+        XG_CHECK_LAUNCH();
+        XG_TRY(product_nn(st, B, R, daf, R, false, ds, 4 * R, p->a2h_w, 4 * R, w.pkt_a2h));
+        XG_TRY(xgk_attn_bwd(st, daf, R, w.P + (size_t)t * B * A, w.Q, w.V, p->a2w_w, w.ALPHA + (size_t)t * B * K,
+                            w.DE + (size_t)t * B * K, dp, B, K, R, A));
+        XG_TRY(product_nn(st, B, R, w.dH[cur ^ 1], R, true, ds, 4 * R, p->h2h_w, 4 * R, w.pkt_h2h, dp, A, p->h2a_w, A, w.pkt_h2a));
+        cur ^= 1;
+    }
+    // batched parameter gradients over the T' B rows (row t B + b)
+    XG_TRY(xgk_embed_gather(st, p->embed_w, E, w.cap, B, T, 1, TB, C, w.Xemb, E));
+    XG_TRY(wgrad(st, TB, 4 * R, E, w.DS, 4 * R, w.Xemb, E, g->i2h_w, g->i2h_b, g->a2h_b, g->h2h_b));   // (the three folded biases)
+    XG_TRY(wgrad(st, TB, 4 * R, R, w.DS, 4 * R, w.AF, R, g->a2h_w, nullptr));
+    XG_TRY(wgrad(st, TB, 4 * R, R, w.DS, 4 * R, w.Hst, R, g->h2h_w, nullptr));
+    XG_TRY(wgrad(st, TB, A, R, w.DP, A, w.Hst, R, g->h2a_w, g->h2a_b));
+    XG_TRY(wgrad(st, TB, C, R, w.DLOG, C, w.Hst + BR, R, g->logit_w, g->logit_b));
+    XG_TRY(dgrad(st, TB, E, 4 * R, w.DS, 4 * R, p->i2h_w, w.DXemb, E, false));
+    XG_TRY(xgk_embed_scatter_add(st, g->embed_w, E, w.cap, B, T, 1, TB, C, w.DXemb, E));
+    // attention after the loop: dV (plain store), d v2a(V) and a2w.weight; then v2a
+    XG_TRY(xgk_attn_post_dV(st, w.P, w.Q, p->a2w_w, w.DE, w.DVPROJ, g->a2w_w, w.ALPHA, w.DAF, R, (int64_t)BR, w.DV, Tp, B, K, A, R));
+    XG_TRY(wgrad(st, BK, A, R, w.DVPROJ, A, w.V, R, g->v2a_w, g->v2a_b));
+    XG_TRY(dgrad(st, BK, R, A, w.DVPROJ, A, p->v2a_w, w.DV, R, true));
+    // init_hidden: h0 / c0 = img_embed_{h,c}_1(vbar), vbar detached
+    XG_TRY(wgrad(st, B, R, R, w.dH[cur], R, w.vbar, R, g->ih1_w, g->ih1_b));
+    XG_TRY(wgrad(st, B, R, R, w.dC, R, w.vbar, R, g->ic1_w, g->ic1_b));
+    return encoder_bwd(st, d, p, g, run, fr, fo, fm, w);
+}
+
+bool run_ok(const XgptRun* run) {
+    return run && run->drop_p >= 0.f && run->drop_p < 1.f && run->bn_momentum >= 0.f && run->bn_momentum <= 1.f;
+}
+
+}  // namespace
+
+extern "C" int xgpt_version(void) { return XGPT_VERSION; }
+
+extern "C" size_t xgpt_workspace_bytes(const XgpDims* d) {
+    if (!dims_ok(d, true)) return 0;
+    return tws_layout(d, nullptr).floats * sizeof(float);
+}
+
+extern "C" int xgpt_forward_train(void* stream, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const XgptRun* run,
+                                  const float* feats_rgb, const float* feats_opfl, const float* feat_mask, const int64_t* cap_classes,
+                                  const float* new_mask, float* logp, int32_t* t_out, void* ws, size_t ws_bytes) {
+    if (!dims_ok(d, true) || !params_ok(p) || !bn_ok(bn) || !run_ok(run) || !feats_rgb || !feats_opfl || !feat_mask || !cap_classes ||
+        !new_mask || !logp || !t_out || !ws)
+        return XG_EINVAL;
+    if (ws_bytes < tws_layout(d, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    XG_TRY(forward_train(st, d, p, bn, run, feats_rgb, feats_opfl, feat_mask, cap_classes, new_mask, logp, tws_layout(d, ws)));
+    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, cap_classes, nullptr, d->B, d->T, 0, t_out);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+
+extern "C" int xgpt_backward(void* stream, const XgpDims* d, const XgpParams* p, const XgpParams* g, const XgptRun* run,
+                             const float* feats_rgb, const float* feats_opfl, const float* feat_mask, int32_t Tp, const float* dlogp,
+                             void* ws, size_t ws_bytes) {
+    if (!dims_ok(d, true) || !params_ok(p) || !params_ok(g) || !run_ok(run) || !feats_rgb || !feats_opfl || !feat_mask || !dlogp ||
+        !ws || Tp < 1 || Tp > d->T)
+        return XG_EINVAL;
+    if (ws_bytes < tws_layout(d, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
+    return backward((hipStream_t)stream, d, p, g, run, feats_rgb, feats_opfl, feat_mask, Tp, dlogp, tws_layout(d, ws));
+}

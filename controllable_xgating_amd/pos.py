@@ -1,10 +1,12 @@
 """The POS sequence generator (reference pos_src/SAModel.py): the model whose greedy rollout states become the captioner's global
 POS feature (pos_src/eval_utils.py:36-75 writes them, caption_src/data_io.py:215-217 reads the last row).
 
-Inference only, in eval mode, with fp32 products.  ``PosModel`` keeps the reference's class surface and state_dict (43 entries: a
-reference checkpoint loads with ``strict=True``); its forward and greedy ``sample`` run the HIP entry points of
-include/xgate_pos.h, one host synchronisation per call (the reference's data-dependent lengths T' and n are computed on the device).
-Training (backward, train-mode BatchNorm / dropout), beam search and sampled rollouts are not implemented and raise.
+fp32 products.  ``PosModel`` keeps the reference's class surface and state_dict (43 entries: a reference checkpoint loads with
+``strict=True``); its eval forward and greedy ``sample`` run the HIP entry points of include/xgate_pos.h, one host synchronisation per
+call (the reference's data-dependent lengths T' and n are computed on the device).  In train mode the teacher-forced forward runs
+include/xgate_pos_train.h (BatchNorm over the batch statistics, hash dropout) and ``loss.backward()`` its HIP backward; the parameters
+live in one flat buffer (``flat_parameters()`` / ``flat_grads()``) so that ``train.ClipAdam`` updates them in one launch.  Train-mode
+``sample()``, beam search and sampled rollouts are not implemented and raise.
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ import torch.nn as nn
 
 from . import _native as nv
 from . import _native_pos as npos
+from . import _native_pos_train as npt
 
 
 def _stream():
@@ -66,18 +69,129 @@ class PosModel(nn.Module):
             self.logit.bias.fill_(0)
             self.logit.weight.uniform_(-0.1, 0.1)
         self._ws = {}
+        self._tws = None                # training workspace: the saved activations of the last train-mode forward
+        self._train_gen = 0             # bumped by every train-mode forward: a backward of an older one must not read them
+        self._flat = self._gflat = None
+        self._offsets = None
+        self._call = 0
+        self.dropout_seed = None        # fixed seed of the dropout hash (tests: a checker regenerates the masks); None = fresh per call
+        self.ss_prob = 0.0              # accepted and ignored: both branches of SAModel.py:76-79 feed the ground truth
 
     # ---- native plumbing
     def _check_eval(self, *tensors):
         if self.training:
-            raise NotImplementedError("PosModel runs in eval mode only (call .eval()): training the POS generator -- backward, "
-                                      "train-mode BatchNorm and dropout -- is not implemented")
+            raise NotImplementedError("this PosModel entry point runs in eval mode only (call .eval()): train mode covers the "
+                                      "teacher-forced forward and its backward")
+        self._check_device(*tensors)
+
+    def _check_device(self, *tensors):
         for t in tensors:
             if not t.is_cuda:
                 raise nv.XgError("PosModel needs CUDA (HIP) tensors: there is no CPU / PyTorch fallback")
         for p in self.parameters():
             if not p.is_cuda or p.dtype != torch.float32:
                 raise nv.XgError("PosModel parameters must be fp32 on the GPU (model.cuda())")
+
+    def _plist(self):
+        named = dict(self.named_parameters())
+        npos.lib()
+        return [named[n] for n in npos.PARAM_NAMES]
+
+    def _ensure_flat(self):
+        """All parameters live in ONE flat fp32 buffer (one Adam launch); the nn.Parameters are views into it.  Rebuilt when
+        .cuda() / .to() replaced the storages."""
+        plist = self._plist()
+        if self._flat is not None and self._flat.device == plist[0].device:
+            base = self._flat.data_ptr()
+            if all(p.data_ptr() == base + 4 * off for p, off in zip(plist, self._offsets)):
+                return
+        if not plist[0].is_cuda:
+            raise nv.XgError("PosModel trains on the GPU only: call model.cuda() first (no CPU path)")
+        total = sum((p.numel() + 63) // 64 * 64 for p in plist)
+        flat = torch.zeros(total, dtype=torch.float32, device=plist[0].device)
+        gflat = torch.zeros_like(flat)
+        off, offsets = 0, []
+        for p in plist:
+            if p.dtype != torch.float32:
+                raise nv.XgError("fp32 parameters only")
+            k = p.numel()
+            v = flat[off:off + k].view_as(p)
+            v.copy_(p.data)
+            had_grad = p.grad is not None
+            if had_grad:
+                gflat[off:off + k].view_as(p).copy_(p.grad)
+            p.data = v
+            p.grad = gflat[off:off + k].view_as(p) if had_grad else None
+            offsets.append(off)
+            off += (k + 63) // 64 * 64
+        self._flat, self._gflat, self._offsets = flat, gflat, offsets
+
+    def flat_parameters(self):
+        self._ensure_flat()
+        return self._flat
+
+    def flat_grads(self):
+        """Flat gradient buffer; binds every p.grad to its slice (zeroing is the caller's zero_grad)."""
+        self._ensure_flat()
+        base = self._gflat.data_ptr()
+        for p, off in zip(self._plist(), self._offsets):
+            if p.grad is None or p.grad.data_ptr() != base + 4 * off:
+                v = self._gflat[off:off + p.numel()].view_as(p)
+                if p.grad is not None:
+                    v.copy_(p.grad)
+                else:
+                    v.zero_()
+                p.grad = v
+        return self._gflat
+
+    def mark_params_changed(self, **kw):
+        """train.ClipAdam's notice that a kernel rewrote the flat buffer.  Nothing to do: every call reads the parameters afresh
+        (the decoder's packed tiles are rebuilt per call)."""
+
+    def _grads_struct(self):
+        """XgpParams of gradient pointers (the library ADDS into them): the flat gradient buffer when every p.grad is bound to
+        it (flat_grads()), else a fresh zero buffer whose views autograd then accumulates."""
+        self._ensure_flat()
+        self._grad_writes = getattr(self, "_grad_writes", 0) + 1
+        plist = self._plist()
+        base = self._gflat.data_ptr()
+        if all(p.grad is not None and p.grad.data_ptr() == base + 4 * off for p, off in zip(plist, self._offsets)):
+            g = None
+            base_g = base
+        else:
+            g = torch.zeros_like(self._flat)
+            base_g = g.data_ptr()
+        s = npos.XgpParams(*[base_g + 4 * off for off in self._offsets])
+        views = [None] * len(plist) if g is None else [g[off:off + p.numel()].view_as(p) for p, off in zip(plist, self._offsets)]
+        return s, views
+
+    def _run(self):
+        r = npt.XgptRun()
+        r.train = 1 if self.training else 0
+        r.drop_p = float(self.drop_prob_lm or 0.0)
+        if self.dropout_seed is not None:
+            seed = int(self.dropout_seed)
+        else:
+            self._call += 1
+            seed = int(torch.initial_seed()) * 2654435761 + self._call * 40503
+        r.seed = seed & 0xFFFFFFFF
+        r.bn_momentum = 0.1
+        return r
+
+    def _bump_bn(self, n=1):
+        if self.training:
+            e = self.two_fc_encoder
+            ts = [m.num_batches_tracked for m in (e.visual_emb_rgb[1], e.visual_emb_opfl[1]) if m.num_batches_tracked is not None]
+            if ts:
+                torch._foreach_add_(ts, n)
+
+    def _train_workspace(self, dims, device):
+        n = npt.lib().xgpt_workspace_bytes(C.byref(dims))
+        if n == 0:
+            raise nv.XgError("xgpt_workspace_bytes: invalid dims")
+        if self._tws is None or self._tws.device != device or self._tws.numel() < n:
+            self._tws = torch.empty(n, dtype=torch.uint8, device=device)
+        return self._tws
 
     def _params(self):
         L = npos.lib()
@@ -144,7 +258,20 @@ class PosModel(nn.Module):
     def forward(self, feats_rgb, feats_opfl, feat_mask, seq, seq_mask, cap_classes, new_mask):
         """SAModel.py:62-90: teacher-forced log-probabilities (B, T', C) over the already rolled `cap_classes` / `new_mask`
         (prepare_pos_targets); the loop stops at the first i >= 1 whose category column is all zero.  `seq` / `seq_mask` are
-        unused, as in the reference."""
+        unused, as in the reference.  In train mode: BatchNorm over the batch (running statistics and num_batches_tracked
+        updated), dropout, and a result that carries a gradient."""
+        if self.training:
+            for t in (feats_rgb, feats_opfl, feat_mask, cap_classes, new_mask):
+                if not t.is_cuda:
+                    raise NotImplementedError("PosModel trains on the GPU only: there is no CPU path (model.cuda() and CUDA inputs)")
+            self._check_device()
+            self._ensure_flat()
+            fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
+            cap = cap_classes.detach().long().contiguous()
+            nm = new_mask.detach().float().contiguous()
+            if cap.shape[0] != fm.shape[0] or tuple(nm.shape) != tuple(cap.shape):
+                raise nv.XgError("cap_classes / new_mask (B,T) expected")
+            return _PosTrainFunction.apply(self, fr.detach(), fo.detach(), fm.detach(), cap, nm, *self._plist())
         self._check_eval(feats_rgb, feats_opfl, feat_mask, cap_classes, new_mask)
         fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
         cap = cap_classes.long().contiguous()
@@ -193,10 +320,48 @@ class PosModel(nn.Module):
         return seq[:, :n], slp[:, :n], states[:, :n + 1], masks[:, :n + 1]
 
 
+class _PosTrainFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, fr, fo, fm, cap, nm, *params):
+        B, K = fm.shape
+        T = cap.shape[1]
+        dev = fr.device
+        dims = model._dims(B, K, T)
+        ws = model._train_workspace(dims, dev)
+        logp = torch.empty(B, T, model.category_size, device=dev)
+        t_out = torch.empty(1, dtype=torch.int32, device=dev)
+        run = model._run()
+        P, bn = model._params(), model._bn()
+        nv.check(npt.lib().xgpt_forward_train(_stream(), C.byref(dims), C.byref(P), C.byref(bn), C.byref(run), fr.data_ptr(),
+                                              fo.data_ptr(), fm.data_ptr(), cap.data_ptr(), nm.data_ptr(), logp.data_ptr(),
+                                              t_out.data_ptr(), ws.data_ptr(), ws.numel()), "xgpt_forward_train")
+        model._bump_bn()
+        model._train_gen += 1
+        Tp = int(t_out.item())                      # the one host synchronisation of the iteration
+        ctx.model, ctx.dims, ctx.run, ctx.Tp, ctx.gen, ctx.keep = model, dims, run, Tp, model._train_gen, (fr, fo, fm)
+        return logp if Tp == T else logp[:, :Tp].contiguous()
+
+    @staticmethod
+    def backward(ctx, dlogp):
+        model = ctx.model
+        if model._train_gen != ctx.gen or model._tws is None:
+            raise nv.XgError("PosModel backward: a later train-mode forward has overwritten this forward's saved activations "
+                             "(call backward before the next forward)")
+        fr, fo, fm = ctx.keep
+        ws = model._tws
+        gs, views = model._grads_struct()
+        dl = dlogp.detach().float().contiguous()
+        run = ctx.run
+        nv.check(npt.lib().xgpt_backward(_stream(), C.byref(ctx.dims), C.byref(model._params()), C.byref(gs), C.byref(run),
+                                         fr.data_ptr(), fo.data_ptr(), fm.data_ptr(), ctx.Tp, dl.data_ptr(), ws.data_ptr(),
+                                         ws.numel()), "xgpt_backward")
+        return (None,) * 6 + tuple(views)
+
+
 class ClassiferCriterion(nn.Module):
     """pos_src/SAModel.py:201-218: masked NLL with the target rolled LEFT by one and an optional class mask (unlike the
     captioner's criterion of the same name).  A forward that stopped early (T' < T) is scored on the first T' columns of the rolled
-    target and masks.  Inference only: the loss carries no gradient."""
+    target and masks.  The loss carries a gradient when its input requires one."""
 
     def forward(self, input, target, mask, class_mask=None):
         if not input.is_cuda:
@@ -209,6 +374,9 @@ class ClassiferCriterion(nn.Module):
             tgt, roll = torch.cat([target[:, 1:], target[:, :1]], 1)[:, :Tp].contiguous(), 0
         m = mask[:, :Tp].float().contiguous()
         m2 = None if class_mask is None else class_mask[:, :Tp].float().contiguous()
+        if input.requires_grad and torch.is_grad_enabled():
+            from .model import _NLLFunction
+            return _NLLFunction.apply(input, tgt, m, m2, roll)
         logp = input.detach().float().contiguous()
         out = torch.empty(2, device=input.device)
         nv.check(nv.lib().xg_nll_fwd(_stream(), logp.data_ptr(), tgt.data_ptr(), m.data_ptr(),
@@ -216,15 +384,16 @@ class ClassiferCriterion(nn.Module):
         return out[0] / out[1]
 
 
-def prepare_pos_targets(cap_classes, class_mask):
+def prepare_pos_targets(cap_classes, class_mask, check=True):
     """starttrain_trainpos.py:132-136 / eval_utils.py:46-50: the categories rolled RIGHT by one (the last column becomes the BOS
-    column) and new_mask = 1 up to and including the last non-zero of each row's class_mask."""
+    column) and new_mask = 1 up to and including the last non-zero of each row's class_mask.  `check`: raise when a row of
+    class_mask has no non-zero entry (a host synchronisation for a device tensor); unchecked, such a row gets new_mask all ones."""
     cap_classes = torch.as_tensor(cap_classes)
     class_mask = torch.as_tensor(class_mask)
     rolled = torch.cat([cap_classes[:, -1:], cap_classes[:, :-1]], dim=-1)
     T = class_mask.shape[1]
     nz = class_mask != 0
-    if not bool(nz.any(1).all()):
+    if check and not bool(nz.any(1).all()):
         raise ValueError("every row of class_mask needs a non-zero entry (the reference indexes its last one)")
     last = (T - 1) - torch.flip(nz, dims=[1]).int().argmax(1)
     new_mask = (torch.arange(T, device=class_mask.device).unsqueeze(0) <= last.unsqueeze(1)).to(class_mask.dtype)
