@@ -9,11 +9,16 @@ batch of 128 videos: zero_grad -> CG encoder fwd -> 21 decoder steps -> both hea
 backward -> (N>1: ONE RCCL all-reduce of the flat gradient) -> clip + Adam.  Inputs are synthetic
  and already resident in HBM.  value = N * B * T * K / max-over-ranks wall time.
 
-Besides the contract line it reports
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the
+line (with the whole iteration against the matrix roof, which needs no run of its own).  --full adds
   roofline     : the decoder-step launch group (xg_step_fwd = attention + POS gate + 2 LSTM cells, the
-                 unit of SURVEY.md 8d) timed with stream events; ALGORITHMIC bytes / duration vs 8 TB/s
+                 unit of SURVEY.md 8d) timed with stream events; ALGORITHMIC bytes / duration vs 8 TB/s;
+                 live PMC traffic; the in-situ step time; host enqueue times
   cpu_baseline : the oracle (CPU restatement of the reference, v2a recomputed per step like the
-                 reference) timed on this box's host cores on a bounded sample of the same workload.
+                 reference) timed on this box's host cores on a bounded sample of the same workload,
+                 and the parity self-check against it (the process exits non-zero when it fails)
+  secondary    : the other single-GPU configurations (SCST, hidden-1024 bf16, split-bf16, drop 0.5)
+  comm         : N > 1, the per-rank exposed communication (the iterations again without the collective)
 """
 from __future__ import annotations
 
@@ -392,8 +397,12 @@ def write_outputs(path, arrays, limit=64 << 20):
             "what": "one more iteration of the timed path from the seeded starting state, after the timed steps"}
 
 
-def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pmc=True, comm_diag=True, drop=None, dump=None):
+def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pmc=True, comm_diag=True, drop=None, dump=None,
+                 full=False):
     """One timed workload on this rank; returns (json-able dict | None on ranks != 0, parity failure text | None).
+    full: after the timed steps (and the dump) also measure what the headline does not need -- host enqueue times, the
+    in-situ and stand-alone decoder step, PMC traffic, the exposed communication (cpu_leg, pmc, comm_diag narrow this) --
+    and run the CPU baseline with its parity self-check.
     dump: a directory.  After the timed steps the model and optimizer are put back into their seeded starting state and the
     timed step runs once more; what it computed is written there (snapshot_outputs).  The timed steps themselves cannot serve:
     each one starts from the weights its predecessors produced, and those differ from run to run -- the kernels accumulate with
@@ -525,10 +534,15 @@ def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pm
         torch.cuda.synchronize()
         dumped = snapshot_outputs(model, loss_d) if rank == 0 else None
         del start
-    # ---- data-parallel diagnosis: the same iterations with the collective switched off (same streams, events and update
-    # segments; only the RCCL kernels are missing) -> what the all-reduce costs each rank, i.e. its EXPOSED part
+    # ---- data parallel: what the timed steps ran (gradient size, all-reduce schedule and buckets); --full adds the diagnosis:
+    # the same iterations with the collective switched off (same streams, events and update segments; only the RCCL kernels are
+    # missing) -> what the all-reduce costs each rank, i.e. its EXPOSED part
     comm = None
-    if use_dist and comm_diag:
+    if use_dist:
+        comm = {"gradient_bytes": int(model.flat_grads().numel() * 4), "schedule": comm_choice,
+                "buckets": "logit | lstmcore+embed+img_embed | classifer | two_spatial_encoder (train.GradSync)"
+                           if (sync is not None and state["overlap_comm"]) else "one"}
+    if use_dist and comm_diag and full:
         try:
             tr._SKIP_COLLECTIVE = True
             try:
@@ -554,86 +568,70 @@ def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pm
                     "host_cores": core_ranges(ctx.get("cores"))}
             allr = [None] * world
             dist.all_gather_object(allr, mine)
-            comm = {"per_rank": allr, "gradient_bytes": int(model.flat_grads().numel() * 4), "schedule": comm_choice,
-                    "buckets": "logit | lstmcore+embed+img_embed | classifer | two_spatial_encoder (train.GradSync)"
-                               if (sync is not None and state["overlap_comm"]) else "one",
+            comm = {"per_rank": allr, **comm,
                     "rccl_channels": rccl_channels(ctx.get("rccl_log")) if ctx.get("rccl_log") else None,
                     "rccl_channel_cap": ctx.get("rccl_cap"),
                     "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version())}
         except Exception as e:                    # never lose the scaling line over the diagnosis
-            comm = {"error": repr(e)}
-    # host-side enqueue cost of one iteration against an IDLE GPU (the loop above also contains queue back-pressure: the
-    # host runs ahead of the GPU until the launch queue is full), median of 5
-    enq = []
-    for _ in range(5):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step()
-        enq.append(time.perf_counter() - t1)
-    torch.cuda.synchronize()
-    host_enqueue_ms = sorted(enq)[len(enq) // 2] * 1e3
-    host_enqueue_eager_ms = None
-    if use_graph:                                # the same iteration as individual launches, for comparison
+            comm = {"error": repr(e), **comm}
+    host_enqueue_ms = host_enqueue_eager_ms = in_situ_us = t_step = None
+    if full:
+        # host-side enqueue cost of one iteration against an IDLE GPU (the loop above also contains queue back-pressure: the
+        # host runs ahead of the GPU until the launch queue is full), median of 5
         enq = []
         for _ in range(5):
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-            eager_step()
+            step()
             enq.append(time.perf_counter() - t1)
         torch.cuda.synchronize()
-        host_enqueue_eager_ms = sorted(enq)[len(enq) // 2] * 1e3
-    # in-situ duration of the T decoder steps inside the timed iteration (XgRun.prof_event0/1: recorded by the library on
-    # the caller's stream around its time loop), median of 5 iterations
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(); e1.record()
-    model._prof_events = (e0, e1)
-    insitu = []
-    for _ in range(5):
-        eager_step()                             # (events inside a replayed graph cannot be read: eager launches here)
-        torch.cuda.synchronize()
-        insitu.append(e0.elapsed_time(e1) * 1e3 / (T - 1 if workload == "scst" else T))   # (a rollout runs L core steps: the reference's L + 1st is dead)
-    model._prof_events = None
-    in_situ_us = sorted(insitu)[len(insitu) // 2]
-
-    t_step = measure_step_group(model, x) if rank == 0 else None
+        host_enqueue_ms = sorted(enq)[len(enq) // 2] * 1e3
+        if use_graph:                            # the same iteration as individual launches, for comparison
+            enq = []
+            for _ in range(5):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                eager_step()
+                enq.append(time.perf_counter() - t1)
+            torch.cuda.synchronize()
+            host_enqueue_eager_ms = sorted(enq)[len(enq) // 2] * 1e3
+        # in-situ duration of the T decoder steps inside the timed iteration (XgRun.prof_event0/1: recorded by the library on
+        # the caller's stream around its time loop), median of 5 iterations
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); e1.record()
+        model._prof_events = (e0, e1)
+        insitu = []
+        for _ in range(5):
+            eager_step()                         # (events inside a replayed graph cannot be read: eager launches here)
+            torch.cuda.synchronize()
+            insitu.append(e0.elapsed_time(e1) * 1e3 / (T - 1 if workload == "scst" else T))   # (a rollout runs L core steps: the reference's L + 1st is dead)
+        model._prof_events = None
+        in_situ_us = sorted(insitu)[len(insitu) // 2]
+        t_step = measure_step_group(model, x) if rank == 0 else None
     if rank != 0:
         return None, None
     step_rows = 2 * cfg["B"] if workload == "scst" else cfg["B"]      # (the SCST pair is ONE 2m-row batch)
-    if workload == "scst":                       # the stand-alone group at the row count the rollout steps really have
+    if full and workload == "scst":              # the stand-alone group at the row count the rollout steps really have
         x2 = {k: torch.cat([v, v]) for k, v in x.items()}
         t_step = measure_step_group(model, x2)
     ms = dt / steps * 1e3
     value = world * cfg["B"] * (2 * (T - 1) if workload == "scst" else T) * steps / dt     # scst: L core steps per row actually run, two rollouts
     bf16 = precision == "bf16"
-    bytes_step = step_bytes(step_rows, cfg["K"], cfg["R"], cfg["A"], cfg["E"], save=False, elem=2 if bf16 else 4)
-    bytes_step_saved = step_bytes(step_rows, cfg["K"], cfg["R"], cfg["A"], cfg["E"], save=True, elem=2 if bf16 else 4)
     mfma_peak = 2500.0 if bf16 else 157.3
-    achieved = bytes_step / t_step / 1e9
-    traffic, traffic_src = (None, None)
-    if cfg["B"] == 128 and workload == "xe" and precision == "fp32":
-        if pmc and not args.no_pmc and world == 1:           # (the two rocprofv3 passes run on rank 0's GPU: single-GPU runs only)
-            traffic, traffic_src = measure_traffic()
-        elif world > 1:
-            traffic_src = "multi-GPU run"
-        if traffic is None:                              # fall back to the committed passes, and say so
-            why = traffic_src
-            traffic, traffic_src = load_traffic()
-            if traffic_src:
-                traffic_src += " (committed earlier: live PMC pass unavailable -- %s)" % why
     wl = {"xe": "configs[%s]: %dxMI355X batch %d per GPU teacher-forced XE train, 26 frames x (1536+1024), hidden 512, "
                 "att 1536, emb 468, vocab 20000, seq_len 20 (T=21), fp32" % ("1" if world == 1 else "3", world, cfg["B"]),
           "scst": "configs[2]: %dxMI355X SCST iteration (sampled rollout + greedy baseline as one 2m-row batch + RL backward + "
                   "clip + Adam), batch %d per GPU, seq_len 30, 26 frames, hidden 512, vocab 20000, CIDEr reward stubbed" % (world, cfg["B"]),
           "xe5": "configs[4]: %dxMI355X batch %d per GPU teacher-forced XE train, 40 frames x (1536+1024), hidden 1024, att 1536, "
                  "vocab 20000, seq_len 20, %s" % (world, cfg["B"], precision)}[workload]
-    flops = step_flops(step_rows, cfg["K"], cfg["R"], cfg["A"], cfg["E"])
     out = {
         "metric": "rollout timesteps/sec, SCST iteration (sample + greedy + RL backward) at batch 64, seq_len 30"
                   if workload == "scst" else "decoder timesteps/sec (train fwd+bwd) at batch 128, MSRVTT 26x1536+1024",
         "value": round(value, 1), "unit": "decoder timesteps/s", "n_gpus": world, "steps": steps,
-        "warmup": warmup, "ms_per_step": round(ms, 3), "host_enqueue_ms_per_step": round(host_enqueue_ms, 3),
+        "warmup": warmup, "ms_per_step": round(ms, 3),
+        **({"host_enqueue_ms_per_step": round(host_enqueue_ms, 3)} if full else {}),
         "host_loop_ms_per_step": round(t_enq * 1e3 / steps, 3),
-        "host_enqueue_ms_per_step_eager": None if host_enqueue_eager_ms is None else round(host_enqueue_eager_ms, 3),
+        **({"host_enqueue_ms_per_step_eager": None if host_enqueue_eager_ms is None else round(host_enqueue_eager_ms, 3)} if full else {}),
         "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": {"fp32": "f32", "bf16x3": "f32 via split-bf16 (3 planes, 6 MFMAs)", "bf16": "bf16"}[precision],
         "data": "synthetic",
@@ -650,27 +648,46 @@ def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pm
         "final_loss": round(final_loss, 5),
         **({"NOT_A_MEASUREMENT": "XG_FORCE_DIST=3: %d ranks time-slicing ONE GPU, all-reduce over gloo -- control-flow exercise only" % world}
            if os.environ.get("XG_FORCE_DIST") == "3" else {}),
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
-                     "frac": round(achieved / 8000.0, 4), "traffic": traffic, "traffic_source": traffic_src,
-                     "kernel": "decoder step launch group (xg_step_fwd: attention + POS gate + lstm_1 + lstm_2)",
-                     "measured_form": "xg_step_fwd stand-alone, %d rows, inference form (tokens gathered inside the products, state "
-                                      "updated in place, nothing saved), 200 back-to-back calls between two stream events" % step_rows,
-                     "algorithmic_bytes_per_launch": bytes_step, "avg_launch_us": round(t_step * 1e6, 2),
-                     # the same steps where the timed iteration runs them: %s loop of the forward pass (saves on, beside the
-                     # side-stream products), events recorded by the library around its time loop
-                     "in_situ_form": ("rollout loop (token choice + step + vocabulary product per step)" if workload == "scst"
-                                      else "teacher-forced loop (token side hoisted, activations saved)") + ", inside the timed iteration",
-                     "in_situ_us_per_step": round(in_situ_us, 2),
-                     "in_situ_algorithmic_bytes": bytes_step_saved,
-                     "in_situ_frac": None if workload == "scst" else round(bytes_step_saved / (in_situ_us * 1e-6) / 8e12, 4),
-                     # the same launch group against the OTHER roof (exact-fp32 MFMA, 157.3 TF): at B = 128 the step's
-                     # arithmetic intensity (33 FLOP/B) is above the ridge (20), i.e. the MFMA roof is the lower one
-                     "mfma_tflops": round(flops / t_step / 1e12, 2),
-                     "mfma_peak_tflops": mfma_peak,
-                     "mfma_frac": round(flops / t_step / (mfma_peak * 1e12), 4)},
+        "roofline": {},
     }
+    if full:
+        bytes_step = step_bytes(step_rows, cfg["K"], cfg["R"], cfg["A"], cfg["E"], save=False, elem=2 if bf16 else 4)
+        bytes_step_saved = step_bytes(step_rows, cfg["K"], cfg["R"], cfg["A"], cfg["E"], save=True, elem=2 if bf16 else 4)
+        achieved = bytes_step / t_step / 1e9
+        traffic, traffic_src = (None, None)
+        if cfg["B"] == 128 and workload == "xe" and precision == "fp32":
+            if pmc and not args.no_pmc and world == 1:           # (the two rocprofv3 passes run on rank 0's GPU: single-GPU runs only)
+                traffic, traffic_src = measure_traffic()
+            elif world > 1:
+                traffic_src = "multi-GPU run"
+            if traffic is None:                              # fall back to the committed passes, and say so
+                why = traffic_src
+                traffic, traffic_src = load_traffic()
+                if traffic_src:
+                    traffic_src += " (committed earlier: live PMC pass unavailable -- %s)" % why
+        flops = step_flops(step_rows, cfg["K"], cfg["R"], cfg["A"], cfg["E"])
+        out["roofline"] = {
+            "bound": "hbm", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
+            "frac": round(achieved / 8000.0, 4), "traffic": traffic, "traffic_source": traffic_src,
+            "kernel": "decoder step launch group (xg_step_fwd: attention + POS gate + lstm_1 + lstm_2)",
+            "measured_form": "xg_step_fwd stand-alone, %d rows, inference form (tokens gathered inside the products, state "
+                             "updated in place, nothing saved), 200 back-to-back calls between two stream events" % step_rows,
+            "algorithmic_bytes_per_launch": bytes_step, "avg_launch_us": round(t_step * 1e6, 2),
+            # the same steps where the timed iteration runs them: %s loop of the forward pass (saves on, beside the
+            # side-stream products), events recorded by the library around its time loop
+            "in_situ_form": ("rollout loop (token choice + step + vocabulary product per step)" if workload == "scst"
+                             else "teacher-forced loop (token side hoisted, activations saved)") + ", inside the timed iteration",
+            "in_situ_us_per_step": round(in_situ_us, 2),
+            "in_situ_algorithmic_bytes": bytes_step_saved,
+            "in_situ_frac": None if workload == "scst" else round(bytes_step_saved / (in_situ_us * 1e-6) / 8e12, 4),
+            # the same launch group against the OTHER roof (exact-fp32 MFMA, 157.3 TF): at B = 128 the step's
+            # arithmetic intensity (33 FLOP/B) is above the ridge (20), i.e. the MFMA roof is the lower one
+            "mfma_tflops": round(flops / t_step / 1e12, 2),
+            "mfma_peak_tflops": mfma_peak,
+            "mfma_frac": round(flops / t_step / (mfma_peak * 1e12), 4)}
     if workload != "scst":
         # the WHOLE iteration against the matrix roof: chains, products and the update share the chip for dt / steps seconds
+        # (from the timed steps alone: a plain run reports it too)
         it_flop = iteration_flops(cfg)
         out["roofline"]["iteration"] = {"bound": "mfma", "flop": it_flop, "achieved": round(it_flop / (dt / steps) / 1e12, 1),
                                         "peak": mfma_peak, "unit": "TFLOP/s", "frac": round(it_flop / (dt / steps) / (mfma_peak * 1e12), 4),
@@ -681,7 +698,7 @@ def run_workload(args, workload, precision, steps, warmup, ctx, cpu_leg=True, pm
     if dumped is not None:
         out["dump_outputs"] = write_outputs(dump, dumped)
     parity_fail = None
-    if world == 1 and cpu_leg and not args.no_cpu_baseline:
+    if full and world == 1 and cpu_leg and not args.no_cpu_baseline:
         tol = 1e-2 if precision == "bf16" else 1e-4        # north_star: 1e-4 on the training loss in fp32, 1e-2 for the bf16 config
         if workload == "scst":
             par = scst_parity(model, cfg, x, reward_b)
@@ -723,12 +740,7 @@ def step_group_by_arithmetic(args, ctx):
     return out
 
 
-def main():
-    # stdout carries exactly ONE line, the JSON: everything else that writes to file descriptor 1 (RCCL prints a version banner
-    # through C stdio when a communicator comes up, rocprofv3 children, ...) is sent to stderr
-    sys.stdout.flush()
-    json_fd = os.dup(1)
-    os.dup2(2, 1)
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20, help="timed iterations (ms_per_step = their wall time / steps)")
@@ -742,19 +754,33 @@ def main():
     ap.add_argument("--workload", choices=["xe", "scst", "xe5"], default="xe",
                     help="xe: BASELINE configs[1] (the metric); scst: configs[2] (sample + greedy rollouts + RL backward, B=64, L=30); "
                          "xe5: configs[4] shape (hidden 1024, 40 frames; pair with --precision bf16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc passes that measure roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what it does not need: the stand-alone and in-situ decoder step, live PMC "
+                         "traffic, host enqueue times, the CPU baseline with its parity self-check (the exit status fails with it), "
+                         "the secondary configurations and, for N > 1, the exposed communication")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its parity self-check")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the two rocprofv3 --pmc passes that measure roofline.traffic")
     ap.add_argument("--graph", action="store_true", help="time the HIP-graph replay of the iteration (single-stream capture) instead of eager launches")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the configs[2] (SCST) and configs[4] (hidden-1024 bf16) lines that the default single-GPU run appends")
-    ap.add_argument("--cpu-budget", type=float, default=15.0)
+                    help="--full: skip the secondary lines (SCST, hidden-1024 bf16, split-bf16, drop 0.5) of a single-GPU run")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="--full: seconds of CPU baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, run the timed iteration once more from the seeded starting state and write what it "
                          "computed (its loss, the updated parameters and BatchNorm buffers; a fixed sample of each large tensor) as "
                          "DIR/<name>.npy")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def main():
+    # stdout carries exactly ONE line, the JSON: everything else that writes to file descriptor 1 (RCCL prints a version banner
+    # through C stdio when a communicator comes up, rocprofv3 children, ...) is sent to stderr
+    sys.stdout.flush()
+    json_fd = os.dup(1)
+    os.dup2(2, 1)
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU, RCCL over xGMI) -- never
@@ -793,7 +819,8 @@ def main():
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
-        ctx["rccl_log"] = rccl_debug_setup(rank)
+        if args.full:                               # (the channel count is reported with comm's diagnosis only)
+            ctx["rccl_log"] = rccl_debug_setup(rank)
         from controllable_xgating_amd.train import dist_diagnosis
         try:
             if one_gpu:
@@ -816,11 +843,12 @@ def main():
     if use_dist:
         dist.barrier()
 
-    out, fail = run_workload(args, args.workload, args.precision, args.steps, args.warmup, ctx, dump=args.dump_outputs)
+    out, fail = run_workload(args, args.workload, args.precision, args.steps, args.warmup, ctx, dump=args.dump_outputs,
+                             full=args.full)
     fails = [fail] if fail else []
-    # the default single-GPU run also carries BASELINE.json's other single-GPU configurations (5 warm-up + 10 timed
+    # a --full single-GPU run also carries BASELINE.json's other single-GPU configurations (5 warm-up + 10 timed
     # iterations each, own roofline and parity self-check): configs[2] (SCST) and configs[4] (hidden 1024 / 40 frames, bf16)
-    if (not args.no_secondary and world == 1 and not use_dist and args.workload == "xe" and args.precision == "fp32"
+    if (args.full and not args.no_secondary and world == 1 and not use_dist and args.workload == "xe" and args.precision == "fp32"
             and args.batch == 128 and args.path == "fused"):
         sec = {}
         # ... and the headline configuration at the reference's default drop_prob_lm = 0.5 (myopts.py:37; SURVEY.md 8d: "throughput
@@ -830,7 +858,7 @@ def main():
             if drop_ is not None and drop_ == args.drop:
                 continue
             try:
-                o, f = run_workload(args, wl_, prec_, 10, 5, ctx, pmc=False, comm_diag=False, drop=drop_)
+                o, f = run_workload(args, wl_, prec_, 10, 5, ctx, pmc=False, comm_diag=False, drop=drop_, full=True)
                 sec[key] = {k: o[k] for k in ("metric", "value", "unit", "ms_per_step", "host_enqueue_ms_per_step", "dtype", "config",
                                               "final_loss", "roofline", "parity_loss_delta", "parity", "steps", "warmup") if k in o}
                 if "cpu_baseline" in o:

@@ -167,14 +167,15 @@ def test_two_rank_update_paths_agree(tmp_path):
 def test_bench_n_rank_control_flow_on_one_gpu_over_gloo(tmp_path):
     """`bench.py --gpus 2` end to end where only one GPU exists (XG_FORCE_DIST=3: both ranks on device 0, gloo instead of RCCL): the
     self-launch through torch.distributed.run, the shard per rank, barriers, max over ranks, schedule choice, per-rank report and
-    the ONE JSON line from rank 0.  The numbers are not measurements (the line says so); what is asserted is the contract's shape."""
+    the ONE JSON line from rank 0 (--full: with the per-rank diagnosis).  The numbers are not measurements (the line says so); what is
+    asserted is the contract's shape."""
     import json, subprocess, sys
     from tests.util import ROOT
     env = dict(os.environ, XG_FORCE_DIST="3", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-pmc"],
-                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
+                        "--no-cpu-baseline", "--no-pmc"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]                     # rank 0 alone prints, once

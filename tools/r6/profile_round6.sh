@@ -40,7 +40,7 @@ hipcc --offload-arch=gfx950 -O2 -o /tmp/grid_barrier tools/ubench/grid_barrier.h
 # 6. large products alone
 python tools/ubench/gemm_bench.py > $OUT/${R}_gemm_bench.txt 2>&1
 # 7. the bench lines themselves (un-profiled)
-python bench.py > $OUT/${R}_bench_line.json 2> $OUT/bench_line.err
-XG_FORCE_DIST=2 python bench.py --no-cpu-baseline --no-pmc --no-secondary > $OUT/${R}_bench_line_one_rank_rccl.json 2>/dev/null
+python bench.py --full > $OUT/${R}_bench_line.json 2> $OUT/bench_line.err
+XG_FORCE_DIST=2 python bench.py --full --no-cpu-baseline --no-pmc --no-secondary > $OUT/${R}_bench_line_one_rank_rccl.json 2>/dev/null
 rm -rf $OUT/bench $OUT/step $OUT/scst $OUT/xe5 $OUT/drop $OUT/pmcF $OUT/pmcW $OUT/pmc1 $OUT/pmc2 $OUT/pmc3
 ls -la $OUT

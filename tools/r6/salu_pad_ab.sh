@@ -5,7 +5,7 @@ L=controllable_xgating_amd/lib
 for rep in 1 2; do
 for v in product pad128 pad256; do
     lib=""; [ $v != product ] && lib="XG_LIBRARY=$L/libxgate_hip_$v.so"
-    env $lib python bench.py --steps 20 --warmup 5 2>/dev/null | python -c "
+    env $lib python bench.py --full --steps 20 --warmup 5 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']

@@ -5,7 +5,7 @@ out=gpurun_out/r6_scst_ab.txt
 : > $out
 run() { # label env...
   label=$1; shift
-  env "$@" python bench.py --workload scst --no-pmc --steps 10 --warmup 5 2>/dev/null | python -c "
+  env "$@" python bench.py --full --workload scst --no-pmc --steps 10 --warmup 5 2>/dev/null | python -c "
 import json,sys
 o=json.loads(sys.stdin.read())
 print('$label', 'ms', o['ms_per_step'], 'in-situ us/step', o['roofline']['in_situ_us_per_step'], 'parity', o.get('parity_loss_delta'))" | tee -a $out

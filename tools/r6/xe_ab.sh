@@ -4,7 +4,7 @@ cd "$(dirname "$0")/../.."
 out=gpurun_out/r6_xe_ab.txt
 : > $out
 run() { label=$1; shift
-  env "$@" python bench.py --no-secondary --no-cpu-baseline --no-pmc --steps 20 --warmup 5 2>/dev/null | python -c "
+  env "$@" python bench.py --full --no-secondary --no-cpu-baseline --no-pmc --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 o=json.loads(sys.stdin.read())
 print('$label', 'ms', o['ms_per_step'], 'step us', o['roofline']['avg_launch_us'], 'in-situ', o['roofline']['in_situ_us_per_step'])" | tee -a $out
