@@ -1062,20 +1062,25 @@ bool run_ok(const XgptRun* run) {
     return run && run->drop_p >= 0.f && run->drop_p < 1.f && run->bn_momentum >= 0.f && run->bn_momentum <= 1.f;
 }
 
+// the attention backward after the step loop (xgk_attn_post_dV -> xgk_attn_bwd_post) keeps a video's T x K score gradients in
+// LDS and refuses more than XGPT_MAX_TK_BYTES of them: such shapes are refused here, before a forward moves the running
+// statistics or a backward adds its first gradient
+bool tk_ok(int64_t T, int64_t K) { return T * K * (int64_t)sizeof(float) <= XGPT_MAX_TK_BYTES; }
+
 }  // namespace
 
 extern "C" int xgpt_version(void) { return XGPT_VERSION; }
 
 extern "C" size_t xgpt_workspace_bytes(const XgpDims* d) {
-    if (!dims_ok(d, true)) return 0;
+    if (!dims_ok(d, true) || !tk_ok(d->T, d->K)) return 0;
     return tws_layout(d, nullptr).floats * sizeof(float);
 }
 
 extern "C" int xgpt_forward_train(void* stream, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const XgptRun* run,
                                   const float* feats_rgb, const float* feats_opfl, const float* feat_mask, const int64_t* cap_classes,
                                   const float* new_mask, float* logp, int32_t* t_out, void* ws, size_t ws_bytes) {
-    if (!dims_ok(d, true) || !params_ok(p) || !bn_ok(bn) || !run_ok(run) || !feats_rgb || !feats_opfl || !feat_mask || !cap_classes ||
-        !new_mask || !logp || !t_out || !ws)
+    if (!dims_ok(d, true) || !tk_ok(d->T, d->K) || !params_ok(p) || !bn_ok(bn) || !run_ok(run) || !feats_rgb || !feats_opfl ||
+        !feat_mask || !cap_classes || !new_mask || !logp || !t_out || !ws)
         return XG_EINVAL;
     if (ws_bytes < tws_layout(d, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -1089,7 +1094,7 @@ extern "C" int xgpt_backward(void* stream, const XgpDims* d, const XgpParams* p,
                              const float* feats_rgb, const float* feats_opfl, const float* feat_mask, int32_t Tp, const float* dlogp,
                              void* ws, size_t ws_bytes) {
     if (!dims_ok(d, true) || !params_ok(p) || !params_ok(g) || !run_ok(run) || !feats_rgb || !feats_opfl || !feat_mask || !dlogp ||
-        !ws || Tp < 1 || Tp > d->T)
+        !ws || Tp < 1 || Tp > d->T || !tk_ok(Tp, d->K))
         return XG_EINVAL;
     if (ws_bytes < tws_layout(d, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
     return backward((hipStream_t)stream, d, p, g, run, feats_rgb, feats_opfl, feat_mask, Tp, dlogp, tws_layout(d, ws));

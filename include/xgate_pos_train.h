@@ -22,6 +22,11 @@ extern "C" {
 
 #define XGPT_VERSION 1
 
+/* Train shapes are limited beyond xgate_pos.h's: T * K * sizeof(float) must not exceed XGPT_MAX_TK_BYTES (the attention
+ * backward holds a video's T x K score gradients in LDS), e.g. K <= 517 frames at seq_length 28 (T = 29).
+ * xgpt_workspace_bytes returns 0 and xgpt_forward_train XG_EINVAL for d->T * d->K beyond it, xgpt_backward for Tp * d->K. */
+#define XGPT_MAX_TK_BYTES 60000
+
 /* train != 0: BatchNorm with batch statistics (running statistics updated in place: running = (1 - bn_momentum) running
  * + bn_momentum batch, unbiased variance) and hash dropout with probability drop_p (oracle/paramgen.py:keep_mask, sites
  * 0 rgb embedding, 1 opfl embedding, 4 fusion, 6 decoder cell at step t).  train == 0: eval-mode BatchNorm over the

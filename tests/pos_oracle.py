@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY -- a CPU torch restatement of the POS sequence generator (reference pos_src/SAModel.py,
+"""TEST INFRASTRUCTURE ONLY -- a torch restatement of the POS sequence generator (reference pos_src/SAModel.py,
 pos_src/sub_modules.py), eval mode, plus seeded parameters and inputs built on oracle.paramgen.uniform.
 
 Written from reading the reference, not copied: the encoder (sub_modules.py:199-239: Linear -> BN -> ReLU, masked LSTMCell
@@ -6,7 +6,9 @@ encoders that ZERO h and c on masked frames, late fusion relu(W [h_rgb ; h_opfl]
 the sum of V over all K rows over the mask count), the one-layer attention decoder (sub_modules.py:679-715, unmasked softmax over K)
 with the two-input cell (:871-889: order i,f,o,g, the mask holds c and h), the teacher-forced forward with its early break
 (SAModel.py:62-90), the pos ClassiferCriterion (SAModel.py:201-218: target rolled left by one) and the greedy rollout that collects
-states (SAModel.py:136-184).  tests/golden/pos_*.npz pin it to the reference itself (tools/gen_pos_golden.py).
+states (SAModel.py:136-184).  tests/golden/pos_*.npz pin it to the reference itself (tools/gen_pos_golden.py).  It runs in the
+dtype and on the device of its inputs: float32 on CPU for the fixtures, float64 (on CPU or a GPU through eager torch) as the
+high-precision reference of tests/test_gpu_pos_edges.py.
 """
 from __future__ import annotations
 
@@ -217,8 +219,14 @@ def prepare_targets(cap_classes, class_mask):
     return rolled, new_mask
 
 
-def to_torch(P):
-    return {k: torch.as_tensor(v) for k, v in P.items()}
+def to_torch(P, dtype=None, device=None):
+    """{name: tensor}; `dtype` / `device` (optional) convert the floating-point entries, e.g. float64 on a GPU for a fast
+    high-precision reference (the functions below run in the dtype and on the device of their inputs)."""
+    out = {}
+    for k, v in P.items():
+        t = torch.as_tensor(v)
+        out[k] = t.to(device=device, dtype=dtype if t.is_floating_point() else None)
+    return out
 
 
 def _lin(x, P, name):
@@ -285,7 +293,7 @@ def forward_tf(P, run, fr, fo, fm, cap_r, new_mask):
     for i in range(cap_r.shape[1]):
         if i >= 1 and int(cap_r[:, i].sum()) == 0:
             break
-        h, c, lp = step(P, V, q, cap_r[:, i], new_mask[:, i:i + 1], h, c)
+        h, c, lp = step(P, V, q, cap_r[:, i], new_mask[:, i:i + 1].to(fr.dtype), h, c)
         outs.append(lp)
     return torch.stack(outs, 1)
 
@@ -315,7 +323,7 @@ def sample_greedy(P, run, fr, fo, fm, L):
     for t in range(L + 1):
         if t == 0:
             it = torch.zeros(B, dtype=torch.int64, device=fr.device)
-            m = torch.ones(B, 1, device=fr.device)
+            m = torch.ones(B, 1, dtype=fr.dtype, device=fr.device)
         else:
             sl, it = torch.max(logp, 1)
             unf = (it > 0) if t == 1 else unf * (it > 0)
@@ -324,7 +332,7 @@ def sample_greedy(P, run, fr, fo, fm, L):
             seq.append(it * unf.long())
             slp.append(sl)
             lps.append(logp)
-            m = unf.float().unsqueeze(1)
+            m = unf.to(fr.dtype).unsqueeze(1)
         h, c, logp = step(P, V, q, it, m, h, c)
         states.append(h)
         masks.append(m)

@@ -128,6 +128,30 @@ def test_train_bad_arguments_return_error_codes_without_a_gpu(built):
     assert L.xgpt_backward(None, B(dims), B(P), B(G0), B(run), fake, fake, fake, 3, fake, fake, 1 << 40) == -1
 
 
+def test_train_refuses_shapes_beyond_the_attention_backward(built):
+    """T K * 4 > XGPT_MAX_TK_BYTES (60000): the attention backward after the step loop cannot run it, so the workspace query
+    returns 0 and both entry points return XG_EINVAL before anything is enqueued (before, the backward failed half-way, after
+    adding most gradients, and the forward had already moved the running statistics)."""
+    from controllable_xgating_amd import _native as nv
+    from controllable_xgating_amd import _native_pos as npos
+    from controllable_xgating_amd import _native_pos_train as npt
+    assert re.search(r"#define XGPT_MAX_TK_BYTES 60000\b", _train_header())
+    L = npt.lib()
+    B = ctypes.byref
+    T = 29                                               # seq_length 28
+    assert L.xgpt_workspace_bytes(B(npos.XgpDims(1, 517, 8, 8, 4, 3, 4, 4, T))) > 0       # 29 * 517 * 4 = 59972
+    dims = npos.XgpDims(1, 600, 8, 8, 4, 3, 4, 4, T)                                       # 29 * 600 * 4 = 69600
+    # first: a library without the check stops the test here, before any call below could enqueue work on fake pointers
+    assert L.xgpt_workspace_bytes(B(dims)) == 0
+    fake = 16
+    P = npos.XgpParams(*([fake] * len(npos.PARAM_NAMES)))
+    G = npos.XgpParams(*([fake] * len(npos.PARAM_NAMES)))
+    bn = nv.XgBnState(fake, fake, fake, fake)
+    run = npt.XgptRun(1, 0.0, 7, 0.1)
+    assert L.xgpt_forward_train(None, B(dims), B(P), B(bn), B(run), fake, fake, fake, fake, fake, fake, fake, fake, 1 << 40) == -1
+    assert L.xgpt_backward(None, B(dims), B(P), B(G), B(run), fake, fake, fake, T, fake, fake, 1 << 40) == -1
+
+
 def _reference_lr(opt, epoch):
     """starttrain_trainpos.py:98-105, restated."""
     if epoch > opt.learning_rate_decay_start and opt.learning_rate_decay_start >= 0:
