@@ -1308,6 +1308,25 @@ extern "C" int xg_debug_dstep_err(void* stream, const XgDims* d, void* ws, size_
     if (hipMemsetAsync(word, 0, sizeof(int), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return XG_EHIP;
     return XG_OK;
 }
+// diag library only, host only (no GPU): where carve() puts the words of a workspace that are NOT plain fp32 data, as byte offsets
+// from the workspace's start, so that a test can overwrite everything else (tests/ws_state.py).  out[0..11] = {offset, bytes} of
+// tickets, dsync (the only words a kernel spin-waits on), TOK (int64), alive (int32), the bf16 mirror region (bytes = 0 for a
+// workspace sized by xg_workspace_bytes_mode(d, gemm_mode != 1)), then xg_workspace_bytes_mode(d, gemm_mode) and core_bytes.
+extern "C" int xg_debug_ws_layout(const XgDims* d, int gemm_mode, uint64_t* out) {
+    if (!dims_ok(d) || !out) return XG_EINVAL;
+    char* const fake = reinterpret_cast<char*>(uintptr_t(1) << 40);       // never dereferenced: carve() only does arithmetic on it
+    const Ws w = carve(*d, fake);
+    auto off = [&](const void* p) { return (uint64_t)(static_cast<const char*>(p) - fake); };
+    const uint64_t total = gemm_mode == 1 ? w.bytes : w.core_bytes;
+    const uint64_t r[12] = {off(w.tickets), (uint64_t)SK_MAX_JOBS * SKPART_INTS * sizeof(int32_t),
+                            off(w.dsync), (uint64_t)XGK_DSTEP_SYNC_BYTES,
+                            off(w.TOK), (uint64_t)d->T * d->B * sizeof(int64_t),
+                            off(w.alive), 4 * sizeof(int32_t),
+                            (uint64_t)w.core_bytes, total - w.core_bytes,
+                            total, (uint64_t)w.core_bytes};
+    for (int i = 0; i < 12; ++i) out[i] = r[i];
+    return XG_OK;
+}
 #endif
 extern "C" size_t xg_workspace_bytes_mode(const XgDims* d, int gemm_mode) {
     if (!dims_ok(d)) return 0;

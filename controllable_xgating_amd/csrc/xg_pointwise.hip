@@ -339,7 +339,8 @@ __global__ void __launch_bounds__(256) compact_kernel(CompactArgs a) {
     for (int i = 1; i < a.n; ++i) if ((int)blockIdx.x >= a.start[i]) ei = i;
     const CompactEntry& e = a.e[ei];
     const int64_t base = (int64_t)(blockIdx.x - a.start[ei]) * CPB;
-    const bool vec = (e.dst_block % 4 == 0) && (e.src_pitch % 4 == 0);
+    // (a block of an odd extent puts the NEXT entry of the same tensor off the 16-byte grid: xg_rollout_pair_videos at R, A not multiples of 4)
+    const bool vec = (e.dst_block % 4 == 0) && (e.src_pitch % 4 == 0) && ((reinterpret_cast<uintptr_t>(e.dst) | reinterpret_cast<uintptr_t>(e.src)) % 16 == 0);
     if (vec) {
 #pragma unroll
         for (int u = 0; u < CPB / (256 * 4); ++u) {
@@ -655,7 +656,7 @@ int xgk_compact(hipStream_t st, CompactArgs& a) {
     int blocks = 0;
     for (int i = 0; i < a.n; ++i) {
         const CompactEntry& e = a.e[i];
-        if (!e.dst || !e.src || e.dst_block <= 0 || e.total < 0 || ((uintptr_t)e.dst % 16) || ((uintptr_t)e.src % 16)) return XG_EINVAL;
+        if (!e.dst || !e.src || e.dst_block <= 0 || e.total < 0 || ((uintptr_t)e.dst % 4) || ((uintptr_t)e.src % 4)) return XG_EINVAL;
         a.start[i] = blocks;
         blocks += (int)xg_cdiv64(e.total, CPB);
     }

@@ -15,9 +15,18 @@
  *   - The caller owns all memory; scratch and saved activations live in one caller-provided
  *     workspace sized by xg_workspace_bytes().  The only thing the library allocates is the
  *     optional side-stream handle of xg_aux_create (two HIP streams + events, no memory).
- *     A workspace must be ZERO-FILLED once after allocation (hipMemset), before its first use: it
+ *     A workspace must be ZERO-FILLED once after allocation (hipMemset / xg_workspace_init), before its first use: it
  *     also holds the inter-workgroup synchronisation words of the step kernels, which every call
- *     leaves at zero again.
+ *     leaves at zero again (also a forward whose backward never follows).  After that, for ONE XgDims, any
+ *     entry point may follow any other on it, in any order, without re-initialising: no call reads a data
+ *     word that it (or, for a *_bwd, its *_fwd) has not written -- every accumulator is cleared by the call
+ *     that adds into it.  The positions of the synchronisation words depend on XgDims: a workspace that
+ *     is re-used with OTHER dims (the last, smaller batch of an epoch) must be zero-filled again first
+ *     (xg_workspace_init), or be a separate allocation.
+ *   - Outputs are written IN FULL by the library unless marked ACCUMULATED: the caller may pass
+ *     uninitialised memory for logp / cat_logp (rows under a zero seq_mask included), V, state, alpha,
+ *     losses[3], seq / seq_logp (every column, also past the early exit), n_steps, dstate, dlogp, dslp.
+ *     ACCUMULATED outputs (parameter gradients g; dV, dvproj, dpos of xg_step_bwd) are added into.
  *   - No library-global mutable state: arithmetic mode, packed weights, side streams and
  *     data-parallel events all travel in XgRun.
  *     The workspace written by a *_fwd call must be handed unchanged to the matching *_bwd.
@@ -254,8 +263,10 @@ int xg_aux_destroy(void *aux);
  * mode GREEDY: argmax (ties -> lowest index, :186); SAMPLE: inverse-CDF draw from
  * exp(logp/temperature) with caller-supplied uniforms (T,B) in [0,1) (:190-194);
  * REPLAY: take `forced` (B,T-1) tokens.  T = seq_length+1 core steps are always run
- * (no per-step host sync, cf. :206); seq / seq_logp are (B,T-1), rows past the reference's
- * early exit are zero tokens.  n_steps (device int32) receives the reference's n. */
+ * (no per-step host sync, cf. :206); seq / seq_logp are (B,T-1), every element is written by the
+ * library (the caller need not zero them): a finished row and every column past the reference's
+ * early exit hold zero tokens (REPLAY returns the forced tokens as they are); seq_logp holds the chosen token's log-prob in every column (the
+ * criteria mask it by seq / n_steps).  n_steps (device int32) receives the reference's n. */
 int xg_rollout(void *stream, const XgDims *d, const XgParams *p, const XgBnState *bn,
                const XgBatch *x, const XgRun *run, int mode, const float *uniforms,
                const int64_t *forced, float temperature, void *ws, size_t ws_bytes,
