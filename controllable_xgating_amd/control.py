@@ -1,0 +1,75 @@
+"""Controlled generation: caption a video under chosen POS templates.
+
+The captioner is steered by the global POS vector ``pos_feats`` (caption_src/data_io.py:215-217: the last state of the POS
+generator's rollout).  ``PosModel.sample_forced`` rolls the POS generator along a caller's tag sequence instead of its own greedy
+choice (include/xgate_pos_control.h), S templates for each of B videos; ``caption_with_templates`` feeds the resulting states to the
+captioner without leaving the device.  Eval mode, fp32, one GPU; sharing the captioner's encoder across a video's templates is
+not done (the video inputs are repeated per template).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+
+def _is_seq(x):
+    return isinstance(x, (list, tuple))
+
+
+def pad_templates(templates, seq_length, category_size):
+    """POS templates as the (B,S,L) int64 tensor `PosModel.sample_forced` takes, L = seq_length, padded with 0 (the end tag).
+
+    `templates`: nested lists ``[video][template][tag]`` (ragged in the last level; ``[video][tag]`` means one template per video)
+    or an integer array / tensor (B,S,L') or (B,L') with L' <= L.  Raises ValueError for a template longer than L, a video with
+    another number of templates than the first, and a tag outside [0, category_size).  A tensor that already lives on the GPU is
+    padded there and its tags are NOT read (that would synchronise): the kernel clamps them into range."""
+    L, Cn = int(seq_length), int(category_size)
+    if _is_seq(templates):
+        rows = list(templates)
+        if not rows:
+            raise ValueError("no templates")
+        if not any(_is_seq(v) for r in rows for v in r):
+            rows = [[r] for r in rows]                      # [video][tag]: one template per video
+        S = len(rows[0])
+        if S < 1:
+            raise ValueError("every video needs at least one template")
+        out = np.zeros((len(rows), S, L), dtype=np.int64)
+        for b, r in enumerate(rows):
+            if len(r) != S:
+                raise ValueError("video %d has %d templates, video 0 has %d" % (b, len(r), S))
+            for s, tags in enumerate(r):
+                if len(tags) > L:
+                    raise ValueError("template %d of video %d has %d tags, seq_length is %d" % (s, b, len(tags), L))
+                out[b, s, :len(tags)] = np.asarray(tags, dtype=np.int64)
+        t = torch.from_numpy(out)
+    else:
+        t = torch.as_tensor(templates)
+        if t.is_floating_point() or t.dtype == torch.bool:
+            raise ValueError("templates are integer tags")
+        if t.dim() == 2:
+            t = t.unsqueeze(1)
+        if t.dim() != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError("templates (B,S,L') or (B,L') expected, got %s" % (tuple(t.shape),))
+        if t.shape[2] > L:
+            raise ValueError("templates have %d tags, seq_length is %d" % (t.shape[2], L))
+        t = F.pad(t.long(), (0, L - t.shape[2]))
+    if not t.is_cuda and t.numel() and (int(t.min()) < 0 or int(t.max()) >= Cn):
+        raise ValueError("tags must lie in [0, %d)" % Cn)
+    return t.contiguous()
+
+
+def caption_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, opt={}):
+    """Caption each of the B videos under each of its S POS templates: (seq (B,S,n) int64, seqLogprobs (B,S,n), template_score
+    (B,S)).  The forced POS rollout (``pos_model.sample_forced``) leaves `pos_feats` (B*S,R) on the device and the captioner's
+    ``sample`` (``opt`` as there: greedy, sampled, or beam search with beam_size > 1) runs over the B*S rows, the video inputs
+    repeated per template; nothing is read back between the two.  template_score is the log-probability the POS generator gives
+    the template (end tag included).  Inference only: both models run under ``torch.no_grad()``, so nothing returned carries a
+    gradient (a sampled captioner rollout that is to be trained on goes through ``cap_model.sample`` directly)."""
+    with torch.no_grad():
+        tag_logp, _, _, pos_feats = pos_model.sample_forced(feats_rgb, feats_opfl, feat_mask, templates, collect_states=False,
+                                                            trim=False)
+        B, S = tag_logp.shape[:2]
+        seq, slp = cap_model.sample(feats_rgb.repeat_interleave(S, 0), feats_opfl.repeat_interleave(S, 0),
+                                    feat_mask.repeat_interleave(S, 0), pos_feats, opt)
+    return seq.reshape(B, S, -1), slp.reshape(B, S, -1), tag_logp.sum(2)

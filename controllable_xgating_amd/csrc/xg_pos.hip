@@ -463,11 +463,11 @@ int encoder(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnStat
     return product(st, BK, R, w.Hcat, 2 * R, p->fusion_w, 2 * R, nullptr, 0, nullptr, 0, p->fusion_b, V, R, true);
 }
 
-// encoder, init_hidden (SAModel.py:54-60: the sum of V over all K rows over the mask count) and the per-call hoisted operands, then
-// the T decoder steps
-int decode(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo, const float* fm,
-           CellHeadArgs ca, const Ws& w) {
-    const int B = d->B, K = d->K, R = d->R, A = d->A, E = d->E, C = d->C, T = d->T;
+// encoder, init_hidden (SAModel.py:54-60: the sum of V over all K rows over the mask count) into X[:, R:2R] and c, and the per-call
+// hoisted operands: v2a(V), the token table and the packed step weights
+int prologue(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
+             const float* fm, const Ws& w) {
+    const int B = d->B, K = d->K, R = d->R, A = d->A, E = d->E, C = d->C;
     XG_TRY(encoder(st, d, p, bn, fr, fo, fm, w.V, w));
     XG_TRY(xgk_masked_mean(st, w.V, fm, w.vbar, B, K, R));
     XG_TRY(product(st, B, R, w.vbar, R, p->ih1_w, R, nullptr, 0, nullptr, 0, p->ih1_b, w.X + R, 2 * R));
@@ -481,6 +481,14 @@ int decode(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState
     hipLaunchKernelGGL(pos_fold_bias_kernel, dim3(xg_cdiv(C * 4 * R, POS_TPB)), dim3(POS_TPB), 0, st, w.tab, p->a2h_b, p->h2h_b, C,
                        4 * R);
     XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+
+// the prologue, then the T decoder steps
+int decode(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo, const float* fm,
+           CellHeadArgs ca, const Ws& w) {
+    const int B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, T = d->T;
+    XG_TRY(prologue(st, d, p, bn, fr, fo, fm, w));
     ca.S = w.S; ca.tab = w.tab; ca.logit_w = p->logit_w; ca.logit_b = p->logit_b;
     ca.X = w.X; ca.c = w.c; ca.B = B; ca.R = R; ca.C = C; ca.T = T;
     int nsplit = STEP_TPB / R;
@@ -1098,4 +1106,365 @@ extern "C" int xgpt_backward(void* stream, const XgpDims* d, const XgpParams* p,
         return XG_EINVAL;
     if (ws_bytes < tws_layout(d, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
     return backward((hipStream_t)stream, d, p, g, run, feats_rgb, feats_opfl, feat_mask, Tp, dlogp, tws_layout(d, ws));
+}
+
+// ==================================================================================================================================
+// Controlled generation (include/xgate_pos_control.h): the greedy rollout with the choice replaced by the caller's tag sequence, S
+// templates for each of B videos.  The prologue (encoder, init_hidden, v2a(V), the token table, the packed weights) runs once over
+// the B videos; one launch copies each video's initial h and c to its S rows (row b S + s); then the four launches of the step run
+// over the M = B S rows: h2a, attention, a2h + h2h, cell + head.
+//   attention      pos_attn_group_kernel: one workgroup per (video, group of CTRL_G templates).  Every row of the video's v2a(V) and
+//                  V is fetched once and applied to each p-vector of the group, so the step reads the video's operands ceil(S / G)
+//                  times instead of S times.  A row's scores and context sums are pos_attn_kernel's expressions in its order; its
+//                  softmax is reduced by one wave (lane-strided partials, then the wave reduction) where pos_attn_kernel sums
+//                  serially over k, so the two kernels may differ in the last bits.  Every row has one fixed order whatever group
+//                  it falls in; S = 1 runs pos_attn_kernel itself, which is what makes that case bit-identical to the greedy call.
+//   cell + head    pos_cell_head_forced_kernel: the tag and the `unfinished` mask of the step from the template, the cell, then
+//                  the log-sum-exp of the head and ONE gathered log-probability (the next tag's); no argmax.
+// ==================================================================================================================================
+#include "../../include/xgate_pos_control.h"
+
+namespace {
+
+constexpr int CTRL_G = XGPC_TEMPLATE_GROUP;
+
+// the initial state of video b (X[b, R:2R], c[b]) to its S rows
+__global__ void __launch_bounds__(POS_TPB) pos_bcast_state_kernel(const float* __restrict__ X, const float* __restrict__ c,
+                                                                  float* __restrict__ X2, float* __restrict__ c2, int S, int R,
+                                                                  int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * POS_TPB + threadIdx.x;
+    if (i >= n) return;
+    const int64_t row = i / R, b = row / S;
+    const int r = (int)(i - row * R);
+    X2[row * 2 * R + R + r] = X[b * 2 * R + R + r];
+    c2[i] = c[b * R + r];
+}
+
+// pos_attn_kernel for G templates of one video at a time: workgroup (b, group) serves rows b S + g0 .. + cnt - 1 (cnt < G in a
+// video's last group when S % G != 0; the missing rows compute on zeros and store nothing).  P (M,A) and X (M,2R) are per row, Q
+// (B,K,A) and V (B,K,R) per video.  The context parts take over the LDS of the p-vectors, which the scores are done with.
+template <int G, bool V4>
+__global__ void __launch_bounds__(STEP_TPB) pos_attn_group_kernel(const float* __restrict__ P, const float* __restrict__ Q,
+                                                                  const float* __restrict__ V, const float* __restrict__ w, float* X,
+                                                                  int K, int R, int A, int S, int nsplit, int pr_floats) {
+    extern __shared__ float lds[];
+    float* ps = lds;                          // G x A, later red: nsplit x G x R
+    float* red = lds;
+    float* wsh = lds + pr_floats;             // A (pr_floats and the A below are rounded up to 4 floats: 16-byte rows for V4)
+    float* al = wsh + (A + 3) / 4 * 4;        // G x K
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ng = (S + G - 1) / G;
+    const int b = blockIdx.x / ng, g0 = (blockIdx.x - b * ng) * G;
+    const int cnt = S - g0 < G ? S - g0 : G;
+    const size_t row0 = (size_t)b * S + g0;
+    const float* vb = V + (size_t)b * K * R;
+    // (tests/test_gpu_pos_control.py: test_cases_reach_the_branches_they_name restates VREG, STEP_TPB and nsplit to pick a K past
+    // the prefetch: change them together)
+    constexpr int VREG = 16;
+    const bool vpre = nsplit * R <= STEP_TPB && xg_cdiv_d(K, nsplit) <= VREG;
+    const int vr = tid % R, vpart = tid / R;
+    float vreg[VREG];
+    if (vpre && tid < nsplit * R) {
+#pragma unroll
+        for (int i = 0; i < VREG; ++i) {
+            const int k = vpart + i * nsplit;
+            vreg[i] = k < K ? vb[(size_t)k * R + vr] : 0.f;
+        }
+    }
+    for (int a = tid; a < A; a += STEP_TPB) {
+        wsh[a] = w[a];
+#pragma unroll
+        for (int g = 0; g < G; ++g) ps[g * A + a] = g < cnt ? P[(row0 + g) * A + a] : 0.f;
+    }
+    __syncthreads();
+    for (int k0 = wave; k0 < K; k0 += 2 * STEP_WAVES) {
+        const int k1 = k0 + STEP_WAVES;
+        const bool two = k1 < K;                                // wave-uniform
+        const float* q0 = Q + ((size_t)b * K + k0) * A;
+        const float* q1 = Q + ((size_t)b * K + (two ? k1 : k0)) * A;
+        float acc0[G], acc1[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc0[g] = acc1[g] = 0.f;
+        if (V4) {
+            const float4* q04 = reinterpret_cast<const float4*>(q0);
+            const float4* q14 = reinterpret_cast<const float4*>(q1);
+            const float4* w4 = reinterpret_cast<const float4*>(wsh);
+#pragma unroll 2
+            for (int a4 = lane; a4 < A / 4; a4 += 64) {
+                const float4 u = q04[a4];
+                const float4 v = q14[a4];
+                const float4 ww = w4[a4];
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const float4 pp = reinterpret_cast<const float4*>(ps + g * A)[a4];
+                    acc0[g] += ww.x * xg_tanh(pp.x + u.x) + ww.y * xg_tanh(pp.y + u.y) + ww.z * xg_tanh(pp.z + u.z) +
+                               ww.w * xg_tanh(pp.w + u.w);
+                    acc1[g] += ww.x * xg_tanh(pp.x + v.x) + ww.y * xg_tanh(pp.y + v.y) + ww.z * xg_tanh(pp.z + v.z) +
+                               ww.w * xg_tanh(pp.w + v.w);
+                }
+            }
+        } else {
+#pragma unroll 2
+            for (int a = lane; a < A; a += 64) {
+                const float u = q0[a], v = q1[a], ww = wsh[a];
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const float pp = ps[g * A + a];
+                    acc0[g] += ww * xg_tanh(pp + u);
+                    acc1[g] += ww * xg_tanh(pp + v);
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float s0 = wave_sum(acc0[g]), s1 = wave_sum(acc1[g]);
+            if (lane == 0) {
+                al[g * K + k0] = s0;
+                if (two) al[g * K + k1] = s1;
+            }
+        }
+    }
+    __syncthreads();
+    // alpha = softmax_k(e), not masked: wave g normalises row g (a fixed order: lane-strided partials, then the wave reduction)
+    if (wave < G) {
+        float* ar = al + wave * K;
+        float mx = -INFINITY;
+        for (int k = lane; k < K; k += 64) mx = fmaxf(mx, ar[k]);
+        mx = wave_max(mx);
+        float s = 0.f;
+        for (int k = lane; k < K; k += 64) s += __expf(ar[k] - mx);
+        s = wave_sum(s);
+        for (int k = lane; k < K; k += 64) ar[k] = __expf(ar[k] - mx) / s;
+    }
+    __syncthreads();                                           // (alpha is final, and every wave is done with ps)
+    if (vpre) {
+        if (tid < nsplit * R) {
+            float acc[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) acc[g] = 0.f;
+#pragma unroll
+            for (int i = 0; i < VREG; ++i) {
+                const int k = vpart + i * nsplit;
+                if (k < K) {
+#pragma unroll
+                    for (int g = 0; g < G; ++g) acc[g] += al[g * K + k] * vreg[i];
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) red[(vpart * G + g) * R + vr] = acc[g];
+        }
+    } else {
+        for (int i = tid; i < nsplit * R; i += STEP_TPB) {
+            const int r = i % R, part = i / R;
+            float acc[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) acc[g] = 0.f;
+            for (int k = part; k < K; k += nsplit) {
+                const float v = vb[(size_t)k * R + r];
+#pragma unroll
+                for (int g = 0; g < G; ++g) acc[g] += al[g * K + k] * v;
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) red[(part * G + g) * R + r] = acc[g];
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < cnt * R; i += STEP_TPB) {
+        const int g = i / R, r = i - g * R;
+        float acc = red[g * R + r];
+        for (int part = 1; part < nsplit; ++part) acc += red[(part * G + g) * R + r];
+        X[(row0 + g) * 2 * R + r] = acc;
+    }
+}
+
+struct ForcedArgs {
+    const float* S;              // (M,4R) af a2h^T + h h2h^T, no bias
+    const float* tab;            // (C,4R) embed i2h^T + the three biases
+    const float *logit_w, *logit_b;
+    float* X;                    // (M,2R): h read from and h' written to columns R..2R
+    float* c;                    // (M,R) cell state, in place
+    const int64_t* tmpl;         // (M,T-1) the tags
+    float *tag_logp, *states, *masks, *pos_feats;   // (M,T-1), (M,T,R) or null, (M,T), (M,R)
+    int R, C, T, t;
+};
+
+// one workgroup per row, step t: the tag fed is tmpl[t-1] (BOS at t = 0) under the mask unfinished_t = unfinished_{t-1} (tag > 0)
+// (unfinished_{t-1} is masks[t-1], written by the step before); pos_cell_head_kernel's cell; then, for t < T - 1, the head's
+// log-sum-exp and the log-probability of the NEXT tag, tmpl[t], which counts while the row is unfinished at step t: up to and
+// including its first 0
+__global__ void __launch_bounds__(STEP_TPB) pos_cell_head_forced_kernel(ForcedArgs a) {
+    extern __shared__ float lds[];
+    float* hs = lds;             // R
+    float* lg = lds + a.R;       // C
+    const int tid = threadIdx.x, R = a.R, C = a.C, T = a.T, t = a.t;
+    const size_t row = blockIdx.x;
+    const int64_t* tr = a.tmpl + row * (T - 1);
+    int64_t tk = 0;
+    float m = 1.0f;
+    if (t > 0) {
+        tk = tr[t - 1];
+        tk = tk < 0 ? 0 : (tk >= C ? C - 1 : tk);
+        m = tk > 0 ? a.masks[row * T + t - 1] : 0.0f;
+    }
+    const float* s = a.S + row * 4 * R;
+    const float* tb = a.tab + (size_t)tk * 4 * R;
+    float* xh = a.X + row * 2 * R + R;
+    float* cb = a.c + row * R;
+    float* st = a.states ? a.states + (row * T + t) * R : nullptr;
+    float* pf = t == T - 1 ? a.pos_feats + row * R : nullptr;
+    for (int j = tid; j < R; j += STEP_TPB) {
+        const float ig = xg_sigmoid(s[j] + tb[j]), fg = xg_sigmoid(s[R + j] + tb[R + j]);
+        const float og = xg_sigmoid(s[2 * R + j] + tb[2 * R + j]), gg = xg_tanh(s[3 * R + j] + tb[3 * R + j]);
+        const float cp = cb[j], hp = xh[j];
+        float cn = fg * cp + ig * gg;
+        cn = cn * m + cp * (1.0f - m);
+        float hn = og * xg_tanh(cn);
+        hn = hn * m + hp * (1.0f - m);
+        cb[j] = cn;
+        xh[j] = hn;
+        hs[j] = hn;
+        if (st) st[j] = hn;
+        if (pf) pf[j] = hn;
+    }
+    if (tid == 0) a.masks[row * T + t] = m;
+    if (t + 1 >= T) return;                                     // (no tag follows the last step)
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int cc = wave; cc < C; cc += STEP_WAVES) {
+        const float* wr = a.logit_w + (size_t)cc * R;
+        float acc = 0.f;
+#pragma unroll 8
+        for (int j = lane; j < R; j += 64) acc += wr[j] * hs[j];
+        acc = wave_sum(acc);
+        if (lane == 0) lg[cc] = acc + a.logit_b[cc];
+    }
+    __syncthreads();
+    int64_t nx = tr[t];
+    nx = nx < 0 ? 0 : (nx >= C ? C - 1 : nx);
+    float* out = a.tag_logp + row * (T - 1) + t;
+    if (C <= 64) {                                              // one lane per category
+        if (wave == 0) {
+            const float v = lane < C ? lg[lane] : -INFINITY;
+            const float mx = wave_max(v);
+            const float lse = mx + logf(wave_sum(lane < C ? expf(v - mx) : 0.f));
+            if (lane == 0) *out = m != 0.0f ? lg[nx] - lse : 0.0f;
+        }
+    } else if (tid == 0) {
+        float mx = lg[0];
+        for (int cc = 1; cc < C; ++cc) mx = fmaxf(mx, lg[cc]);
+        float se = 0.f;
+        for (int cc = 0; cc < C; ++cc) se += expf(lg[cc] - mx);
+        *out = m != 0.0f ? lg[nx] - (mx + logf(se)) : 0.0f;
+    }
+}
+
+// the workspace: xgp's regions for the B videos, then the step's operands for the M = B S rows
+struct CWs {
+    Ws v;
+    float *X, *P, *S, *c;
+    size_t floats;
+};
+
+CWs cws_layout(const XgpDims* d, int S, void* base) {
+    CWs w;
+    w.v = ws_layout(d, base);
+    const size_t M = (size_t)d->B * S, R = d->R, A = d->A;
+    float* p = (float*)base;
+    size_t off = w.v.floats;
+    auto take = [&](size_t n) { float* r = p ? p + off : nullptr; off += (n + 63) / 64 * 64; return r; };
+    w.X = take(M * 2 * R);           // [af ; h] of every row
+    w.P = take(M * A);
+    w.S = take(M * 4 * R);
+    w.c = take(M * R);
+    w.floats = off;
+    return w;
+}
+
+// LDS floats of pos_attn_group_kernel<G>: the p-vectors / context parts, w, the scores
+// (restated as group_lds in tests/test_gpu_pos_control.py, with the 64 KiB limit of sample_forced below, to name the cases that take
+// the one-template form: change them together)
+size_t attn_group_lds(int G, int K, int R, int A, int nsplit, int* pr_floats) {
+    const size_t pr = ((size_t)G * (A > nsplit * R ? A : nsplit * R) + 3) / 4 * 4;
+    *pr_floats = (int)pr;
+    return (pr + (size_t)(A + 3) / 4 * 4 + (size_t)G * K) * sizeof(float);
+}
+
+bool ctrl_dims_ok(const XgpDims* d, int S) {
+    if (!dims_ok(d, true) || d->T < 2 || S < 1) return false;
+    const int64_t M = (int64_t)d->B * S;
+    // (A, R <= 4096: 32-bit row offsets into the (M, .) operands, and the (M,T,R) states)
+    return M * 4 * 4096 < (1LL << 31) && M * d->T * d->R < (1LL << 31);
+}
+
+template <int G>
+void launch_attn_group(hipStream_t st, int B, int S, bool v4, size_t lds, const float* P, const float* Q, const float* V,
+                       const float* w, float* X, int K, int R, int A, int nsplit, int pr_floats) {
+    const dim3 grid(B * xg_cdiv(S, G));
+    if (v4) hipLaunchKernelGGL((pos_attn_group_kernel<G, true>), grid, dim3(STEP_TPB), lds, st, P, Q, V, w, X, K, R, A, S, nsplit, pr_floats);
+    else    hipLaunchKernelGGL((pos_attn_group_kernel<G, false>), grid, dim3(STEP_TPB), lds, st, P, Q, V, w, X, K, R, A, S, nsplit, pr_floats);
+}
+
+int sample_forced(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
+                  const float* fm, ForcedArgs fa, const CWs& w) {
+    const int B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, T = d->T, M = B * S;
+    XG_TRY(prologue(st, d, p, bn, fr, fo, fm, w.v));
+    const int64_t n = (int64_t)M * R;
+    hipLaunchKernelGGL(pos_bcast_state_kernel, dim3((unsigned)xg_cdiv(n, POS_TPB)), dim3(POS_TPB), 0, st, w.v.X, w.v.c, w.X, w.c, S, R, n);
+    XG_CHECK_LAUNCH();
+    fa.S = w.S; fa.tab = w.v.tab; fa.logit_w = p->logit_w; fa.logit_b = p->logit_b;
+    fa.X = w.X; fa.c = w.c; fa.R = R; fa.C = C; fa.T = T;
+    int nsplit = STEP_TPB / R;
+    nsplit = nsplit < 1 ? 1 : (nsplit > K ? K : nsplit);
+    const size_t lds_attn1 = (size_t)(2 * A + K + nsplit * R) * sizeof(float), lds_cell = (size_t)(R + C) * sizeof(float);
+    // the full group while its p-vectors fit the 64 KiB of LDS a workgroup gets without opting in; beyond that (A or R near
+    // 4096) one template per workgroup
+    int pr_floats = 0;
+    size_t lds_group = attn_group_lds(CTRL_G, K, R, A, nsplit, &pr_floats);
+    const bool full = lds_group <= 64 * 1024;
+    if (!full) lds_group = attn_group_lds(1, K, R, A, nsplit, &pr_floats);
+    const bool v4 = A % 4 == 0;
+    for (int t = 0; t < T; ++t) {
+        XG_TRY(product(st, M, A, w.X + R, 2 * R, p->h2a_w, R, nullptr, 0, nullptr, 0, p->h2a_b, w.P, A, false, w.v.pk_h2a));
+        if (S == 1) {
+            if (v4) hipLaunchKernelGGL(pos_attn_kernel<true>, dim3(B), dim3(STEP_TPB), lds_attn1, st, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit);
+            else    hipLaunchKernelGGL(pos_attn_kernel<false>, dim3(B), dim3(STEP_TPB), lds_attn1, st, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit);
+        } else if (full) {
+            launch_attn_group<CTRL_G>(st, B, S, v4, lds_group, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit, pr_floats);
+        } else {
+            launch_attn_group<1>(st, B, S, v4, lds_group, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit, pr_floats);
+        }
+        XG_CHECK_LAUNCH();
+        XG_TRY(product(st, M, 4 * R, w.X, 2 * R, p->a2h_w, R, w.X + R, 2 * R, p->h2h_w, R, nullptr, w.S, 4 * R, false, w.v.pk_a2h,
+                       w.v.pk_h2h));
+        fa.t = t;
+        hipLaunchKernelGGL(pos_cell_head_forced_kernel, dim3(M), dim3(STEP_TPB), lds_cell, st, fa);
+        XG_CHECK_LAUNCH();
+    }
+    return XG_OK;
+}
+
+}  // namespace
+
+extern "C" int xgpc_version(void) { return XGPC_VERSION; }
+
+extern "C" size_t xgpc_workspace_bytes(const XgpDims* d, int32_t S) {
+    if (!ctrl_dims_ok(d, S)) return 0;
+    return cws_layout(d, S, nullptr).floats * sizeof(float);
+}
+
+extern "C" int xgpc_sample_forced(void* stream, const XgpDims* d, int32_t S, const XgpParams* p, const XgBnState* bn,
+                                  const float* feats_rgb, const float* feats_opfl, const float* feat_mask, const int64_t* templates,
+                                  float* tag_logp, float* states, float* masks, float* pos_feats, int32_t* n_out, void* ws,
+                                  size_t ws_bytes) {
+    if (!ctrl_dims_ok(d, S) || !params_ok(p) || !bn_ok(bn) || !feats_rgb || !feats_opfl || !feat_mask || !templates || !tag_logp ||
+        !masks || !pos_feats || !n_out || !ws)
+        return XG_EINVAL;
+    if (ws_bytes < cws_layout(d, S, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    ForcedArgs fa{};
+    fa.tmpl = templates; fa.tag_logp = tag_logp; fa.states = states; fa.masks = masks; fa.pos_feats = pos_feats;
+    XG_TRY(sample_forced(st, d, S, p, bn, feats_rgb, feats_opfl, feat_mask, fa, cws_layout(d, S, ws)));
+    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, nullptr, masks, d->B * S, d->T, 1, n_out);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
 }

@@ -6,7 +6,8 @@ fp32 products.  ``PosModel`` keeps the reference's class surface and state_dict 
 call (the reference's data-dependent lengths T' and n are computed on the device).  In train mode the teacher-forced forward runs
 include/xgate_pos_train.h (BatchNorm over the batch statistics, hash dropout) and ``loss.backward()`` its HIP backward; the parameters
 live in one flat buffer (``flat_parameters()`` / ``flat_grads()``) so that ``train.ClipAdam`` updates them in one launch.  Train-mode
-``sample()``, beam search and sampled rollouts are not implemented and raise.
+``sample()``, beam search and sampled rollouts are not implemented and raise.  ``sample_forced`` rolls the generator along a caller's
+POS templates, several per video (include/xgate_pos_control.h; control.py carries the result into the captioner).
 """
 from __future__ import annotations
 
@@ -69,6 +70,7 @@ class PosModel(nn.Module):
             self.logit.bias.fill_(0)
             self.logit.weight.uniform_(-0.1, 0.1)
         self._ws = {}
+        self._cws = None                # workspace of sample_forced (grows to the largest call)
         self._tws = None                # training workspace: the saved activations of the last train-mode forward
         self._train_gen = 0             # bumped by every train-mode forward: a backward of an older one must not read them
         self._flat = self._gflat = None
@@ -318,6 +320,51 @@ class PosModel(nn.Module):
                                               n_out.data_ptr(), ws.data_ptr(), ws.numel()), "xgp_sample_greedy")
         n = int(n_out.item())                       # the one host synchronisation of the rollout
         return seq[:, :n], slp[:, :n], states[:, :n + 1], masks[:, :n + 1]
+
+    def sample_forced(self, feats_rgb, feats_opfl, feat_mask, templates, collect_states=True, trim=True):
+        """The rollout of `sample` with the greedy choice replaced by the caller's POS templates (include/xgate_pos_control.h),
+        S templates for each of the B videos: (tag_logp (B,S,n), states (B,S,n+1,R) or None, masks (B,S,n+1), pos_feats (B*S,R)).
+
+        `templates`: what control.pad_templates takes -- (B,S,L') or (B,L') (one template per video) integer tags with
+        L' <= seq_length, or nested lists; entry t-1 is the tag fed at step t, a 0 ends the template and whatever follows it is
+        ignored.  tag_logp[b,s,t-1] is the log-probability of tag t given the tags before it, up to and including the end tag, 0
+        after it: its sum over the last axis is the template's score.  pos_feats, row b S + s, is the state after the last step:
+        the captioner's global POS vector for video b under template s.  `trim`: cut to the reference's n (the longest template,
+        one host synchronisation); trim=False returns the full seq_length and does not synchronise.  `collect_states=False`
+        skips storing the states."""
+        from . import _native_pos_control as npc
+        from .control import pad_templates
+        self._check_eval(feats_rgb, feats_opfl, feat_mask)
+        fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
+        B, K = fm.shape
+        L = self.seq_length
+        dev = fr.device
+        tm = pad_templates(templates, L, self.category_size).to(dev)
+        if tm.shape[0] != B:
+            raise ValueError("templates for %d videos, features for %d" % (tm.shape[0], B))
+        S = tm.shape[1]
+        dims = self._dims(B, K, L + 1)
+        lib = npc.lib()
+        nbytes = lib.xgpc_workspace_bytes(C.byref(dims), S)
+        if nbytes == 0:
+            raise nv.XgError("xgpc_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S))
+        ws = self._cws
+        if ws is None or ws.device != dev or ws.numel() < nbytes:
+            ws = self._cws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        tag_logp = torch.empty(B, S, L, device=dev)
+        states = torch.empty(B, S, L + 1, self.rnn_size, device=dev) if collect_states else None
+        masks = torch.empty(B, S, L + 1, device=dev)
+        pos_feats = torch.empty(B * S, self.rnn_size, device=dev)
+        n_out = torch.empty(1, dtype=torch.int32, device=dev)
+        P, bn = self._params(), self._bn()
+        nv.check(lib.xgpc_sample_forced(_stream(), C.byref(dims), S, C.byref(P), C.byref(bn), fr.data_ptr(), fo.data_ptr(),
+                                        fm.data_ptr(), tm.data_ptr(), tag_logp.data_ptr(),
+                                        None if states is None else states.data_ptr(), masks.data_ptr(), pos_feats.data_ptr(),
+                                        n_out.data_ptr(), ws.data_ptr(), ws.numel()), "xgpc_sample_forced")
+        if not trim:
+            return tag_logp, states, masks, pos_feats
+        n = int(n_out.item())                       # the one host synchronisation of the call
+        return tag_logp[:, :, :n], None if states is None else states[:, :, :n + 1], masks[:, :, :n + 1], pos_feats
 
 
 class _PosTrainFunction(torch.autograd.Function):
