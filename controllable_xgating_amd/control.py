@@ -3,8 +3,9 @@
 The captioner is steered by the global POS vector ``pos_feats`` (caption_src/data_io.py:215-217: the last state of the POS
 generator's rollout).  ``PosModel.sample_forced`` rolls the POS generator along a caller's tag sequence instead of its own greedy
 choice (include/xgate_pos_control.h), S templates for each of B videos; ``caption_with_templates`` feeds the resulting states to the
-captioner without leaving the device.  Eval mode, fp32, one GPU; sharing the captioner's encoder across a video's templates is
-not done (the video inputs are repeated per template).
+captioner without leaving the device.  ``PosModel.sample_templates`` (include/xgate_pos_sample.h) lets the generator draw the templates
+itself, ``caption_sampled`` captions under them and ``first_occurrences`` marks a video's distinct draws.  Eval mode, fp32, one GPU;
+sharing the captioner's encoder across a video's templates is not done (the video inputs are repeated per template).
 """
 from __future__ import annotations
 
@@ -73,3 +74,35 @@ def caption_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mas
         seq, slp = cap_model.sample(feats_rgb.repeat_interleave(S, 0), feats_opfl.repeat_interleave(S, 0),
                                     feat_mask.repeat_interleave(S, 0), pos_feats, opt)
     return seq.reshape(B, S, -1), slp.reshape(B, S, -1), tag_logp.sum(2)
+
+
+def first_occurrences(templates):
+    """(B,S) bool for templates (B,S,L): True where no EARLIER template of the same video is identical (slot 0 always is), so
+    ``templates[first]`` are a video's distinct templates in the order they were drawn.  Torch ops on the tensor's device; nothing
+    is read back."""
+    t = torch.as_tensor(templates)
+    if t.dim() != 3:
+        raise ValueError("templates (B,S,L) expected, got %s" % (tuple(t.shape),))
+    S = t.shape[1]
+    same = (t.unsqueeze(2) == t.unsqueeze(1)).all(3)                         # (B,S,S): template s equals template s'
+    earlier = torch.ones(S, S, dtype=torch.bool, device=t.device).tril(-1)   # [s, s'] : s' < s
+    return ~(same & earlier).any(2)
+
+
+def caption_sampled(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, S, temperature=1.0, uniforms=None, generator=None,
+                    opt={}):
+    """Caption each of the B videos under S POS templates the generator draws itself: (seq (B,S,n) int64, seqLogprobs (B,S,n),
+    templates (B,S,L) int64, template_score (B,S), first (B,S) bool).  The sampled POS rollout (``pos_model.sample_templates``:
+    `temperature`, `uniforms`, `generator` as there) leaves `pos_feats` (B*S,R) on the device and the captioner's ``sample``
+    (``opt`` as there) runs over the B*S rows exactly as in ``caption_with_templates``; nothing is read back between the two.
+    template_score is the untempered log-probability the POS generator gives the drawn template (end tag included); `first`
+    marks each video's distinct templates (``first_occurrences``).  Inference only: both models run under ``torch.no_grad()``."""
+    with torch.no_grad():
+        templates, tag_logp, _, _, pos_feats = pos_model.sample_templates(feats_rgb, feats_opfl, feat_mask, S, temperature=temperature,
+                                                                          uniforms=uniforms, generator=generator,
+                                                                          collect_states=False, trim=False)
+        B, S = tag_logp.shape[:2]
+        seq, slp = cap_model.sample(feats_rgb.repeat_interleave(S, 0), feats_opfl.repeat_interleave(S, 0),
+                                    feat_mask.repeat_interleave(S, 0), pos_feats, opt)
+        first = first_occurrences(templates)
+    return seq.reshape(B, S, -1), slp.reshape(B, S, -1), templates, tag_logp.sum(2), first

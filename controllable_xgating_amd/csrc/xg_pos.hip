@@ -1404,8 +1404,11 @@ void launch_attn_group(hipStream_t st, int B, int S, bool v4, size_t lds, const 
     else    hipLaunchKernelGGL((pos_attn_group_kernel<G, false>), grid, dim3(STEP_TPB), lds, st, P, Q, V, w, X, K, R, A, S, nsplit, pr_floats);
 }
 
-int sample_forced(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
-                  const float* fm, ForcedArgs fa, const CWs& w) {
+// the rollout over the M = B S rows; `cell` is the step's fourth launch (the forced kernel, or the sampled one of
+// xgate_pos_sample.h below: the same operands under the same field names) with lds_cell bytes of LDS
+template <class CellArgs>
+int rollout_rows(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
+                 const float* fm, CellArgs fa, void (*cell)(CellArgs), size_t lds_cell, const CWs& w) {
     const int B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, T = d->T, M = B * S;
     XG_TRY(prologue(st, d, p, bn, fr, fo, fm, w.v));
     const int64_t n = (int64_t)M * R;
@@ -1415,7 +1418,7 @@ int sample_forced(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, c
     fa.X = w.X; fa.c = w.c; fa.R = R; fa.C = C; fa.T = T;
     int nsplit = STEP_TPB / R;
     nsplit = nsplit < 1 ? 1 : (nsplit > K ? K : nsplit);
-    const size_t lds_attn1 = (size_t)(2 * A + K + nsplit * R) * sizeof(float), lds_cell = (size_t)(R + C) * sizeof(float);
+    const size_t lds_attn1 = (size_t)(2 * A + K + nsplit * R) * sizeof(float);
     // the full group while its p-vectors fit the 64 KiB of LDS a workgroup gets without opting in; beyond that (A or R near
     // 4096) one template per workgroup
     int pr_floats = 0;
@@ -1437,10 +1440,15 @@ int sample_forced(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, c
         XG_TRY(product(st, M, 4 * R, w.X, 2 * R, p->a2h_w, R, w.X + R, 2 * R, p->h2h_w, R, nullptr, w.S, 4 * R, false, w.v.pk_a2h,
                        w.v.pk_h2h));
         fa.t = t;
-        hipLaunchKernelGGL(pos_cell_head_forced_kernel, dim3(M), dim3(STEP_TPB), lds_cell, st, fa);
+        hipLaunchKernelGGL(cell, dim3(M), dim3(STEP_TPB), lds_cell, st, fa);
         XG_CHECK_LAUNCH();
     }
     return XG_OK;
+}
+
+int sample_forced(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
+                  const float* fm, ForcedArgs fa, const CWs& w) {
+    return rollout_rows(st, d, S, p, bn, fr, fo, fm, fa, pos_cell_head_forced_kernel, (size_t)(d->R + d->C) * sizeof(float), w);
 }
 
 }  // namespace
@@ -1464,6 +1472,162 @@ extern "C" int xgpc_sample_forced(void* stream, const XgpDims* d, int32_t S, con
     ForcedArgs fa{};
     fa.tmpl = templates; fa.tag_logp = tag_logp; fa.states = states; fa.masks = masks; fa.pos_feats = pos_feats;
     XG_TRY(sample_forced(st, d, S, p, bn, feats_rgb, feats_opfl, feat_mask, fa, cws_layout(d, S, ws)));
+    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, nullptr, masks, d->B * S, d->T, 1, n_out);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+
+// ==================================================================================================================================
+// Sampled templates (include/xgate_pos_sample.h): the forced rollout above with the tag of step t + 1 DRAWN at the end of step t
+// from the head's distribution and written to `templates`, where the next step's launch reads it as the forced kernel reads the
+// caller's.  Same prologue, same broadcast, same first three launches per step (rollout_rows), same workspace; only the fourth
+// launch differs: pos_cell_head_sampled_kernel.  The draw is the captioner's (xg_select.h): inverse CDF over
+// exp((x - max x) / temperature) from a uniform the caller supplies.
+// ==================================================================================================================================
+#include "../../include/xgate_pos_sample.h"
+
+namespace {
+
+struct SampledArgs {             // (ForcedArgs' operands under ForcedArgs' names: rollout_rows fills either)
+    const float* S;
+    const float* tab;
+    const float *logit_w, *logit_b;
+    float* X;
+    float* c;
+    int64_t* tmpl;               // (M,T-1) out: column t is written by step t and read by step t + 1
+    float *tag_logp, *states, *masks, *pos_feats;
+    const float* uniforms;       // (M,T-1)
+    float temperature;
+    int R, C, T, t;
+};
+
+// inclusive scan over the 64 lanes: row_shr 1, 2, 4, 8 inside each row of 16 (zeros shift in), then the totals of the rows before
+// the lane's own, added in row order.  Every lane must be active.
+__device__ __forceinline__ float wave_scan(float v) {
+    v += xg_dpp<0x111>(v);
+    v += xg_dpp<0x112>(v);
+    v += xg_dpp<0x114>(v);
+    v += xg_dpp<0x118>(v);
+    const float r0 = xg_readlane(v, 15), r1 = xg_readlane(v, 31), r2 = xg_readlane(v, 47);
+    const int row = (threadIdx.x & 63) >> 4;
+    const float before = row == 0 ? 0.f : (row == 1 ? r0 : (row == 2 ? r0 + r1 : (r0 + r1) + r2));
+    return before + v;
+}
+
+// one workgroup per row, step t: pos_cell_head_forced_kernel with the template an OUTPUT.  The tag fed is tmpl[t-1], which the
+// launch of step t - 1 drew (BOS at t = 0); the cell is the forced kernel's, expression for expression; then, for t < T - 1, the
+// head's logits and log-sum-exp as there, and the draw of tmpl[t]: the first category whose running sum of
+// w_c = exp((x_c - max x) / temperature) exceeds uniforms[t] * sum(w), C - 1 when none does.  tmpl[t] = tag * unfinished and
+// tag_logp[t] = the untempered log-probability of the tag while the row is unfinished at step t, 0 after.
+__global__ void __launch_bounds__(STEP_TPB) pos_cell_head_sampled_kernel(SampledArgs a) {
+    extern __shared__ float lds[];
+    float* hs = lds;             // R
+    float* lg = lds + a.R;       // C
+    float* wt = lg + a.C;        // C (the serial head's weights)
+    const int tid = threadIdx.x, R = a.R, C = a.C, T = a.T, t = a.t;
+    const size_t row = blockIdx.x;
+    int64_t* tr = a.tmpl + row * (T - 1);
+    int64_t tk = 0;
+    float m = 1.0f;
+    if (t > 0) {
+        tk = tr[t - 1];
+        tk = tk < 0 ? 0 : (tk >= C ? C - 1 : tk);
+        m = tk > 0 ? a.masks[row * T + t - 1] : 0.0f;
+    }
+    const float* s = a.S + row * 4 * R;
+    const float* tb = a.tab + (size_t)tk * 4 * R;
+    float* xh = a.X + row * 2 * R + R;
+    float* cb = a.c + row * R;
+    float* st = a.states ? a.states + (row * T + t) * R : nullptr;
+    float* pf = t == T - 1 ? a.pos_feats + row * R : nullptr;
+    for (int j = tid; j < R; j += STEP_TPB) {
+        const float ig = xg_sigmoid(s[j] + tb[j]), fg = xg_sigmoid(s[R + j] + tb[R + j]);
+        const float og = xg_sigmoid(s[2 * R + j] + tb[2 * R + j]), gg = xg_tanh(s[3 * R + j] + tb[3 * R + j]);
+        const float cp = cb[j], hp = xh[j];
+        float cn = fg * cp + ig * gg;
+        cn = cn * m + cp * (1.0f - m);
+        float hn = og * xg_tanh(cn);
+        hn = hn * m + hp * (1.0f - m);
+        cb[j] = cn;
+        xh[j] = hn;
+        hs[j] = hn;
+        if (st) st[j] = hn;
+        if (pf) pf[j] = hn;
+    }
+    if (tid == 0) a.masks[row * T + t] = m;
+    if (t + 1 >= T) return;                                     // (no tag follows the last step)
+    const float u = a.uniforms[row * (T - 1) + t];              // (requested here: the head's products hide the round trip)
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int cc = wave; cc < C; cc += STEP_WAVES) {
+        const float* wr = a.logit_w + (size_t)cc * R;
+        float acc = 0.f;
+#pragma unroll 8
+        for (int j = lane; j < R; j += 64) acc += wr[j] * hs[j];
+        acc = wave_sum(acc);
+        if (lane == 0) lg[cc] = acc + a.logit_b[cc];
+    }
+    __syncthreads();
+    float* out = a.tag_logp + row * (T - 1) + t;
+    if (C <= 64) {                                              // one lane per category
+        if (wave == 0) {
+            const float v = lane < C ? lg[lane] : -INFINITY;
+            const float mx = wave_max(v);
+            const float lse = mx + logf(wave_sum(lane < C ? expf(v - mx) : 0.f));
+            const float inc = wave_scan(lane < C ? expf((v - mx) / a.temperature) : 0.f);
+            const float target = u * xg_readlane(inc, C - 1);     // (the total in the last category's own summation order)
+            const unsigned long long pass = __ballot(lane < C && inc > target);
+            const int nx = pass ? __ffsll(pass) - 1 : C - 1;   // (nothing passes: rounding at the very end, or u = 1)
+            if (lane == 0) {
+                *out = m != 0.0f ? lg[nx] - lse : 0.0f;
+                tr[t] = m != 0.0f ? nx : 0;
+            }
+        }
+    } else if (tid == 0) {
+        float mx = lg[0];
+        for (int cc = 1; cc < C; ++cc) mx = fmaxf(mx, lg[cc]);
+        float se = 0.f;
+        for (int cc = 0; cc < C; ++cc) se += expf(lg[cc] - mx);
+        float tot = 0.f;
+        for (int cc = 0; cc < C; ++cc) {
+            wt[cc] = expf((lg[cc] - mx) / a.temperature);
+            tot += wt[cc];
+        }
+        const float target = u * tot;
+        int nx = C - 1;
+        float run = 0.f;
+        for (int cc = 0; cc < C; ++cc) {
+            run += wt[cc];
+            if (run > target) { nx = cc; break; }
+        }
+        *out = m != 0.0f ? lg[nx] - (mx + logf(se)) : 0.0f;
+        tr[t] = m != 0.0f ? nx : 0;
+    }
+}
+
+}  // namespace
+
+extern "C" int xgps_version(void) { return XGPS_VERSION; }
+
+extern "C" size_t xgps_workspace_bytes(const XgpDims* d, int32_t S) {
+    if (!ctrl_dims_ok(d, S)) return 0;
+    return cws_layout(d, S, nullptr).floats * sizeof(float);
+}
+
+extern "C" int xgps_sample_templates(void* stream, const XgpDims* d, int32_t S, float temperature, const XgpParams* p,
+                                     const XgBnState* bn, const float* feats_rgb, const float* feats_opfl, const float* feat_mask,
+                                     const float* uniforms, int64_t* templates, float* tag_logp, float* states, float* masks,
+                                     float* pos_feats, int32_t* n_out, void* ws, size_t ws_bytes) {
+    if (!ctrl_dims_ok(d, S) || !(temperature > 0.0f) || temperature == INFINITY || !params_ok(p) || !bn_ok(bn) || !feats_rgb ||
+        !feats_opfl || !feat_mask || !uniforms || !templates || !tag_logp || !masks || !pos_feats || !n_out || !ws)
+        return XG_EINVAL;
+    if (ws_bytes < cws_layout(d, S, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    SampledArgs sa{};
+    sa.tmpl = templates; sa.tag_logp = tag_logp; sa.states = states; sa.masks = masks; sa.pos_feats = pos_feats;
+    sa.uniforms = uniforms; sa.temperature = temperature;
+    XG_TRY(rollout_rows(st, d, S, p, bn, feats_rgb, feats_opfl, feat_mask, sa, pos_cell_head_sampled_kernel,
+                        (size_t)(d->R + 2 * d->C) * sizeof(float), cws_layout(d, S, ws)));
     hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, nullptr, masks, d->B * S, d->T, 1, n_out);
     XG_CHECK_LAUNCH();
     return XG_OK;

@@ -6,8 +6,9 @@ fp32 products.  ``PosModel`` keeps the reference's class surface and state_dict 
 call (the reference's data-dependent lengths T' and n are computed on the device).  In train mode the teacher-forced forward runs
 include/xgate_pos_train.h (BatchNorm over the batch statistics, hash dropout) and ``loss.backward()`` its HIP backward; the parameters
 live in one flat buffer (``flat_parameters()`` / ``flat_grads()``) so that ``train.ClipAdam`` updates them in one launch.  Train-mode
-``sample()``, beam search and sampled rollouts are not implemented and raise.  ``sample_forced`` rolls the generator along a caller's
-POS templates, several per video (include/xgate_pos_control.h; control.py carries the result into the captioner).
+``sample()``, beam search and ``sample(sample_max=0)`` are not implemented and raise.  ``sample_forced`` rolls the generator along a
+caller's POS templates, several per video (include/xgate_pos_control.h), and ``sample_templates`` draws the templates from the
+generator's own distribution, several per video (include/xgate_pos_sample.h); control.py carries either result into the captioner.
 """
 from __future__ import annotations
 
@@ -365,6 +366,62 @@ class PosModel(nn.Module):
             return tag_logp, states, masks, pos_feats
         n = int(n_out.item())                       # the one host synchronisation of the call
         return tag_logp[:, :, :n], None if states is None else states[:, :, :n + 1], masks[:, :, :n + 1], pos_feats
+
+    def sample_templates(self, feats_rgb, feats_opfl, feat_mask, S, temperature=1.0, uniforms=None, generator=None,
+                         collect_states=False, trim=True):
+        """S sampled rollouts for each of the B videos (include/xgate_pos_sample.h): the rollout of `sample` with the greedy
+        choice replaced by an inverse-CDF draw over exp(logit / temperature), the captioner's rule.  Returns (templates (B,S,n)
+        int64, tag_logp (B,S,n), states (B,S,n+1,R) or None, masks (B,S,n+1), pos_feats (B*S,R)).
+
+        `templates` is zero from a row's first 0 onwards, so it is directly a valid input of `sample_forced`; tag_logp is the
+        UNTEMPERED log-probability of each drawn tag up to and including the end tag, 0 after it, and its row sum is the
+        template's score, as in the forced call.  `uniforms`: float32 (B,S,L), L = seq_length, one per draw (moved to the device);
+        None: ``torch.rand(B,S,L, device=..., generator=generator)``.  No random number generator lives in the library.
+        `trim`: cut to the reference's n (one host synchronisation); trim=False returns the full seq_length and does not
+        synchronise."""
+        from . import _native_pos_sample as nps
+        self._check_eval(feats_rgb, feats_opfl, feat_mask)
+        fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
+        B, K = fm.shape
+        L = self.seq_length
+        dev = fr.device
+        S = int(S)
+        temperature = float(temperature)
+        if S < 1:
+            raise ValueError("S >= 1 rollouts per video expected, got %d" % S)
+        if not (0.0 < temperature < float("inf")):
+            raise ValueError("temperature must be finite and > 0, got %r" % temperature)
+        if uniforms is None:
+            u = torch.rand(B, S, L, device=dev, generator=generator)
+        else:
+            u = torch.as_tensor(uniforms)
+            if u.dtype != torch.float32 or tuple(u.shape) != (B, S, L):
+                raise ValueError("uniforms: float32 (%d,%d,%d) expected, got %s %s" % (B, S, L, u.dtype, tuple(u.shape)))
+            u = u.to(dev).contiguous()
+        dims = self._dims(B, K, L + 1)
+        lib = nps.lib()
+        nbytes = lib.xgps_workspace_bytes(C.byref(dims), S)
+        if nbytes == 0:
+            raise nv.XgError("xgps_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S))
+        ws = self._cws
+        if ws is None or ws.device != dev or ws.numel() < nbytes:
+            ws = self._cws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        templates = torch.empty(B, S, L, dtype=torch.int64, device=dev)
+        tag_logp = torch.empty(B, S, L, device=dev)
+        states = torch.empty(B, S, L + 1, self.rnn_size, device=dev) if collect_states else None
+        masks = torch.empty(B, S, L + 1, device=dev)
+        pos_feats = torch.empty(B * S, self.rnn_size, device=dev)
+        n_out = torch.empty(1, dtype=torch.int32, device=dev)
+        P, bn = self._params(), self._bn()
+        nv.check(lib.xgps_sample_templates(_stream(), C.byref(dims), S, temperature, C.byref(P), C.byref(bn), fr.data_ptr(),
+                                           fo.data_ptr(), fm.data_ptr(), u.data_ptr(), templates.data_ptr(), tag_logp.data_ptr(),
+                                           None if states is None else states.data_ptr(), masks.data_ptr(), pos_feats.data_ptr(),
+                                           n_out.data_ptr(), ws.data_ptr(), ws.numel()), "xgps_sample_templates")
+        if not trim:
+            return templates, tag_logp, states, masks, pos_feats
+        n = int(n_out.item())                       # the one host synchronisation of the call
+        return (templates[:, :, :n], tag_logp[:, :, :n], None if states is None else states[:, :, :n + 1], masks[:, :, :n + 1],
+                pos_feats)
 
 
 class _PosTrainFunction(torch.autograd.Function):
