@@ -182,8 +182,60 @@ __device__ __forceinline__ void pos_choose(const CellHeadArgs& a, int b, int bes
     a.tok[b] = best;
 }
 
-// one workgroup per video: the two_inputs_lstmcell epilogue (pos_src/sub_modules.py:871-889: order i,f,o,g, the mask holds c and
-// h, dropout is the identity in eval mode), then logit + log_softmax (SAModel.py:79-80 / :178) and, for greedy, the choice
+// The straight-line pieces every cell-head kernel of this file shares (greedy / teacher-forced, train, rows).  The greedy, forced and
+// sampled calls are bit-identical where they meet (tested) BECAUSE these are one definition each: hipcc contracts to FMA, so a
+// regrouped expression here changes bits everywhere at once, never in one kernel alone.
+
+// (the reference would raise on an out-of-range category)
+__device__ __forceinline__ int64_t pos_clamp_tag(int64_t tk, int C) { return tk < 0 ? 0 : (tk >= C ? C - 1 : tk); }
+
+// unit j of the two_inputs_lstmcell epilogue (pos_src/sub_modules.py:871-889: order i,f,o,g, the mask holds c and h) from the row
+// s of the step's product, the hoisted token row tb and the state (cp, hp) before the step
+struct PosCell { float ig, fg, og, gg, cn, hn; };   // the activated gates and the new state, held where the mask is 0
+__device__ __forceinline__ PosCell pos_cell(const float* s, const float* tb, int R, int j, float cp, float hp, float m) {
+    PosCell o;
+    o.ig = xg_sigmoid(s[j] + tb[j]), o.fg = xg_sigmoid(s[R + j] + tb[R + j]);
+    o.og = xg_sigmoid(s[2 * R + j] + tb[2 * R + j]), o.gg = xg_tanh(s[3 * R + j] + tb[3 * R + j]);
+    o.cn = o.fg * cp + o.ig * o.gg;
+    o.cn = o.cn * m + cp * (1.0f - m);
+    o.hn = o.og * xg_tanh(o.cn);
+    o.hn = o.hn * m + hp * (1.0f - m);
+    return o;
+}
+
+// lg[0:C] = logit_w hs + logit_b, one wave per category at a time.  Called by the whole workgroup: the first barrier makes hs
+// (written by the cell loop) visible, the second lg.
+__device__ __forceinline__ void pos_head_logits(const float* logit_w, const float* logit_b, const float* hs, float* lg, int R, int C) {
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int cc = wave; cc < C; cc += STEP_WAVES) {
+        const float* wr = logit_w + (size_t)cc * R;
+        float acc = 0.f;
+#pragma unroll 8
+        for (int j = lane; j < R; j += 64) acc += wr[j] * hs[j];
+        acc = wave_sum(acc);
+        if (lane == 0) lg[cc] = acc + logit_b[cc];
+    }
+    __syncthreads();
+}
+
+// log-sum-exp of the logits and their maximum, C <= 64: one lane per category (v = the lane's logit, -inf where !in); whole wave
+__device__ __forceinline__ float pos_lse_lanes(float v, bool in, float& mx) {
+    mx = wave_max(v);
+    return mx + logf(wave_sum(in ? expf(v - mx) : 0.f));
+}
+
+// the same for any C by one thread, in index order
+__device__ __forceinline__ float pos_lse_serial(const float* lg, int C, float& mx) {
+    mx = lg[0];
+    for (int cc = 1; cc < C; ++cc) mx = fmaxf(mx, lg[cc]);
+    float se = 0.f;
+    for (int cc = 0; cc < C; ++cc) se += expf(lg[cc] - mx);
+    return mx + logf(se);
+}
+
+// one workgroup per video: the cell (dropout is the identity in eval mode), then logit + log_softmax (SAModel.py:79-80 / :178)
+// and, for greedy, the choice
 __global__ void __launch_bounds__(STEP_TPB) pos_cell_head_kernel(CellHeadArgs a) {
     extern __shared__ float lds[];
     float* hs = lds;             // R
@@ -200,42 +252,27 @@ __global__ void __launch_bounds__(STEP_TPB) pos_cell_head_kernel(CellHeadArgs a)
         tk = t == 0 ? 0 : a.tok[b];
         m = t == 0 ? 1.0f : a.masks[(size_t)b * T + t];
     }
-    tk = tk < 0 ? 0 : (tk >= C ? C - 1 : tk);                   // (the reference would raise on an out-of-range category)
+    tk = pos_clamp_tag(tk, C);
     const float* s = a.S + (size_t)b * 4 * R;
     const float* tb = a.tab + (size_t)tk * 4 * R;
     float* xh = a.X + (size_t)b * 2 * R + R;
     float* cb = a.c + (size_t)b * R;
     for (int j = tid; j < R; j += STEP_TPB) {
-        const float ig = xg_sigmoid(s[j] + tb[j]), fg = xg_sigmoid(s[R + j] + tb[R + j]);
-        const float og = xg_sigmoid(s[2 * R + j] + tb[2 * R + j]), gg = xg_tanh(s[3 * R + j] + tb[3 * R + j]);
-        const float cp = cb[j], hp = xh[j];
-        float cn = fg * cp + ig * gg;
-        cn = cn * m + cp * (1.0f - m);
-        float hn = og * xg_tanh(cn);
-        hn = hn * m + hp * (1.0f - m);
-        cb[j] = cn;
-        xh[j] = hn;
-        hs[j] = hn;
-        if (!tf) a.states[((size_t)b * T + t) * R + j] = hn;
+        const PosCell o = pos_cell(s, tb, R, j, cb[j], xh[j], m);
+        cb[j] = o.cn;
+        xh[j] = o.hn;
+        hs[j] = o.hn;
+        if (!tf) a.states[((size_t)b * T + t) * R + j] = o.hn;
     }
     if (!tf && t == 0 && tid == 0) a.masks[(size_t)b * T] = 1.0f;
-    __syncthreads();
+    pos_head_logits(a.logit_w, a.logit_b, hs, lg, R, C);
     const int lane = tid & 63, wave = tid >> 6;
-    for (int cc = wave; cc < C; cc += STEP_WAVES) {
-        const float* wr = a.logit_w + (size_t)cc * R;
-        float acc = 0.f;
-#pragma unroll 8
-        for (int j = lane; j < R; j += 64) acc += wr[j] * hs[j];
-        acc = wave_sum(acc);
-        if (lane == 0) lg[cc] = acc + a.logit_b[cc];
-    }
-    __syncthreads();
     const bool choose = !tf && t + 1 < T;
+    float mx;
     if (C <= 64) {                                              // one lane per category
         if (wave == 0) {
             const float v = lane < C ? lg[lane] : -INFINITY;
-            const float mx = wave_max(v);
-            const float lse = mx + logf(wave_sum(lane < C ? expf(v - mx) : 0.f));
+            const float lse = pos_lse_lanes(v, lane < C, mx);
             if (lane == 0) s_lse = lse;
             if (choose) {
                 const float lp = lane < C ? v - lse : -INFINITY;
@@ -245,11 +282,7 @@ __global__ void __launch_bounds__(STEP_TPB) pos_cell_head_kernel(CellHeadArgs a)
             }
         }
     } else if (tid == 0) {
-        float mx = lg[0];
-        for (int cc = 1; cc < C; ++cc) mx = fmaxf(mx, lg[cc]);
-        float se = 0.f;
-        for (int cc = 0; cc < C; ++cc) se += expf(lg[cc] - mx);
-        const float lse = mx + logf(se);
+        const float lse = pos_lse_serial(lg, C, mx);
         s_lse = lse;
         if (choose) {
             int best = 0;
@@ -463,49 +496,68 @@ int encoder(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnStat
     return product(st, BK, R, w.Hcat, 2 * R, p->fusion_w, 2 * R, nullptr, 0, nullptr, 0, p->fusion_b, V, R, true);
 }
 
-// encoder, init_hidden (SAModel.py:54-60: the sum of V over all K rows over the mask count) into X[:, R:2R] and c, and the per-call
-// hoisted operands: v2a(V), the token table and the packed step weights
-int prologue(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
-             const float* fm, const Ws& w) {
+// the per-call hoisted operands of the decoder step, eval and train alike: Q = v2a(V), the token table tab = embed i2h^T with the
+// three biases folded in, and the step's weights packed for the fast skinny kernel
+int hoist_operands(hipStream_t st, const XgpDims* d, const XgpParams* p, const float* V, float* Q, float* tab, float* pk_h2a,
+                   float* pk_a2h, float* pk_h2h) {
     const int B = d->B, K = d->K, R = d->R, A = d->A, E = d->E, C = d->C;
-    XG_TRY(encoder(st, d, p, bn, fr, fo, fm, w.V, w));
-    XG_TRY(xgk_masked_mean(st, w.V, fm, w.vbar, B, K, R));
-    XG_TRY(product(st, B, R, w.vbar, R, p->ih1_w, R, nullptr, 0, nullptr, 0, p->ih1_b, w.X + R, 2 * R));
-    XG_TRY(product(st, B, R, w.vbar, R, p->ic1_w, R, nullptr, 0, nullptr, 0, p->ic1_b, w.c, R));
-    XG_TRY(product(st, B * K, A, w.V, R, p->v2a_w, R, nullptr, 0, nullptr, 0, p->v2a_b, w.Q, A));
-    XG_TRY(product(st, C, 4 * R, p->embed_w, E, p->i2h_w, E, nullptr, 0, nullptr, 0, p->i2h_b, w.tab, 4 * R));
-    hipLaunchKernelGGL(pos_pack_kernel, dim3(xg_cdiv(A, 32) * xg_cdiv(R, 32)), dim3(POS_TPB), 0, st, p->h2a_w, A, R, w.pk_h2a);
-    hipLaunchKernelGGL(pos_pack_kernel, dim3(xg_cdiv(4 * R, 32) * xg_cdiv(R, 32)), dim3(POS_TPB), 0, st, p->a2h_w, 4 * R, R, w.pk_a2h);
-    hipLaunchKernelGGL(pos_pack_kernel, dim3(xg_cdiv(4 * R, 32) * xg_cdiv(R, 32)), dim3(POS_TPB), 0, st, p->h2h_w, 4 * R, R, w.pk_h2h);
+    XG_TRY(product(st, B * K, A, V, R, p->v2a_w, R, nullptr, 0, nullptr, 0, p->v2a_b, Q, A));
+    XG_TRY(product(st, C, 4 * R, p->embed_w, E, p->i2h_w, E, nullptr, 0, nullptr, 0, p->i2h_b, tab, 4 * R));
+    hipLaunchKernelGGL(pos_pack_kernel, dim3(xg_cdiv(A, 32) * xg_cdiv(R, 32)), dim3(POS_TPB), 0, st, p->h2a_w, A, R, pk_h2a);
+    hipLaunchKernelGGL(pos_pack_kernel, dim3(xg_cdiv(4 * R, 32) * xg_cdiv(R, 32)), dim3(POS_TPB), 0, st, p->a2h_w, 4 * R, R, pk_a2h);
+    hipLaunchKernelGGL(pos_pack_kernel, dim3(xg_cdiv(4 * R, 32) * xg_cdiv(R, 32)), dim3(POS_TPB), 0, st, p->h2h_w, 4 * R, R, pk_h2h);
     XG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pos_fold_bias_kernel, dim3(xg_cdiv(C * 4 * R, POS_TPB)), dim3(POS_TPB), 0, st, w.tab, p->a2h_b, p->h2h_b, C,
-                       4 * R);
+    hipLaunchKernelGGL(pos_fold_bias_kernel, dim3(xg_cdiv(C * 4 * R, POS_TPB)), dim3(POS_TPB), 0, st, tab, p->a2h_b, p->h2h_b, C, 4 * R);
     XG_CHECK_LAUNCH();
     return XG_OK;
 }
 
-// the prologue, then the T decoder steps
+// encoder, init_hidden (SAModel.py:54-60: the sum of V over all K rows over the mask count) into X[:, R:2R] and c, and the hoisted
+// operands
+int prologue(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
+             const float* fm, const Ws& w) {
+    const int B = d->B, K = d->K, R = d->R;
+    XG_TRY(encoder(st, d, p, bn, fr, fo, fm, w.V, w));
+    XG_TRY(xgk_masked_mean(st, w.V, fm, w.vbar, B, K, R));
+    XG_TRY(product(st, B, R, w.vbar, R, p->ih1_w, R, nullptr, 0, nullptr, 0, p->ih1_b, w.X + R, 2 * R));
+    XG_TRY(product(st, B, R, w.vbar, R, p->ic1_w, R, nullptr, 0, nullptr, 0, p->ic1_b, w.c, R));
+    return hoist_operands(st, d, p, w.V, w.Q, w.tab, w.pk_h2a, w.pk_a2h, w.pk_h2h);
+}
+
+// the context parts of pos_attn_kernel / pos_attn_group_kernel: as many as fill the workgroup, at most one per frame
+int attn_nsplit(int K, int R) {
+    const int nsplit = STEP_TPB / R;
+    return nsplit < 1 ? 1 : (nsplit > K ? K : nsplit);
+}
+
+// pos_attn_kernel over B rows, each with its own video
+void launch_attn(hipStream_t st, int B, const float* P, const float* Q, const float* V, const float* w, float* X, int K, int R, int A) {
+    const int nsplit = attn_nsplit(K, R);
+    const size_t lds = (size_t)(2 * A + K + nsplit * R) * sizeof(float);
+    if (A % 4 == 0) hipLaunchKernelGGL(pos_attn_kernel<true>, dim3(B), dim3(STEP_TPB), lds, st, P, Q, V, w, X, K, R, A, nsplit);
+    else            hipLaunchKernelGGL(pos_attn_kernel<false>, dim3(B), dim3(STEP_TPB), lds, st, P, Q, V, w, X, K, R, A, nsplit);
+}
+
+// the prologue, the T decoder steps, then the early exit into `out`.  ca.cap set is the teacher-forced call (T' from the categories,
+// sub 0), null the greedy one (n from ca.masks, sub 1): the same test pos_cell_head_kernel makes (`tf`)
 int decode(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo, const float* fm,
-           CellHeadArgs ca, const Ws& w) {
+           CellHeadArgs ca, int32_t* out, const Ws& w) {
     const int B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, T = d->T;
     XG_TRY(prologue(st, d, p, bn, fr, fo, fm, w));
     ca.S = w.S; ca.tab = w.tab; ca.logit_w = p->logit_w; ca.logit_b = p->logit_b;
     ca.X = w.X; ca.c = w.c; ca.B = B; ca.R = R; ca.C = C; ca.T = T;
-    int nsplit = STEP_TPB / R;
-    nsplit = nsplit < 1 ? 1 : (nsplit > K ? K : nsplit);
-    const size_t lds_attn = (size_t)(2 * A + K + nsplit * R) * sizeof(float), lds_cell = (size_t)(R + C) * sizeof(float);
-    const bool v4 = A % 4 == 0;
     for (int t = 0; t < T; ++t) {
         XG_TRY(product(st, B, A, w.X + R, 2 * R, p->h2a_w, R, nullptr, 0, nullptr, 0, p->h2a_b, w.P, A, false, w.pk_h2a));
-        if (v4) hipLaunchKernelGGL(pos_attn_kernel<true>, dim3(B), dim3(STEP_TPB), lds_attn, st, w.P, w.Q, w.V, p->a2w_w, w.X, K, R, A, nsplit);
-        else    hipLaunchKernelGGL(pos_attn_kernel<false>, dim3(B), dim3(STEP_TPB), lds_attn, st, w.P, w.Q, w.V, p->a2w_w, w.X, K, R, A, nsplit);
+        launch_attn(st, B, w.P, w.Q, w.V, p->a2w_w, w.X, K, R, A);
         XG_CHECK_LAUNCH();
         XG_TRY(product(st, B, 4 * R, w.X, 2 * R, p->a2h_w, R, w.X + R, 2 * R, p->h2h_w, R, nullptr, w.S, 4 * R, false, w.pk_a2h,
                        w.pk_h2h));
         ca.t = t;
-        hipLaunchKernelGGL(pos_cell_head_kernel, dim3(B), dim3(STEP_TPB), lds_cell, st, ca);
+        hipLaunchKernelGGL(pos_cell_head_kernel, dim3(B), dim3(STEP_TPB), (size_t)(R + C) * sizeof(float), st, ca);
         XG_CHECK_LAUNCH();
     }
+    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, ca.cap, ca.masks, B, T, ca.cap ? 0 : 1, out);
+    XG_CHECK_LAUNCH();
     return XG_OK;
 }
 
@@ -545,13 +597,9 @@ extern "C" int xgp_forward_tf(void* stream, const XgpDims* d, const XgpParams* p
                               float* logp, int32_t* t_out, void* ws, size_t ws_bytes) {
     XG_TRY(common_checks(d, p, bn, feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, true));
     if (!cap_classes || !new_mask || !logp || !t_out) return XG_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
     CellHeadArgs ca{};
     ca.cap = cap_classes; ca.new_mask = new_mask; ca.logp = logp;
-    XG_TRY(decode(st, d, p, bn, feats_rgb, feats_opfl, feat_mask, ca, ws_layout(d, ws)));
-    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, cap_classes, nullptr, d->B, d->T, 0, t_out);
-    XG_CHECK_LAUNCH();
-    return XG_OK;
+    return decode((hipStream_t)stream, d, p, bn, feats_rgb, feats_opfl, feat_mask, ca, t_out, ws_layout(d, ws));
 }
 
 extern "C" int xgp_sample_greedy(void* stream, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* feats_rgb,
@@ -559,14 +607,10 @@ extern "C" int xgp_sample_greedy(void* stream, const XgpDims* d, const XgpParams
                                  float* masks, int32_t* n_out, void* ws, size_t ws_bytes) {
     XG_TRY(common_checks(d, p, bn, feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, true));
     if (d->T < 2 || !seq || !seq_logp || !states || !masks || !n_out) return XG_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
     const Ws w = ws_layout(d, ws);
     CellHeadArgs ca{};
     ca.tok = w.tok; ca.masks = masks; ca.seq = seq; ca.seq_logp = seq_logp; ca.states = states;
-    XG_TRY(decode(st, d, p, bn, feats_rgb, feats_opfl, feat_mask, ca, w));
-    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, nullptr, masks, d->B, d->T, 1, n_out);
-    XG_CHECK_LAUNCH();
-    return XG_OK;
+    return decode((hipStream_t)stream, d, p, bn, feats_rgb, feats_opfl, feat_mask, ca, n_out, w);
 }
 
 // ==================================================================================================================================
@@ -644,36 +688,22 @@ __global__ void __launch_bounds__(STEP_TPB) pos_cell_head_train_kernel(CellTrain
     float* lg = lds + a.R;       // C
     __shared__ float s_lse;
     const int b = blockIdx.x, tid = threadIdx.x, R = a.R, C = a.C, T = a.T, t = a.t;
-    int64_t tk = a.cap[(size_t)b * T + t];
+    const int64_t tk = pos_clamp_tag(a.cap[(size_t)b * T + t], C);
     const float m = a.new_mask[(size_t)b * T + t];
-    tk = tk < 0 ? 0 : (tk >= C ? C - 1 : tk);
     const float* s = a.S + (size_t)b * 4 * R;
     const float* tb = a.tab + (size_t)tk * 4 * R;
     float* gb = a.gates + (size_t)b * 4 * R;
     for (int j = tid; j < R; j += STEP_TPB) {
-        const float ig = xg_sigmoid(s[j] + tb[j]), fg = xg_sigmoid(s[R + j] + tb[R + j]);
-        const float og = xg_sigmoid(s[2 * R + j] + tb[2 * R + j]), gg = xg_tanh(s[3 * R + j] + tb[3 * R + j]);
-        const float cp = a.c_prev[(size_t)b * R + j], hp = a.h_prev[(size_t)b * R + j];
-        float cn = fg * cp + ig * gg;
-        cn = cn * m + cp * (1.0f - m);
-        float hn = og * xg_tanh(cn);
-        hn = (hn * m + hp * (1.0f - m)) * xg_keep(a.drop, (uint32_t)(b * R + j));
-        gb[j] = ig; gb[R + j] = fg; gb[2 * R + j] = og; gb[3 * R + j] = gg;
-        a.c_out[(size_t)b * R + j] = cn;
+        const PosCell o = pos_cell(s, tb, R, j, a.c_prev[(size_t)b * R + j], a.h_prev[(size_t)b * R + j], m);
+        const float hn = o.hn * xg_keep(a.drop, (uint32_t)(b * R + j));
+        gb[j] = o.ig; gb[R + j] = o.fg; gb[2 * R + j] = o.og; gb[3 * R + j] = o.gg;
+        a.c_out[(size_t)b * R + j] = o.cn;
         a.h_out[(size_t)b * R + j] = hn;
         hs[j] = hn;
     }
-    __syncthreads();
+    pos_head_logits(a.logit_w, a.logit_b, hs, lg, R, C);
     const int lane = tid & 63, wave = tid >> 6;
-    for (int cc = wave; cc < C; cc += STEP_WAVES) {
-        const float* wr = a.logit_w + (size_t)cc * R;
-        float acc = 0.f;
-#pragma unroll 8
-        for (int j = lane; j < R; j += 64) acc += wr[j] * hs[j];
-        acc = wave_sum(acc);
-        if (lane == 0) lg[cc] = acc + a.logit_b[cc];
-    }
-    __syncthreads();
+    // (chunks of 64 rather than pos_lse_lanes / pos_lse_serial: for C > 64 the wave sums in another order than the serial form)
     if (wave == 0) {
         float mx = -INFINITY;
         for (int c0 = 0; c0 < C; c0 += 64) mx = fmaxf(mx, wave_max(c0 + lane < C ? lg[c0 + lane] : -INFINITY));
@@ -834,10 +864,8 @@ int dgrad(hipStream_t st, int M, int N, int K, const float* dY, int lddy, const 
     return xgk_gemm(st, 0, false, false, M, N, K, dY, lddy, W, N, dX, lddx, nullptr, false, acc);
 }
 
-void pack(hipStream_t st, const float* W, int N, int K, float* dst, bool transposed) {
-    const dim3 grid(xg_cdiv(N, 32) * xg_cdiv(K, 32));
-    if (transposed) hipLaunchKernelGGL(pos_pack_t_kernel, grid, dim3(POS_TPB), 0, st, W, N, K, dst);
-    else hipLaunchKernelGGL(pos_pack_kernel, grid, dim3(POS_TPB), 0, st, W, N, K, dst);
+void pack_t(hipStream_t st, const float* W, int N, int K, float* dst) {
+    hipLaunchKernelGGL(pos_pack_t_kernel, dim3(xg_cdiv(N, 32) * xg_cdiv(K, 32)), dim3(POS_TPB), 0, st, W, N, K, dst);
 }
 
 int encoder_train(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const XgptRun* run, const float* fr,
@@ -904,7 +932,7 @@ int encoder_train(hipStream_t st, const XgpDims* d, const XgpParams* p, const Xg
 
 int forward_train(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const XgptRun* run, const float* fr,
                   const float* fo, const float* fm, const int64_t* cap, const float* nm, float* logp, const TWs& w) {
-    const int B = d->B, K = d->K, R = d->R, A = d->A, E = d->E, C = d->C, T = d->T;
+    const int B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, T = d->T;
     const size_t BR = (size_t)B * R;
     if (hipMemcpyAsync(w.cap, cap, sizeof(int64_t) * B * T, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
     if (hipMemcpyAsync(w.nm, nm, sizeof(float) * B * T, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
@@ -912,15 +940,7 @@ int forward_train(hipStream_t st, const XgpDims* d, const XgpParams* p, const Xg
     XG_TRY(xgk_masked_mean(st, w.V, fm, w.vbar, B, K, R));                 // (detached: SAModel.py:54-60)
     XG_TRY(product(st, B, R, w.vbar, R, p->ih1_w, R, nullptr, 0, nullptr, 0, p->ih1_b, w.Hst, R));
     XG_TRY(product(st, B, R, w.vbar, R, p->ic1_w, R, nullptr, 0, nullptr, 0, p->ic1_b, w.Cst, R));
-    XG_TRY(product(st, B * K, A, w.V, R, p->v2a_w, R, nullptr, 0, nullptr, 0, p->v2a_b, w.Q, A));
-    XG_TRY(product(st, C, 4 * R, p->embed_w, E, p->i2h_w, E, nullptr, 0, nullptr, 0, p->i2h_b, w.tab, 4 * R));
-    pack(st, p->h2a_w, A, R, w.pk_h2a, false);
-    pack(st, p->a2h_w, 4 * R, R, w.pk_a2h, false);
-    pack(st, p->h2h_w, 4 * R, R, w.pk_h2h, false);
-    XG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pos_fold_bias_kernel, dim3(xg_cdiv(C * 4 * R, POS_TPB)), dim3(POS_TPB), 0, st, w.tab, p->a2h_b, p->h2h_b, C,
-                       4 * R);
-    XG_CHECK_LAUNCH();
+    XG_TRY(hoist_operands(st, d, p, w.V, w.Q, w.tab, w.pk_h2a, w.pk_a2h, w.pk_h2h));
     CellTrainArgs ca{};
     ca.S = w.S; ca.tab = w.tab; ca.logit_w = p->logit_w; ca.logit_b = p->logit_b;
     ca.cap = w.cap; ca.new_mask = w.nm; ca.logp = logp;
@@ -1018,9 +1038,9 @@ int backward(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgpPara
              const float* fo, const float* fm, int Tp, const float* dlogp, const TWs& w) {
     const int B = d->B, K = d->K, R = d->R, A = d->A, E = d->E, C = d->C, T = d->T, BK = B * K, TB = Tp * B;
     const size_t BR = (size_t)B * R;
-    pack(st, p->a2h_w, R, 4 * R, w.pkt_a2h, true);
-    pack(st, p->h2h_w, R, 4 * R, w.pkt_h2h, true);
-    pack(st, p->h2a_w, R, A, w.pkt_h2a, true);
+    pack_t(st, p->a2h_w, R, 4 * R, w.pkt_a2h);
+    pack_t(st, p->h2h_w, R, 4 * R, w.pkt_h2h);
+    pack_t(st, p->h2a_w, R, A, w.pkt_h2a);
     XG_CHECK_LAUNCH();
     XG_TRY(xgk_fill(st, w.dH[0], 0.f, (int64_t)BR));
     XG_TRY(xgk_fill(st, w.dC, 0.f, (int64_t)BR));
@@ -1119,7 +1139,7 @@ extern "C" int xgpt_backward(void* stream, const XgpDims* d, const XgpParams* p,
 //                  softmax is reduced by one wave (lane-strided partials, then the wave reduction) where pos_attn_kernel sums
 //                  serially over k, so the two kernels may differ in the last bits.  Every row has one fixed order whatever group
 //                  it falls in; S = 1 runs pos_attn_kernel itself, which is what makes that case bit-identical to the greedy call.
-//   cell + head    pos_cell_head_forced_kernel: the tag and the `unfinished` mask of the step from the template, the cell, then
+//   cell + head    pos_cell_head_rows_kernel<false>: the tag and the `unfinished` mask of the step from the template, the cell, then
 //                  the log-sum-exp of the head and ONE gathered log-probability (the next tag's); no argmax.
 // ==================================================================================================================================
 #include "../../include/xgate_pos_control.h"
@@ -1277,33 +1297,54 @@ __global__ void __launch_bounds__(STEP_TPB) pos_attn_group_kernel(const float* _
     }
 }
 
-struct ForcedArgs {
+struct RowsArgs {
     const float* S;              // (M,4R) af a2h^T + h h2h^T, no bias
     const float* tab;            // (C,4R) embed i2h^T + the three biases
     const float *logit_w, *logit_b;
     float* X;                    // (M,2R): h read from and h' written to columns R..2R
     float* c;                    // (M,R) cell state, in place
-    const int64_t* tmpl;         // (M,T-1) the tags
+    const int64_t* tmpl;         // (M,T-1) the tags: column t - 1 is read by step t
     float *tag_logp, *states, *masks, *pos_feats;   // (M,T-1), (M,T,R) or null, (M,T), (M,R)
+    // DRAW only: tmpl_out is tmpl, writable (step t writes column t); one uniform per row and step
+    int64_t* tmpl_out;
+    const float* uniforms;       // (M,T-1)
+    float temperature;
     int R, C, T, t;
 };
 
+// inclusive scan over the 64 lanes: row_shr 1, 2, 4, 8 inside each row of 16 (zeros shift in), then the totals of the rows before
+// the lane's own, added in row order.  Every lane must be active.
+__device__ __forceinline__ float wave_scan(float v) {
+    v += xg_dpp<0x111>(v);
+    v += xg_dpp<0x112>(v);
+    v += xg_dpp<0x114>(v);
+    v += xg_dpp<0x118>(v);
+    const float r0 = xg_readlane(v, 15), r1 = xg_readlane(v, 31), r2 = xg_readlane(v, 47);
+    const int row = (threadIdx.x & 63) >> 4;
+    const float before = row == 0 ? 0.f : (row == 1 ? r0 : (row == 2 ? r0 + r1 : (r0 + r1) + r2));
+    return before + v;
+}
+
 // one workgroup per row, step t: the tag fed is tmpl[t-1] (BOS at t = 0) under the mask unfinished_t = unfinished_{t-1} (tag > 0)
-// (unfinished_{t-1} is masks[t-1], written by the step before); pos_cell_head_kernel's cell; then, for t < T - 1, the head's
-// log-sum-exp and the log-probability of the NEXT tag, tmpl[t], which counts while the row is unfinished at step t: up to and
-// including its first 0
-__global__ void __launch_bounds__(STEP_TPB) pos_cell_head_forced_kernel(ForcedArgs a) {
+// (unfinished_{t-1} is masks[t-1], written by the step before); the cell; then, for t < T - 1, the head's log-sum-exp and the
+// log-probability of the NEXT tag, which counts while the row is unfinished at step t: up to and including its first 0.
+//   !DRAW  the next tag is the caller's tmpl[t].
+//   DRAW   it is drawn here and written to tmpl_out[t], where the launch of step t + 1 reads it: the first category whose running
+//          sum of w_c = exp((x_c - max x) / temperature) exceeds uniforms[t] * sum(w), C - 1 when none does (the captioner's draw,
+//          xg_select.h).  tmpl_out[t] = tag * unfinished; tag_logp[t] is the UNtempered log-probability of the tag.
+template <bool DRAW>
+__global__ void __launch_bounds__(STEP_TPB) pos_cell_head_rows_kernel(RowsArgs a) {
     extern __shared__ float lds[];
     float* hs = lds;             // R
     float* lg = lds + a.R;       // C
+    float* wt = lg + a.C;        // C, DRAW only (the serial head's weights)
     const int tid = threadIdx.x, R = a.R, C = a.C, T = a.T, t = a.t;
     const size_t row = blockIdx.x;
     const int64_t* tr = a.tmpl + row * (T - 1);
     int64_t tk = 0;
     float m = 1.0f;
     if (t > 0) {
-        tk = tr[t - 1];
-        tk = tk < 0 ? 0 : (tk >= C ? C - 1 : tk);
+        tk = pos_clamp_tag(tr[t - 1], C);
         m = tk > 0 ? a.masks[row * T + t - 1] : 0.0f;
     }
     const float* s = a.S + row * 4 * R;
@@ -1313,48 +1354,50 @@ __global__ void __launch_bounds__(STEP_TPB) pos_cell_head_forced_kernel(ForcedAr
     float* st = a.states ? a.states + (row * T + t) * R : nullptr;
     float* pf = t == T - 1 ? a.pos_feats + row * R : nullptr;
     for (int j = tid; j < R; j += STEP_TPB) {
-        const float ig = xg_sigmoid(s[j] + tb[j]), fg = xg_sigmoid(s[R + j] + tb[R + j]);
-        const float og = xg_sigmoid(s[2 * R + j] + tb[2 * R + j]), gg = xg_tanh(s[3 * R + j] + tb[3 * R + j]);
-        const float cp = cb[j], hp = xh[j];
-        float cn = fg * cp + ig * gg;
-        cn = cn * m + cp * (1.0f - m);
-        float hn = og * xg_tanh(cn);
-        hn = hn * m + hp * (1.0f - m);
-        cb[j] = cn;
-        xh[j] = hn;
-        hs[j] = hn;
-        if (st) st[j] = hn;
-        if (pf) pf[j] = hn;
+        const PosCell o = pos_cell(s, tb, R, j, cb[j], xh[j], m);
+        cb[j] = o.cn;
+        xh[j] = o.hn;
+        hs[j] = o.hn;
+        if (st) st[j] = o.hn;
+        if (pf) pf[j] = o.hn;
     }
     if (tid == 0) a.masks[row * T + t] = m;
     if (t + 1 >= T) return;                                     // (no tag follows the last step)
-    __syncthreads();
+    const float u = DRAW ? a.uniforms[row * (T - 1) + t] : 0.f;   // (requested here: the head's products hide the round trip)
+    pos_head_logits(a.logit_w, a.logit_b, hs, lg, R, C);
     const int lane = tid & 63, wave = tid >> 6;
-    for (int cc = wave; cc < C; cc += STEP_WAVES) {
-        const float* wr = a.logit_w + (size_t)cc * R;
-        float acc = 0.f;
-#pragma unroll 8
-        for (int j = lane; j < R; j += 64) acc += wr[j] * hs[j];
-        acc = wave_sum(acc);
-        if (lane == 0) lg[cc] = acc + a.logit_b[cc];
-    }
-    __syncthreads();
-    int64_t nx = tr[t];
-    nx = nx < 0 ? 0 : (nx >= C ? C - 1 : nx);
-    float* out = a.tag_logp + row * (T - 1) + t;
+    int nx = DRAW ? C - 1 : (int)pos_clamp_tag(tr[t], C);   // DRAW: stays when nothing passes the target (rounding, u = 1)
+    float mx, lse = 0.f;
     if (C <= 64) {                                              // one lane per category
         if (wave == 0) {
             const float v = lane < C ? lg[lane] : -INFINITY;
-            const float mx = wave_max(v);
-            const float lse = mx + logf(wave_sum(lane < C ? expf(v - mx) : 0.f));
-            if (lane == 0) *out = m != 0.0f ? lg[nx] - lse : 0.0f;
+            lse = pos_lse_lanes(v, lane < C, mx);
+            if (DRAW) {
+                const float inc = wave_scan(lane < C ? expf((v - mx) / a.temperature) : 0.f);
+                const float target = u * xg_readlane(inc, C - 1);     // (the total in the last category's own summation order)
+                const unsigned long long pass = __ballot(lane < C && inc > target);
+                if (pass) nx = __ffsll(pass) - 1;
+            }
         }
     } else if (tid == 0) {
-        float mx = lg[0];
-        for (int cc = 1; cc < C; ++cc) mx = fmaxf(mx, lg[cc]);
-        float se = 0.f;
-        for (int cc = 0; cc < C; ++cc) se += expf(lg[cc] - mx);
-        *out = m != 0.0f ? lg[nx] - (mx + logf(se)) : 0.0f;
+        lse = pos_lse_serial(lg, C, mx);
+        if (DRAW) {
+            float tot = 0.f;
+            for (int cc = 0; cc < C; ++cc) {
+                wt[cc] = expf((lg[cc] - mx) / a.temperature);
+                tot += wt[cc];
+            }
+            const float target = u * tot;
+            float run = 0.f;
+            for (int cc = 0; cc < C; ++cc) {
+                run += wt[cc];
+                if (run > target) { nx = cc; break; }
+            }
+        }
+    }
+    if (tid == 0) {                                             // (the thread that holds lse and nx in both forms)
+        a.tag_logp[row * (T - 1) + t] = m != 0.0f ? lg[nx] - lse : 0.0f;
+        if (DRAW) a.tmpl_out[row * (T - 1) + t] = m != 0.0f ? nx : 0;
     }
 }
 
@@ -1381,7 +1424,7 @@ CWs cws_layout(const XgpDims* d, int S, void* base) {
 }
 
 // LDS floats of pos_attn_group_kernel<G>: the p-vectors / context parts, w, the scores
-// (restated as group_lds in tests/test_gpu_pos_control.py, with the 64 KiB limit of sample_forced below, to name the cases that take
+// (restated as group_lds in tests/test_gpu_pos_control.py, with the 64 KiB limit of rollout_rows below, to name the cases that take
 // the one-template form: change them together)
 size_t attn_group_lds(int G, int K, int R, int A, int nsplit, int* pr_floats) {
     const size_t pr = ((size_t)G * (A > nsplit * R ? A : nsplit * R) + 3) / 4 * 4;
@@ -1404,11 +1447,10 @@ void launch_attn_group(hipStream_t st, int B, int S, bool v4, size_t lds, const 
     else    hipLaunchKernelGGL((pos_attn_group_kernel<G, false>), grid, dim3(STEP_TPB), lds, st, P, Q, V, w, X, K, R, A, S, nsplit, pr_floats);
 }
 
-// the rollout over the M = B S rows; `cell` is the step's fourth launch (the forced kernel, or the sampled one of
-// xgate_pos_sample.h below: the same operands under the same field names) with lds_cell bytes of LDS
-template <class CellArgs>
+// the rollout over the M = B S rows (fa: the caller's operands; the workspace's and the step are filled in here), then n_out from
+// the masks.  `draw` picks pos_cell_head_rows_kernel<true>, which needs C more floats of LDS for the weights of its serial head.
 int rollout_rows(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
-                 const float* fm, CellArgs fa, void (*cell)(CellArgs), size_t lds_cell, const CWs& w) {
+                 const float* fm, RowsArgs fa, bool draw, int32_t* n_out, const CWs& w) {
     const int B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, T = d->T, M = B * S;
     XG_TRY(prologue(st, d, p, bn, fr, fo, fm, w.v));
     const int64_t n = (int64_t)M * R;
@@ -1416,9 +1458,8 @@ int rollout_rows(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, co
     XG_CHECK_LAUNCH();
     fa.S = w.S; fa.tab = w.v.tab; fa.logit_w = p->logit_w; fa.logit_b = p->logit_b;
     fa.X = w.X; fa.c = w.c; fa.R = R; fa.C = C; fa.T = T;
-    int nsplit = STEP_TPB / R;
-    nsplit = nsplit < 1 ? 1 : (nsplit > K ? K : nsplit);
-    const size_t lds_attn1 = (size_t)(2 * A + K + nsplit * R) * sizeof(float);
+    const size_t lds_cell = (size_t)(R + (draw ? 2 : 1) * C) * sizeof(float);
+    const int nsplit = attn_nsplit(K, R);
     // the full group while its p-vectors fit the 64 KiB of LDS a workgroup gets without opting in; beyond that (A or R near
     // 4096) one template per workgroup
     int pr_floats = 0;
@@ -1428,27 +1469,20 @@ int rollout_rows(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, co
     const bool v4 = A % 4 == 0;
     for (int t = 0; t < T; ++t) {
         XG_TRY(product(st, M, A, w.X + R, 2 * R, p->h2a_w, R, nullptr, 0, nullptr, 0, p->h2a_b, w.P, A, false, w.v.pk_h2a));
-        if (S == 1) {
-            if (v4) hipLaunchKernelGGL(pos_attn_kernel<true>, dim3(B), dim3(STEP_TPB), lds_attn1, st, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit);
-            else    hipLaunchKernelGGL(pos_attn_kernel<false>, dim3(B), dim3(STEP_TPB), lds_attn1, st, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit);
-        } else if (full) {
-            launch_attn_group<CTRL_G>(st, B, S, v4, lds_group, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit, pr_floats);
-        } else {
-            launch_attn_group<1>(st, B, S, v4, lds_group, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit, pr_floats);
-        }
+        if (S == 1) launch_attn(st, B, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A);
+        else if (full) launch_attn_group<CTRL_G>(st, B, S, v4, lds_group, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit, pr_floats);
+        else launch_attn_group<1>(st, B, S, v4, lds_group, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit, pr_floats);
         XG_CHECK_LAUNCH();
         XG_TRY(product(st, M, 4 * R, w.X, 2 * R, p->a2h_w, R, w.X + R, 2 * R, p->h2h_w, R, nullptr, w.S, 4 * R, false, w.v.pk_a2h,
                        w.v.pk_h2h));
         fa.t = t;
-        hipLaunchKernelGGL(cell, dim3(M), dim3(STEP_TPB), lds_cell, st, fa);
+        if (draw) hipLaunchKernelGGL(pos_cell_head_rows_kernel<true>, dim3(M), dim3(STEP_TPB), lds_cell, st, fa);
+        else      hipLaunchKernelGGL(pos_cell_head_rows_kernel<false>, dim3(M), dim3(STEP_TPB), lds_cell, st, fa);
         XG_CHECK_LAUNCH();
     }
+    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, nullptr, fa.masks, M, T, 1, n_out);
+    XG_CHECK_LAUNCH();
     return XG_OK;
-}
-
-int sample_forced(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
-                  const float* fm, ForcedArgs fa, const CWs& w) {
-    return rollout_rows(st, d, S, p, bn, fr, fo, fm, fa, pos_cell_head_forced_kernel, (size_t)(d->R + d->C) * sizeof(float), w);
 }
 
 }  // namespace
@@ -1468,151 +1502,21 @@ extern "C" int xgpc_sample_forced(void* stream, const XgpDims* d, int32_t S, con
         !masks || !pos_feats || !n_out || !ws)
         return XG_EINVAL;
     if (ws_bytes < cws_layout(d, S, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    ForcedArgs fa{};
+    RowsArgs fa{};
     fa.tmpl = templates; fa.tag_logp = tag_logp; fa.states = states; fa.masks = masks; fa.pos_feats = pos_feats;
-    XG_TRY(sample_forced(st, d, S, p, bn, feats_rgb, feats_opfl, feat_mask, fa, cws_layout(d, S, ws)));
-    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, nullptr, masks, d->B * S, d->T, 1, n_out);
-    XG_CHECK_LAUNCH();
-    return XG_OK;
+    return rollout_rows((hipStream_t)stream, d, S, p, bn, feats_rgb, feats_opfl, feat_mask, fa, false, n_out, cws_layout(d, S, ws));
 }
 
 // ==================================================================================================================================
 // Sampled templates (include/xgate_pos_sample.h): the forced rollout above with the tag of step t + 1 DRAWN at the end of step t
-// from the head's distribution and written to `templates`, where the next step's launch reads it as the forced kernel reads the
-// caller's.  Same prologue, same broadcast, same first three launches per step (rollout_rows), same workspace; only the fourth
-// launch differs: pos_cell_head_sampled_kernel.  The draw is the captioner's (xg_select.h): inverse CDF over
-// exp((x - max x) / temperature) from a uniform the caller supplies.
+// from the head's distribution and written to `templates`, where the next step's launch reads it as the forced call reads the
+// caller's.  The same rollout_rows and workspace; the step's fourth launch is pos_cell_head_rows_kernel<true>.
 // ==================================================================================================================================
 #include "../../include/xgate_pos_sample.h"
 
-namespace {
-
-struct SampledArgs {             // (ForcedArgs' operands under ForcedArgs' names: rollout_rows fills either)
-    const float* S;
-    const float* tab;
-    const float *logit_w, *logit_b;
-    float* X;
-    float* c;
-    int64_t* tmpl;               // (M,T-1) out: column t is written by step t and read by step t + 1
-    float *tag_logp, *states, *masks, *pos_feats;
-    const float* uniforms;       // (M,T-1)
-    float temperature;
-    int R, C, T, t;
-};
-
-// inclusive scan over the 64 lanes: row_shr 1, 2, 4, 8 inside each row of 16 (zeros shift in), then the totals of the rows before
-// the lane's own, added in row order.  Every lane must be active.
-__device__ __forceinline__ float wave_scan(float v) {
-    v += xg_dpp<0x111>(v);
-    v += xg_dpp<0x112>(v);
-    v += xg_dpp<0x114>(v);
-    v += xg_dpp<0x118>(v);
-    const float r0 = xg_readlane(v, 15), r1 = xg_readlane(v, 31), r2 = xg_readlane(v, 47);
-    const int row = (threadIdx.x & 63) >> 4;
-    const float before = row == 0 ? 0.f : (row == 1 ? r0 : (row == 2 ? r0 + r1 : (r0 + r1) + r2));
-    return before + v;
-}
-
-// one workgroup per row, step t: pos_cell_head_forced_kernel with the template an OUTPUT.  The tag fed is tmpl[t-1], which the
-// launch of step t - 1 drew (BOS at t = 0); the cell is the forced kernel's, expression for expression; then, for t < T - 1, the
-// head's logits and log-sum-exp as there, and the draw of tmpl[t]: the first category whose running sum of
-// w_c = exp((x_c - max x) / temperature) exceeds uniforms[t] * sum(w), C - 1 when none does.  tmpl[t] = tag * unfinished and
-// tag_logp[t] = the untempered log-probability of the tag while the row is unfinished at step t, 0 after.
-__global__ void __launch_bounds__(STEP_TPB) pos_cell_head_sampled_kernel(SampledArgs a) {
-    extern __shared__ float lds[];
-    float* hs = lds;             // R
-    float* lg = lds + a.R;       // C
-    float* wt = lg + a.C;        // C (the serial head's weights)
-    const int tid = threadIdx.x, R = a.R, C = a.C, T = a.T, t = a.t;
-    const size_t row = blockIdx.x;
-    int64_t* tr = a.tmpl + row * (T - 1);
-    int64_t tk = 0;
-    float m = 1.0f;
-    if (t > 0) {
-        tk = tr[t - 1];
-        tk = tk < 0 ? 0 : (tk >= C ? C - 1 : tk);
-        m = tk > 0 ? a.masks[row * T + t - 1] : 0.0f;
-    }
-    const float* s = a.S + row * 4 * R;
-    const float* tb = a.tab + (size_t)tk * 4 * R;
-    float* xh = a.X + row * 2 * R + R;
-    float* cb = a.c + row * R;
-    float* st = a.states ? a.states + (row * T + t) * R : nullptr;
-    float* pf = t == T - 1 ? a.pos_feats + row * R : nullptr;
-    for (int j = tid; j < R; j += STEP_TPB) {
-        const float ig = xg_sigmoid(s[j] + tb[j]), fg = xg_sigmoid(s[R + j] + tb[R + j]);
-        const float og = xg_sigmoid(s[2 * R + j] + tb[2 * R + j]), gg = xg_tanh(s[3 * R + j] + tb[3 * R + j]);
-        const float cp = cb[j], hp = xh[j];
-        float cn = fg * cp + ig * gg;
-        cn = cn * m + cp * (1.0f - m);
-        float hn = og * xg_tanh(cn);
-        hn = hn * m + hp * (1.0f - m);
-        cb[j] = cn;
-        xh[j] = hn;
-        hs[j] = hn;
-        if (st) st[j] = hn;
-        if (pf) pf[j] = hn;
-    }
-    if (tid == 0) a.masks[row * T + t] = m;
-    if (t + 1 >= T) return;                                     // (no tag follows the last step)
-    const float u = a.uniforms[row * (T - 1) + t];              // (requested here: the head's products hide the round trip)
-    __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int cc = wave; cc < C; cc += STEP_WAVES) {
-        const float* wr = a.logit_w + (size_t)cc * R;
-        float acc = 0.f;
-#pragma unroll 8
-        for (int j = lane; j < R; j += 64) acc += wr[j] * hs[j];
-        acc = wave_sum(acc);
-        if (lane == 0) lg[cc] = acc + a.logit_b[cc];
-    }
-    __syncthreads();
-    float* out = a.tag_logp + row * (T - 1) + t;
-    if (C <= 64) {                                              // one lane per category
-        if (wave == 0) {
-            const float v = lane < C ? lg[lane] : -INFINITY;
-            const float mx = wave_max(v);
-            const float lse = mx + logf(wave_sum(lane < C ? expf(v - mx) : 0.f));
-            const float inc = wave_scan(lane < C ? expf((v - mx) / a.temperature) : 0.f);
-            const float target = u * xg_readlane(inc, C - 1);     // (the total in the last category's own summation order)
-            const unsigned long long pass = __ballot(lane < C && inc > target);
-            const int nx = pass ? __ffsll(pass) - 1 : C - 1;   // (nothing passes: rounding at the very end, or u = 1)
-            if (lane == 0) {
-                *out = m != 0.0f ? lg[nx] - lse : 0.0f;
-                tr[t] = m != 0.0f ? nx : 0;
-            }
-        }
-    } else if (tid == 0) {
-        float mx = lg[0];
-        for (int cc = 1; cc < C; ++cc) mx = fmaxf(mx, lg[cc]);
-        float se = 0.f;
-        for (int cc = 0; cc < C; ++cc) se += expf(lg[cc] - mx);
-        float tot = 0.f;
-        for (int cc = 0; cc < C; ++cc) {
-            wt[cc] = expf((lg[cc] - mx) / a.temperature);
-            tot += wt[cc];
-        }
-        const float target = u * tot;
-        int nx = C - 1;
-        float run = 0.f;
-        for (int cc = 0; cc < C; ++cc) {
-            run += wt[cc];
-            if (run > target) { nx = cc; break; }
-        }
-        *out = m != 0.0f ? lg[nx] - (mx + logf(se)) : 0.0f;
-        tr[t] = m != 0.0f ? nx : 0;
-    }
-}
-
-}  // namespace
-
 extern "C" int xgps_version(void) { return XGPS_VERSION; }
 
-extern "C" size_t xgps_workspace_bytes(const XgpDims* d, int32_t S) {
-    if (!ctrl_dims_ok(d, S)) return 0;
-    return cws_layout(d, S, nullptr).floats * sizeof(float);
-}
+extern "C" size_t xgps_workspace_bytes(const XgpDims* d, int32_t S) { return xgpc_workspace_bytes(d, S); }
 
 extern "C" int xgps_sample_templates(void* stream, const XgpDims* d, int32_t S, float temperature, const XgpParams* p,
                                      const XgBnState* bn, const float* feats_rgb, const float* feats_opfl, const float* feat_mask,
@@ -1622,13 +1526,8 @@ extern "C" int xgps_sample_templates(void* stream, const XgpDims* d, int32_t S, 
         !feats_opfl || !feat_mask || !uniforms || !templates || !tag_logp || !masks || !pos_feats || !n_out || !ws)
         return XG_EINVAL;
     if (ws_bytes < cws_layout(d, S, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    SampledArgs sa{};
+    RowsArgs sa{};
     sa.tmpl = templates; sa.tag_logp = tag_logp; sa.states = states; sa.masks = masks; sa.pos_feats = pos_feats;
-    sa.uniforms = uniforms; sa.temperature = temperature;
-    XG_TRY(rollout_rows(st, d, S, p, bn, feats_rgb, feats_opfl, feat_mask, sa, pos_cell_head_sampled_kernel,
-                        (size_t)(d->R + 2 * d->C) * sizeof(float), cws_layout(d, S, ws)));
-    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, nullptr, masks, d->B * S, d->T, 1, n_out);
-    XG_CHECK_LAUNCH();
-    return XG_OK;
+    sa.tmpl_out = templates; sa.uniforms = uniforms; sa.temperature = temperature;
+    return rollout_rows((hipStream_t)stream, d, S, p, bn, feats_rgb, feats_opfl, feat_mask, sa, true, n_out, cws_layout(d, S, ws));
 }

@@ -23,7 +23,7 @@ F64 = torch.float64
 ST_TOL, LP_TOL = 1e-4, 3e-4
 GROUP = 4                                   # XGPC_TEMPLATE_GROUP (tests/test_pos_control_cpu.py pins the binding's copy to the header)
 
-# name -> (dims, S): the smallest shapes at which each branch of pos_attn_group_kernel / pos_cell_head_forced_kernel and of the
+# name -> (dims, S): the smallest shapes at which each branch of pos_attn_group_kernel / pos_cell_head_rows_kernel<false> and of the
 # launches around them can go wrong
 SMALL = dict(E=18, C=5, L=6, F1=20, F2=12)
 CASES = {

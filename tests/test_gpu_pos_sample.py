@@ -1,6 +1,6 @@
 """Sampled POS templates on the MI355X: PosModel.sample_templates (include/xgate_pos_sample.h) against the float64 oracle's own
 draw from the same uniforms (tests/pos_sample_oracle.py in eager torch on the same GPU), every row against a float64 replay of
-the kernel's own tokens (tests/pos_control_oracle.py) over every branch of pos_cell_head_sampled_kernel and the launches around
+the kernel's own tokens (tests/pos_control_oracle.py) over every branch of pos_cell_head_rows_kernel<true> and the launches around
 it, bit for bit against the forced call fed the sampled templates and against the greedy call at a low temperature, at the edge
 uniforms, and control.caption_sampled against control.caption_with_templates.
 
@@ -26,7 +26,7 @@ GROUP = 4                                   # XGPC_TEMPLATE_GROUP
 FIXTURES = ("tiny", "c1", "ragged", "eos")
 TEMPERATURES = (0.7, 1.0, 1.3)
 
-# name -> (dims, S): the smallest shapes at which each branch of pos_cell_head_sampled_kernel and of the launches around it can go
+# name -> (dims, S): the smallest shapes at which each branch of pos_cell_head_rows_kernel<true> and of the launches around it can go
 # wrong (tests/test_pos_sample_cpu.py: test_replay_cases_reach_the_branches_they_name)
 SMALL = dict(E=18, C=5, L=6, F1=20, F2=12)
 HEAD = dict(B=2, K=5, R=40, A=52, E=24, L=6, F1=20, F2=12)

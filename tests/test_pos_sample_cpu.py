@@ -204,7 +204,7 @@ def test_replay_cases_reach_the_branches_they_name():
     assert (d["B"], d["K"], d["R"], d["A"]) == (3, 5, 22, 38) and d["A"] % 4 and d["R"] % 4      # scalar loads; the staged product
     d, S = CASES["group_plus_1"]
     assert S == 5 and S % GROUP == 1 and S > GROUP                                              # a full group and a partial one
-    # pos_cell_head_sampled_kernel: C <= 64 one lane per category (scan + ballot), serial beyond
+    # pos_cell_head_rows_kernel<true>: C <= 64 one lane per category (scan + ballot), serial beyond
     assert [CASES[k][0]["C"] for k in ("c64", "c65", "c130")] == [64, 65, 130]
     for k in ("c64", "c65", "c130"):
         d, S = CASES[k]
