@@ -4,7 +4,9 @@ The captioner is steered by the global POS vector ``pos_feats`` (caption_src/dat
 generator's rollout).  ``PosModel.sample_forced`` rolls the POS generator along a caller's tag sequence instead of its own greedy
 choice (include/xgate_pos_control.h), S templates for each of B videos; ``caption_with_templates`` feeds the resulting states to the
 captioner without leaving the device.  ``PosModel.sample_templates`` (include/xgate_pos_sample.h) lets the generator draw the templates
-itself, ``caption_sampled`` captions under them and ``first_occurrences`` marks a video's distinct draws.  Eval mode, fp32, one GPU;
+itself, ``caption_sampled`` captions under them and ``first_occurrences`` marks a video's distinct draws.
+``PosModel.beam_templates`` (include/xgate_pos_beam.h) finds the W templates the generator thinks most likely and ``caption_beam``
+captions under them.  Eval mode, fp32, one GPU;
 sharing the captioner's encoder across a video's templates is not done (the video inputs are repeated per template).
 """
 from __future__ import annotations
@@ -106,3 +108,18 @@ def caption_sampled(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, S, t
                                     feat_mask.repeat_interleave(S, 0), pos_feats, opt)
         first = first_occurrences(templates)
     return seq.reshape(B, S, -1), slp.reshape(B, S, -1), templates, tag_logp.sum(2), first
+
+
+def caption_beam(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, beam_size=5, suppress_tag=1, opt={}):
+    """Caption each of the B videos under the W = beam_size POS templates the generator itself finds most likely: (seq (B,W,n)
+    int64, seqLogprobs (B,W,n), templates (B,W,L) int64, score (B,W)), a video's templates best first.  The beam search
+    (``pos_model.beam_templates``: `beam_size`, `suppress_tag` as there) runs without a host synchronisation and its templates go
+    through ``caption_with_templates``.  `pos_feats` come from that forced replay: the search permutes its slots at every step and
+    overwrites dead ones, so it ends with no held state per returned beam to hand over.  `score` is the beam's summed
+    log-probability at its finish (with the -1000 of a suppressed tag, should the beam hold one), not the replay's template score.
+    Inference only: both models run under ``torch.no_grad()``."""
+    with torch.no_grad():
+        templates, _, score, _ = pos_model.beam_templates(feats_rgb, feats_opfl, feat_mask, beam_size=beam_size,
+                                                          suppress_tag=suppress_tag, trim=False)
+        seq, slp, _ = caption_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, opt)
+    return seq, slp, templates, score

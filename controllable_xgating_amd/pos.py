@@ -6,9 +6,11 @@ fp32 products.  ``PosModel`` keeps the reference's class surface and state_dict 
 call (the reference's data-dependent lengths T' and n are computed on the device).  In train mode the teacher-forced forward runs
 include/xgate_pos_train.h (BatchNorm over the batch statistics, hash dropout) and ``loss.backward()`` its HIP backward; the parameters
 live in one flat buffer (``flat_parameters()`` / ``flat_grads()``) so that ``train.ClipAdam`` updates them in one launch.  Train-mode
-``sample()``, beam search and ``sample(sample_max=0)`` are not implemented and raise.  ``sample_forced`` rolls the generator along a
-caller's POS templates, several per video (include/xgate_pos_control.h), and ``sample_templates`` draws the templates from the
-generator's own distribution, several per video (include/xgate_pos_sample.h); control.py carries either result into the captioner.
+``sample()``, ``sample(beam_size > 1)`` and ``sample(sample_max=0)`` are not implemented and raise.  ``sample_forced`` rolls the
+generator along a caller's POS templates, several per video (include/xgate_pos_control.h), ``sample_templates`` draws the templates
+from the generator's own distribution, several per video (include/xgate_pos_sample.h), and ``beam_templates`` returns the W
+templates the generator itself finds most likely for each video (beam search on the device, include/xgate_pos_beam.h); control.py
+carries each of these results into the captioner.
 """
 from __future__ import annotations
 
@@ -71,7 +73,7 @@ class PosModel(nn.Module):
             self.logit.bias.fill_(0)
             self.logit.weight.uniform_(-0.1, 0.1)
         self._ws = {}
-        self._cws = None                # workspace of sample_forced (grows to the largest call)
+        self._cws = None                # workspace of sample_forced / sample_templates / beam_templates (grows to the largest call)
         self._tws = None                # training workspace: the saved activations of the last train-mode forward
         self._train_gen = 0             # bumped by every train-mode forward: a backward of an older one must not read them
         self._flat = self._gflat = None
@@ -423,6 +425,54 @@ class PosModel(nn.Module):
         return (templates[:, :, :n], tag_logp[:, :, :n], None if states is None else states[:, :, :n + 1], masks[:, :, :n + 1],
                 pos_feats)
 
+
+    def beam_templates(self, feats_rgb, feats_opfl, feat_mask, beam_size=5, suppress_tag=1, trim=True, return_trace=False):
+        """The W = beam_size templates the generator itself finds most likely for each of the B videos (include/xgate_pos_beam.h:
+        the reference's sample_beam, pos_src/SAModel.py:104-134, run on the device with no host work per step).  Returns (templates
+        (B,W,n) int64, tag_logp (B,W,n), score (B,W), masks (B,W,n+1)[, trace (B,L,W,2) int32]).
+
+        A video's beams come best first, each ranked by its summed log-probability `score` at the moment it finished.  `templates`
+        is zero after a beam's finish, so it is directly a valid input of `sample_forced`; tag_logp holds the log-probability of
+        every tag up to and including the end tag.  `suppress_tag`: the category whose log-probability is lowered by 1000 before
+        every merge (the reference does this for category 1); -1 turns it off.  `trim`: cut to the reference's n (one host
+        synchronisation); trim=False returns the full seq_length and does not synchronise.  `return_trace`: also the (token, parent
+        slot) of every slot and step.  beam_size may not exceed category_size or 8."""
+        from . import _native_pos_beam as npb
+        self._check_eval(feats_rgb, feats_opfl, feat_mask)
+        fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
+        B, K = fm.shape
+        L = self.seq_length
+        dev = fr.device
+        W, sup = int(beam_size), int(suppress_tag)
+        if W < 1 or W > self.category_size or W > npb.XGPB_MAX_BEAM:
+            raise ValueError("1 <= beam_size <= min(category_size = %d, %d) expected, got %d" % (self.category_size, npb.XGPB_MAX_BEAM, W))
+        if sup >= self.category_size:
+            raise ValueError("suppress_tag must lie below category_size = %d (-1: none), got %d" % (self.category_size, sup))
+        dims = self._dims(B, K, L + 1)
+        lib = npb.lib()
+        nbytes = lib.xgpb_workspace_bytes(C.byref(dims), W)
+        if nbytes == 0:
+            raise nv.XgError("xgpb_workspace_bytes: invalid dims, too many rows (B %d, W %d) or W * rnn_size beyond the merge "
+                             "kernel's LDS" % (B, W))
+        ws = self._cws
+        if ws is None or ws.device != dev or ws.numel() < nbytes:
+            ws = self._cws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        templates = torch.empty(B, W, L, dtype=torch.int64, device=dev)
+        tag_logp = torch.empty(B, W, L, device=dev)
+        score = torch.empty(B, W, device=dev)
+        masks = torch.empty(B, W, L + 1, device=dev)
+        trace = torch.empty(B, L, W, 2, dtype=torch.int32, device=dev) if return_trace else None
+        n_out = torch.empty(1, dtype=torch.int32, device=dev)
+        P, bn = self._params(), self._bn()
+        nv.check(lib.xgpb_beam_templates(_stream(), C.byref(dims), W, sup, C.byref(P), C.byref(bn), fr.data_ptr(), fo.data_ptr(),
+                                         fm.data_ptr(), templates.data_ptr(), tag_logp.data_ptr(), score.data_ptr(), masks.data_ptr(),
+                                         n_out.data_ptr(), None if trace is None else trace.data_ptr(), ws.data_ptr(), ws.numel()),
+                 "xgpb_beam_templates")
+        if trim:
+            n = int(n_out.item())                   # the one host synchronisation of the call
+            templates, tag_logp, masks = templates[:, :, :n], tag_logp[:, :, :n], masks[:, :, :n + 1]
+        out = (templates, tag_logp, score, masks)
+        return out + (trace,) if return_trace else out
 
 class _PosTrainFunction(torch.autograd.Function):
     @staticmethod
