@@ -9,28 +9,20 @@ from . import _native_pos as npos
 
 XGPS_VERSION = 1                      # include/xgate_pos_sample.h
 
+
 _lib = None
 
 
 def lib():
     """The library with the xgps_* signatures declared (loaded once)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    L = npos.lib()
-    need = ("xgps_version", "xgps_workspace_bytes", "xgps_sample_templates")
-    missing = [n for n in need if not hasattr(L, n)]
-    if missing:
-        raise nv.XgError("%s lacks %s: a stale build -- rebuild it with `python __graft_entry__.py --force`"
-                         % (nv.LIB_PATH, ", ".join(missing)))
-    vp = C.c_void_p
-    PD, PP, PB = C.POINTER(npos.XgpDims), C.POINTER(npos.XgpParams), C.POINTER(nv.XgBnState)
-    L.xgps_version.restype = C.c_int
-    L.xgps_workspace_bytes.restype = C.c_size_t
-    L.xgps_workspace_bytes.argtypes = [PD, C.c_int32]
-    L.xgps_sample_templates.restype = C.c_int
-    L.xgps_sample_templates.argtypes = [vp, PD, C.c_int32, C.c_float, PP, PB, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
-    if L.xgps_version() != XGPS_VERSION:
-        raise nv.XgError("libxgate_hip.so carries POS sampling ABI %d, this binding expects %d" % (L.xgps_version(), XGPS_VERSION))
-    _lib = L
-    return L
+    if _lib is None:
+        L = npos.lib()
+        vp, PD, PP, PB = C.c_void_p, C.POINTER(npos.XgpDims), C.POINTER(npos.XgpParams), C.POINTER(nv.XgBnState)
+        _lib = npos.declare(L, "POS sampling", "xgps_version", XGPS_VERSION, {
+            "xgps_version": (C.c_int, []),
+            "xgps_workspace_bytes": (C.c_size_t, [PD, C.c_int32]),
+            "xgps_sample_templates": (C.c_int, [vp, PD, C.c_int32, C.c_float, PP, PB, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                C.c_size_t]),
+        })
+    return _lib

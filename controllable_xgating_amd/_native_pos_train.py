@@ -20,24 +20,14 @@ _lib = None
 def lib():
     """The library with the xgpt_* signatures declared (loaded once)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    L = npos.lib()
-    need = ("xgpt_version", "xgpt_workspace_bytes", "xgpt_forward_train", "xgpt_backward")
-    missing = [n for n in need if not hasattr(L, n)]
-    if missing:
-        raise nv.XgError("%s lacks %s: a stale build -- rebuild it with `python __graft_entry__.py --force`"
-                         % (nv.LIB_PATH, ", ".join(missing)))
-    vp = C.c_void_p
-    PD, PP, PB, PR = C.POINTER(npos.XgpDims), C.POINTER(npos.XgpParams), C.POINTER(nv.XgBnState), C.POINTER(XgptRun)
-    L.xgpt_version.restype = C.c_int
-    L.xgpt_workspace_bytes.restype = C.c_size_t
-    L.xgpt_workspace_bytes.argtypes = [PD]
-    L.xgpt_forward_train.restype = C.c_int
-    L.xgpt_forward_train.argtypes = [vp, PD, PP, PB, PR, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
-    L.xgpt_backward.restype = C.c_int
-    L.xgpt_backward.argtypes = [vp, PD, PP, PP, PR, vp, vp, vp, C.c_int32, vp, vp, C.c_size_t]
-    if L.xgpt_version() != XGPT_VERSION:
-        raise nv.XgError("libxgate_hip.so carries POS training ABI %d, this binding expects %d" % (L.xgpt_version(), XGPT_VERSION))
-    _lib = L
-    return L
+    if _lib is None:
+        L = npos.lib()
+        vp, PD, PP, PB = C.c_void_p, C.POINTER(npos.XgpDims), C.POINTER(npos.XgpParams), C.POINTER(nv.XgBnState)
+        PR = C.POINTER(XgptRun)
+        _lib = npos.declare(L, "POS training", "xgpt_version", XGPT_VERSION, {
+            "xgpt_version": (C.c_int, []),
+            "xgpt_workspace_bytes": (C.c_size_t, [PD]),
+            "xgpt_forward_train": (C.c_int, [vp, PD, PP, PB, PR, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]),
+            "xgpt_backward": (C.c_int, [vp, PD, PP, PP, PR, vp, vp, vp, C.c_int32, vp, vp, C.c_size_t]),
+        })
+    return _lib

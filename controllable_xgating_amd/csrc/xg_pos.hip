@@ -366,7 +366,13 @@ int64_t numel_of(const XgpDims* d, int i) {
     return -1;
 }
 
-// workspace regions in floats, each rounded up to 64 floats (256 bytes)
+// workspace regions in floats, each rounded up to 64 floats (256 bytes); every layout carves with one (base null: sizes only)
+struct Carve {
+    float* base;
+    size_t off;
+    float* take(size_t n) { float* r = base ? base + off : nullptr; off += (n + 63) / 64 * 64; return r; }
+};
+
 struct Ws {
     float *Z, *Xe, *Pre, *S2, *c2, *hz, *Hcat, *V, *vbar, *Q, *tab, *X, *P, *S, *c;
     int64_t* tok;
@@ -376,30 +382,28 @@ struct Ws {
 
 Ws ws_layout(const XgpDims* d, void* base) {
     const size_t B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, BK = B * K;
-    float* p = (float*)base;
-    size_t off = 0;
-    auto take = [&](size_t n) { float* r = p ? p + off : nullptr; off += (n + 63) / 64 * 64; return r; };
+    Carve cv{(float*)base, 0};
     Ws w;
-    w.Z = take(2 * BK * R);          // visual embeddings (rgb, opfl)
-    w.Xe = take(2 * BK * R);         // after BatchNorm + ReLU + frame mask
-    w.Pre = take(2 * BK * 4 * R);    // hoisted input side of the two encoder cells
-    w.S2 = take(2 * B * 4 * R);      // recurrent side of one frame
-    w.c2 = take(2 * B * R);
-    w.hz = take(B * R);              // zero state
-    w.Hcat = take(BK * 2 * R);       // [h_rgb ; h_opfl] of every frame
-    w.V = take(BK * R);
-    w.vbar = take(B * R);
-    w.Q = take(BK * A);              // v2a(V)
-    w.tab = take(C * 4 * R);         // embed i2h^T + i2h.bias
-    w.X = take(B * 2 * R);           // [af ; h]
-    w.P = take(B * A);
-    w.S = take(B * 4 * R);
-    w.c = take(B * R);
-    w.tok = (int64_t*)take(2 * B);
-    w.pk_h2a = take(packed_floats(A, R));
-    w.pk_a2h = take(packed_floats(4 * R, R));
-    w.pk_h2h = take(packed_floats(4 * R, R));
-    w.floats = off;
+    w.Z = cv.take(2 * BK * R);          // visual embeddings (rgb, opfl)
+    w.Xe = cv.take(2 * BK * R);         // after BatchNorm + ReLU + frame mask
+    w.Pre = cv.take(2 * BK * 4 * R);    // hoisted input side of the two encoder cells
+    w.S2 = cv.take(2 * B * 4 * R);      // recurrent side of one frame
+    w.c2 = cv.take(2 * B * R);
+    w.hz = cv.take(B * R);              // zero state
+    w.Hcat = cv.take(BK * 2 * R);       // [h_rgb ; h_opfl] of every frame
+    w.V = cv.take(BK * R);
+    w.vbar = cv.take(B * R);
+    w.Q = cv.take(BK * A);              // v2a(V)
+    w.tab = cv.take(C * 4 * R);         // embed i2h^T + i2h.bias
+    w.X = cv.take(B * 2 * R);           // [af ; h]
+    w.P = cv.take(B * A);
+    w.S = cv.take(B * 4 * R);
+    w.c = cv.take(B * R);
+    w.tok = (int64_t*)cv.take(2 * B);
+    w.pk_h2a = cv.take(packed_floats(A, R));
+    w.pk_a2h = cv.take(packed_floats(4 * R, R));
+    w.pk_h2h = cv.take(packed_floats(4 * R, R));
+    w.floats = cv.off;
     return w;
 }
 
@@ -443,6 +447,54 @@ bool params_ok(const XgpParams* p) {
 
 bool bn_ok(const XgBnState* bn) { return bn && bn->rgb_mean && bn->rgb_var && bn->opfl_mean && bn->opfl_var; }
 
+constexpr float POS_BN_EPS = 1e-5f;
+
+// one modality (rgb, opfl) of the encoder: its features and parameters out of XgpParams / XgBnState, then the recurrent loop's
+// operands, set by the caller: the hoisted input side `pre` (B K,4R), the cell state before frame 0 `c0` (B,R), the states `cs`
+// and, to keep them, the activated gates (B K,4R).  The parameter pointers are non-const on purpose: encoder_bwd fills a second
+// pair from the gradient struct and adds into them (there only ew .. bhh mean anything); the forward encoders only read theirs.
+struct EncMod {
+    const float* feats;
+    int F, site;
+    float *ew, *eb, *bg, *bb, *rm, *rv, *wih, *whh, *bih, *bhh;
+    const float *pre, *c0;
+    float *cs, *gates;
+};
+
+void enc_mods(const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo, EncMod mo[2]) {
+    mo[0] = EncMod{fr, d->F1, XG_SITE_EMB_RGB, p->emb_rgb_w, p->emb_rgb_b, p->bn_rgb_g, p->bn_rgb_b, bn ? bn->rgb_mean : nullptr,
+                   bn ? bn->rgb_var : nullptr, p->lstm_rgb_wih, p->lstm_rgb_whh, p->lstm_rgb_bih, p->lstm_rgb_bhh};
+    mo[1] = EncMod{fo, d->F2, XG_SITE_EMB_OPFL, p->emb_opfl_w, p->emb_opfl_b, p->bn_opfl_g, p->bn_opfl_b, bn ? bn->opfl_mean : nullptr,
+                   bn ? bn->opfl_var : nullptr, p->lstm_opfl_wih, p->lstm_opfl_whh, p->lstm_opfl_bih, p->lstm_opfl_bhh};
+}
+
+// the two masked LSTM cells over the K frames into Hcat (B K,2R).  Frame k reads the cell state of frame k - 1 (c0 at k = 0) and
+// writes cs + k cstep, row stride ldc: cstep 0 is one state in place, cstep R with ldc = K R keeps every frame's.  `hz`: zero h.
+int encoder_recur(hipStream_t st, const XgpDims* d, const EncMod mo[2], const float* fm, const float* hz, float* S2, float* Hcat,
+                  int cstep, int ldc, const XgDrop& drop) {
+    const int B = d->B, K = d->K, R = d->R;
+    for (int k = 0; k < K; ++k) {
+        for (int m = 0; m < 2; ++m) {
+            const float* hp = k == 0 ? hz : Hcat + (size_t)(k - 1) * 2 * R + m * R;
+            float* S = S2 + (size_t)m * B * 4 * R;
+            XG_TRY(product(st, B, 4 * R, hp, k == 0 ? R : K * 2 * R, mo[m].whh, R, nullptr, 0, nullptr, 0, mo[m].bhh, S, 4 * R));
+            LstmFwdArgs a{};
+            a.s = S; a.lds_ = 4 * R;
+            a.add = mo[m].pre + (size_t)k * 4 * R; a.ldadd = K * 4 * R;
+            a.c_prev = k == 0 ? mo[m].c0 : mo[m].cs + (size_t)(k - 1) * cstep; a.ldcp = k == 0 ? R : ldc;
+            a.h_prev = nullptr; a.ldhp = 0;
+            a.mask = fm + k; a.ldm = K;
+            a.gates = mo[m].gates ? mo[m].gates + (size_t)k * 4 * R : nullptr; a.ldg = mo[m].gates ? K * 4 * R : 0;
+            a.c_out = mo[m].cs + (size_t)k * cstep; a.ldco = ldc;
+            a.h_out = Hcat + (size_t)k * 2 * R + m * R; a.ldho = K * 2 * R;
+            a.B = B; a.R = R; a.order = XG_ORDER_IFGO; a.mask_mode = XG_MASK_ZERO;
+            a.drop = drop;
+            XG_TRY(xgk_lstm_fwd(st, a));
+        }
+    }
+    return XG_OK;
+}
+
 // eval-mode encoder (pos_src/sub_modules.py:199-239) into V (B*K rows of R)
 int encoder(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
             const float* fm, float* V, const Ws& w) {
@@ -450,48 +502,23 @@ int encoder(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnStat
     const size_t BKR = (size_t)BK * R;
     XgDrop nodrop;
     nodrop.seed = 0; nodrop.site = 0; nodrop.step = 0; nodrop.thresh = 0u; nodrop.scale = 1.0f;
-    const float* feats[2] = {fr, fo};
-    const int F[2] = {d->F1, d->F2};
-    const float* ew[2] = {p->emb_rgb_w, p->emb_opfl_w};
-    const float* eb[2] = {p->emb_rgb_b, p->emb_opfl_b};
-    const float* bg[2] = {p->bn_rgb_g, p->bn_opfl_g};
-    const float* bb[2] = {p->bn_rgb_b, p->bn_opfl_b};
-    const float* rm[2] = {bn->rgb_mean, bn->opfl_mean};
-    const float* rv[2] = {bn->rgb_var, bn->opfl_var};
-    const float* wih[2] = {p->lstm_rgb_wih, p->lstm_opfl_wih};
-    const float* whh[2] = {p->lstm_rgb_whh, p->lstm_opfl_whh};
-    const float* bih[2] = {p->lstm_rgb_bih, p->lstm_opfl_bih};
-    const float* bhh[2] = {p->lstm_rgb_bhh, p->lstm_opfl_bhh};
+    EncMod mo[2];
+    enc_mods(d, p, bn, fr, fo, mo);
     for (int m = 0; m < 2; ++m) {
+        EncMod& e = mo[m];
         float* Z = w.Z + m * BKR;
         float* Xe = w.Xe + m * BKR;
-        XG_TRY(product(st, BK, R, feats[m], F[m], ew[m], F[m], nullptr, 0, nullptr, 0, eb[m], Z, R));
+        float* Pre = w.Pre + m * BKR * 4;
+        XG_TRY(product(st, BK, R, e.feats, e.F, e.ew, e.F, nullptr, 0, nullptr, 0, e.eb, Z, R));
         // eval BatchNorm with the running statistics, ReLU, then the frame mask (the dropout is the identity)
-        XG_TRY(xgk_bn_apply(st, Z, rm[m], rv[m], bg[m], bb[m], fm, Xe, BK, R, 1e-5f, nodrop));
-        XG_TRY(product(st, BK, 4 * R, Xe, R, wih[m], R, nullptr, 0, nullptr, 0, bih[m], w.Pre + m * BKR * 4, 4 * R));
-        XG_TRY(xgk_fill(st, w.c2 + (size_t)m * B * R, 0.f, (int64_t)B * R));
+        XG_TRY(xgk_bn_apply(st, Z, e.rm, e.rv, e.bg, e.bb, fm, Xe, BK, R, POS_BN_EPS, nodrop));
+        XG_TRY(product(st, BK, 4 * R, Xe, R, e.wih, R, nullptr, 0, nullptr, 0, e.bih, Pre, 4 * R));
+        e.pre = Pre;
+        e.c0 = e.cs = w.c2 + (size_t)m * B * R;     // one state per modality, zeroed here and updated in place
+        XG_TRY(xgk_fill(st, e.cs, 0.f, (int64_t)B * R));
     }
     XG_TRY(xgk_fill(st, w.hz, 0.f, (int64_t)B * R));
-    for (int k = 0; k < K; ++k) {
-        for (int m = 0; m < 2; ++m) {
-            const float* hp = k == 0 ? w.hz : w.Hcat + (size_t)(k - 1) * 2 * R + m * R;
-            const int ldh = k == 0 ? R : K * 2 * R;
-            float* S = w.S2 + (size_t)m * B * 4 * R;
-            XG_TRY(product(st, B, 4 * R, hp, ldh, whh[m], R, nullptr, 0, nullptr, 0, bhh[m], S, 4 * R));
-            LstmFwdArgs a{};
-            a.s = S; a.lds_ = 4 * R;
-            a.add = w.Pre + m * BKR * 4 + (size_t)k * 4 * R; a.ldadd = K * 4 * R;
-            a.c_prev = w.c2 + (size_t)m * B * R; a.ldcp = R;
-            a.h_prev = nullptr; a.ldhp = 0;
-            a.mask = fm + k; a.ldm = K;
-            a.gates = nullptr; a.ldg = 0;
-            a.c_out = w.c2 + (size_t)m * B * R; a.ldco = R;
-            a.h_out = w.Hcat + (size_t)k * 2 * R + m * R; a.ldho = K * 2 * R;
-            a.B = B; a.R = R; a.order = XG_ORDER_IFGO; a.mask_mode = XG_MASK_ZERO;
-            a.drop = nodrop;
-            XG_TRY(xgk_lstm_fwd(st, a));
-        }
-    }
+    XG_TRY(encoder_recur(st, d, mo, fm, w.hz, w.S2, w.Hcat, 0, R, nodrop));
     // late fusion: relu(W [h_rgb ; h_opfl] + b); masked frames carry relu(b)
     return product(st, BK, R, w.Hcat, 2 * R, p->fusion_w, 2 * R, nullptr, 0, nullptr, 0, p->fusion_b, V, R, true);
 }
@@ -524,34 +551,37 @@ int prologue(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnSta
     return hoist_operands(st, d, p, w.V, w.Q, w.tab, w.pk_h2a, w.pk_a2h, w.pk_h2h);
 }
 
-// the context parts of pos_attn_kernel / pos_attn_group_kernel: as many as fill the workgroup, at most one per frame
-int attn_nsplit(int K, int R) {
-    const int nsplit = STEP_TPB / R;
-    return nsplit < 1 ? 1 : (nsplit > K ? K : nsplit);
+// step_front: the first three launches of the decoder step, the same in every eval call, over M = B S rows (row b S + s) with the
+// operands X (M,2R), P (M,A), S (M,4R) and the videos' hoisted operands `v`.  The plan is what the attention launch needs beyond
+// that, computed once per call before the time loop.  (Both are defined below pos_attn_group_kernel, the attention of S > 1.)
+struct StepPlan {
+    int S;                       // rows per video
+    int G;                       // 0: pos_attn_kernel (S = 1), else pos_attn_group_kernel<G>
+    int nsplit, pr_floats;
+    size_t lds;                  // the attention's dynamic LDS bytes
+    bool v4;
+};
+StepPlan step_plan(const XgpDims* d, int S);
+// pos_attn_kernel over B rows, each with its own video (the plan's S = 1 form)
+void launch_attn(hipStream_t st, int B, const StepPlan& pl, const float* P, const float* Q, const float* V, const float* w, float* X,
+                 int K, int R, int A) {
+    if (pl.v4) hipLaunchKernelGGL(pos_attn_kernel<true>, dim3(B), dim3(STEP_TPB), pl.lds, st, P, Q, V, w, X, K, R, A, pl.nsplit);
+    else       hipLaunchKernelGGL(pos_attn_kernel<false>, dim3(B), dim3(STEP_TPB), pl.lds, st, P, Q, V, w, X, K, R, A, pl.nsplit);
 }
 
-// pos_attn_kernel over B rows, each with its own video
-void launch_attn(hipStream_t st, int B, const float* P, const float* Q, const float* V, const float* w, float* X, int K, int R, int A) {
-    const int nsplit = attn_nsplit(K, R);
-    const size_t lds = (size_t)(2 * A + K + nsplit * R) * sizeof(float);
-    if (A % 4 == 0) hipLaunchKernelGGL(pos_attn_kernel<true>, dim3(B), dim3(STEP_TPB), lds, st, P, Q, V, w, X, K, R, A, nsplit);
-    else            hipLaunchKernelGGL(pos_attn_kernel<false>, dim3(B), dim3(STEP_TPB), lds, st, P, Q, V, w, X, K, R, A, nsplit);
-}
+int step_front(hipStream_t st, const XgpDims* d, const XgpParams* p, const StepPlan& pl, const Ws& v, float* X, float* P, float* S);
 
 // the prologue, the T decoder steps, then the early exit into `out`.  ca.cap set is the teacher-forced call (T' from the categories,
 // sub 0), null the greedy one (n from ca.masks, sub 1): the same test pos_cell_head_kernel makes (`tf`)
 int decode(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo, const float* fm,
            CellHeadArgs ca, int32_t* out, const Ws& w) {
-    const int B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, T = d->T;
+    const int B = d->B, R = d->R, C = d->C, T = d->T;
     XG_TRY(prologue(st, d, p, bn, fr, fo, fm, w));
     ca.S = w.S; ca.tab = w.tab; ca.logit_w = p->logit_w; ca.logit_b = p->logit_b;
     ca.X = w.X; ca.c = w.c; ca.B = B; ca.R = R; ca.C = C; ca.T = T;
+    const StepPlan pl = step_plan(d, 1);
     for (int t = 0; t < T; ++t) {
-        XG_TRY(product(st, B, A, w.X + R, 2 * R, p->h2a_w, R, nullptr, 0, nullptr, 0, p->h2a_b, w.P, A, false, w.pk_h2a));
-        launch_attn(st, B, w.P, w.Q, w.V, p->a2w_w, w.X, K, R, A);
-        XG_CHECK_LAUNCH();
-        XG_TRY(product(st, B, 4 * R, w.X, 2 * R, p->a2h_w, R, w.X + R, 2 * R, p->h2h_w, R, nullptr, w.S, 4 * R, false, w.pk_a2h,
-                       w.pk_h2h));
+        XG_TRY(step_front(st, d, p, pl, w, w.X, w.P, w.S));
         ca.t = t;
         hipLaunchKernelGGL(pos_cell_head_kernel, dim3(B), dim3(STEP_TPB), (size_t)(R + C) * sizeof(float), st, ca);
         XG_CHECK_LAUNCH();
@@ -561,11 +591,18 @@ int decode(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState
     return XG_OK;
 }
 
+// the argument gate of every entry point, after the test of its own dims, scalars and pointers: parameters, running statistics
+// (bn_good: true for a call that takes none), features, ws, then its size against the call's layout (`floats`).  XG_EINVAL first.
+int args_gate(const XgpParams* p, bool bn_good, const float* fr, const float* fo, const float* fm, void* ws, size_t ws_bytes,
+              size_t floats) {
+    if (!params_ok(p) || !bn_good || !fr || !fo || !fm || !ws) return XG_EINVAL;
+    return ws_bytes < floats * sizeof(float) ? XG_EWORKSPACE : XG_OK;
+}
+
 int common_checks(const XgpDims* d, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo, const float* fm,
                   void* ws, size_t ws_bytes, bool need_t) {
-    if (!dims_ok(d, need_t) || !params_ok(p) || !bn_ok(bn) || !fr || !fo || !fm || !ws) return XG_EINVAL;
-    if (ws_bytes < ws_layout(d, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
-    return XG_OK;
+    if (!dims_ok(d, need_t)) return XG_EINVAL;
+    return args_gate(p, bn_ok(bn), fr, fo, fm, ws, ws_bytes, ws_layout(d, nullptr).floats);
 }
 
 }  // namespace
@@ -628,8 +665,6 @@ extern "C" int xgp_sample_greedy(void* stream, const XgpDims* d, const XgpParams
 #include "../../include/xgate_pos_train.h"
 
 namespace {
-
-constexpr float POS_BN_EPS = 1e-5f;
 
 XgDrop pos_drop(const XgptRun* run, uint32_t site, uint32_t step) {
     XgDrop d;
@@ -801,30 +836,28 @@ struct TWs {
 
 TWs tws_layout(const XgpDims* d, void* base) {
     const size_t B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, E = d->E, T = d->T, BK = B * K;
-    float* p = (float*)base;
-    size_t off = 0;
-    auto take = [&](size_t n) { float* r = p ? p + off : nullptr; off += (n + 63) / 64 * 64; return r; };
+    Carve cv{(float*)base, 0};
     TWs w;
     for (int m = 0; m < 2; ++m) {
-        w.Z[m] = take(BK * R); w.Xe[m] = take(BK * R); w.mean[m] = take(R); w.var[m] = take(R);
-        w.Pre[m] = take(BK * 4 * R); w.G[m] = take(BK * 4 * R); w.Cs[m] = take(BK * R);
+        w.Z[m] = cv.take(BK * R); w.Xe[m] = cv.take(BK * R); w.mean[m] = cv.take(R); w.var[m] = cv.take(R);
+        w.Pre[m] = cv.take(BK * 4 * R); w.G[m] = cv.take(BK * 4 * R); w.Cs[m] = cv.take(BK * R);
     }
-    w.S2 = take(2 * B * 4 * R); w.zero = take(B * R); w.Hcat = take(BK * 2 * R); w.V = take(BK * R); w.vbar = take(B * R);
-    w.Q = take(BK * A); w.tab = take(C * 4 * R);
-    w.Hst = take((T + 1) * B * R); w.Cst = take((T + 1) * B * R); w.P = take(T * B * A); w.ALPHA = take(T * B * K);
-    w.AF = take(T * B * R); w.GD = take(T * B * 4 * R); w.LP = take(T * B * C); w.S = take(B * 4 * R); w.nm = take(B * T);
-    w.cap = (int64_t*)take(2 * B * T);
-    w.pk_h2a = take(packed_floats(A, R)); w.pk_a2h = take(packed_floats(4 * R, R)); w.pk_h2h = take(packed_floats(4 * R, R));
-    w.pkt_a2h = take(packed_floats(R, 4 * R)); w.pkt_h2h = take(packed_floats(R, 4 * R)); w.pkt_h2a = take(packed_floats(R, A));
-    w.dH[0] = take(B * R); w.dH[1] = take(B * R); w.dC = take(B * R);
-    w.DS = take(T * B * 4 * R); w.DP = take(T * B * A); w.DAF = take(T * B * R); w.DE = take(T * B * K); w.DLOG = take(T * B * C);
-    w.Xemb = take(T * B * E); w.DXemb = take(T * B * E); w.DVPROJ = take(BK * A); w.DV = take(BK * R); w.dVw = take(BK * R);
-    w.dHcat = take(BK * 2 * R);
+    w.S2 = cv.take(2 * B * 4 * R); w.zero = cv.take(B * R); w.Hcat = cv.take(BK * 2 * R); w.V = cv.take(BK * R); w.vbar = cv.take(B * R);
+    w.Q = cv.take(BK * A); w.tab = cv.take(C * 4 * R);
+    w.Hst = cv.take((T + 1) * B * R); w.Cst = cv.take((T + 1) * B * R); w.P = cv.take(T * B * A); w.ALPHA = cv.take(T * B * K);
+    w.AF = cv.take(T * B * R); w.GD = cv.take(T * B * 4 * R); w.LP = cv.take(T * B * C); w.S = cv.take(B * 4 * R); w.nm = cv.take(B * T);
+    w.cap = (int64_t*)cv.take(2 * B * T);
+    w.pk_h2a = cv.take(packed_floats(A, R)); w.pk_a2h = cv.take(packed_floats(4 * R, R)); w.pk_h2h = cv.take(packed_floats(4 * R, R));
+    w.pkt_a2h = cv.take(packed_floats(R, 4 * R)); w.pkt_h2h = cv.take(packed_floats(R, 4 * R)); w.pkt_h2a = cv.take(packed_floats(R, A));
+    w.dH[0] = cv.take(B * R); w.dH[1] = cv.take(B * R); w.dC = cv.take(B * R);
+    w.DS = cv.take(T * B * 4 * R); w.DP = cv.take(T * B * A); w.DAF = cv.take(T * B * R); w.DE = cv.take(T * B * K); w.DLOG = cv.take(T * B * C);
+    w.Xemb = cv.take(T * B * E); w.DXemb = cv.take(T * B * E); w.DVPROJ = cv.take(BK * A); w.DV = cv.take(BK * R); w.dVw = cv.take(BK * R);
+    w.dHcat = cv.take(BK * 2 * R);
     for (int m = 0; m < 2; ++m) {
-        w.dHrec[m] = take(B * R); w.dCrec[m][0] = take(B * R); w.dCrec[m][1] = take(B * R); w.dS[m] = take(BK * 4 * R);
+        w.dHrec[m] = cv.take(B * R); w.dCrec[m][0] = cv.take(B * R); w.dCrec[m][1] = cv.take(B * R); w.dS[m] = cv.take(BK * 4 * R);
     }
-    w.Hprev = take(BK * R); w.dX = take(BK * R); w.bn_s1 = take(R); w.bn_s2 = take(R);
-    w.floats = off;
+    w.Hprev = cv.take(BK * R); w.dX = cv.take(BK * R); w.bn_s1 = cv.take(R); w.bn_s2 = cv.take(R);
+    w.floats = cv.off;
     return w;
 }
 
@@ -871,60 +904,34 @@ void pack_t(hipStream_t st, const float* W, int N, int K, float* dst) {
 int encoder_train(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const XgptRun* run, const float* fr,
                   const float* fo, const float* fm, const TWs& w) {
     const int B = d->B, K = d->K, R = d->R, BK = B * K;
-    const float* feats[2] = {fr, fo};
-    const int F[2] = {d->F1, d->F2};
-    const float* ew[2] = {p->emb_rgb_w, p->emb_opfl_w};
-    const float* eb[2] = {p->emb_rgb_b, p->emb_opfl_b};
-    const float* bg[2] = {p->bn_rgb_g, p->bn_opfl_g};
-    const float* bb[2] = {p->bn_rgb_b, p->bn_opfl_b};
-    float* rm[2] = {bn->rgb_mean, bn->opfl_mean};
-    float* rv[2] = {bn->rgb_var, bn->opfl_var};
-    const float* wih[2] = {p->lstm_rgb_wih, p->lstm_opfl_wih};
-    const float* whh[2] = {p->lstm_rgb_whh, p->lstm_opfl_whh};
-    const float* bih[2] = {p->lstm_rgb_bih, p->lstm_opfl_bih};
-    const float* bhh[2] = {p->lstm_rgb_bhh, p->lstm_opfl_bhh};
+    EncMod mo[2];
+    enc_mods(d, p, bn, fr, fo, mo);
     XgptRun nd = *run;
     nd.drop_p = 0.f;
     for (int m = 0; m < 2; ++m) {
-        XG_TRY(product(st, BK, R, feats[m], F[m], ew[m], F[m], nullptr, 0, nullptr, 0, eb[m], w.Z[m], R));
-        const XgDrop drop = pos_drop(run, m == 0 ? XG_SITE_EMB_RGB : XG_SITE_EMB_OPFL, 0);
+        EncMod& e = mo[m];
+        XG_TRY(product(st, BK, R, e.feats, e.F, e.ew, e.F, nullptr, 0, nullptr, 0, e.eb, w.Z[m], R));
+        const XgDrop drop = pos_drop(run, e.site, 0);
         if (run->train) {
             // batch statistics over all B K rows (masked frames included, as nn.BatchNorm1d sees them) + the running update
-            const int rc = xgk_bn_train_fwd(st, w.Z[m], BK, R, w.mean[m], w.var[m], rm[m], rv[m], run->bn_momentum, bg[m], bb[m], fm,
+            const int rc = xgk_bn_train_fwd(st, w.Z[m], BK, R, w.mean[m], w.var[m], e.rm, e.rv, run->bn_momentum, e.bg, e.bb, fm,
                                             w.Xe[m], POS_BN_EPS, drop);
             if (rc == 1) {
-                XG_TRY(xgk_bn_stats(st, w.Z[m], BK, R, w.mean[m], w.var[m], rm[m], rv[m], run->bn_momentum));
-                XG_TRY(xgk_bn_apply(st, w.Z[m], w.mean[m], w.var[m], bg[m], bb[m], fm, w.Xe[m], BK, R, POS_BN_EPS, drop));
+                XG_TRY(xgk_bn_stats(st, w.Z[m], BK, R, w.mean[m], w.var[m], e.rm, e.rv, run->bn_momentum));
+                XG_TRY(xgk_bn_apply(st, w.Z[m], w.mean[m], w.var[m], e.bg, e.bb, fm, w.Xe[m], BK, R, POS_BN_EPS, drop));
             } else if (rc != XG_OK) {
                 return rc;
             }
         } else {
-            if (hipMemcpyAsync(w.mean[m], rm[m], sizeof(float) * R, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
-            if (hipMemcpyAsync(w.var[m], rv[m], sizeof(float) * R, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
-            XG_TRY(xgk_bn_apply(st, w.Z[m], w.mean[m], w.var[m], bg[m], bb[m], fm, w.Xe[m], BK, R, POS_BN_EPS, drop));
+            if (hipMemcpyAsync(w.mean[m], e.rm, sizeof(float) * R, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+            if (hipMemcpyAsync(w.var[m], e.rv, sizeof(float) * R, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+            XG_TRY(xgk_bn_apply(st, w.Z[m], w.mean[m], w.var[m], e.bg, e.bb, fm, w.Xe[m], BK, R, POS_BN_EPS, drop));
         }
-        XG_TRY(product(st, BK, 4 * R, w.Xe[m], R, wih[m], R, nullptr, 0, nullptr, 0, bih[m], w.Pre[m], 4 * R));
+        XG_TRY(product(st, BK, 4 * R, w.Xe[m], R, e.wih, R, nullptr, 0, nullptr, 0, e.bih, w.Pre[m], 4 * R));
+        e.pre = w.Pre[m]; e.c0 = w.zero; e.cs = w.Cs[m]; e.gates = w.G[m];     // the backward reads every frame's state and gates
     }
     XG_TRY(xgk_fill(st, w.zero, 0.f, (int64_t)B * R));
-    for (int k = 0; k < K; ++k) {
-        for (int m = 0; m < 2; ++m) {
-            const float* hp = k == 0 ? w.zero : w.Hcat + (size_t)(k - 1) * 2 * R + m * R;
-            float* S = w.S2 + (size_t)m * B * 4 * R;
-            XG_TRY(product(st, B, 4 * R, hp, k == 0 ? R : K * 2 * R, whh[m], R, nullptr, 0, nullptr, 0, bhh[m], S, 4 * R));
-            LstmFwdArgs a{};
-            a.s = S; a.lds_ = 4 * R;
-            a.add = w.Pre[m] + (size_t)k * 4 * R; a.ldadd = K * 4 * R;
-            a.c_prev = k == 0 ? w.zero : w.Cs[m] + (size_t)(k - 1) * R; a.ldcp = k == 0 ? R : K * R;
-            a.h_prev = nullptr; a.ldhp = 0;
-            a.mask = fm + k; a.ldm = K;
-            a.gates = w.G[m] + (size_t)k * 4 * R; a.ldg = K * 4 * R;
-            a.c_out = w.Cs[m] + (size_t)k * R; a.ldco = K * R;
-            a.h_out = w.Hcat + (size_t)k * 2 * R + m * R; a.ldho = K * 2 * R;
-            a.B = B; a.R = R; a.order = XG_ORDER_IFGO; a.mask_mode = XG_MASK_ZERO;
-            a.drop = pos_drop(&nd, 0, 0);
-            XG_TRY(xgk_lstm_fwd(st, a));
-        }
-    }
+    XG_TRY(encoder_recur(st, d, mo, fm, w.zero, w.S2, w.Hcat, R, K * R, pos_drop(&nd, 0, 0)));
     // late fusion: dropout(relu(W [h_rgb ; h_opfl] + b)) (sub_modules.py:63-66)
     XG_TRY(product(st, BK, R, w.Hcat, 2 * R, p->fusion_w, 2 * R, nullptr, 0, nullptr, 0, p->fusion_b, w.V, R, true));
     return xgk_relu_drop_fwd(st, w.V, (int64_t)BK * R, pos_drop(run, XG_SITE_FUSION, 0));
@@ -968,19 +975,9 @@ int forward_train(hipStream_t st, const XgpDims* d, const XgpParams* p, const Xg
 int encoder_bwd(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgpParams* g, const XgptRun* run, const float* fr,
                 const float* fo, const float* fm, const TWs& w) {
     const int B = d->B, K = d->K, R = d->R, BK = B * K;
-    const float* feats[2] = {fr, fo};
-    const int F[2] = {d->F1, d->F2};
-    const float* wih[2] = {p->lstm_rgb_wih, p->lstm_opfl_wih};
-    const float* whh[2] = {p->lstm_rgb_whh, p->lstm_opfl_whh};
-    const float* bg[2] = {p->bn_rgb_g, p->bn_opfl_g};
-    float* g_wih[2] = {g->lstm_rgb_wih, g->lstm_opfl_wih};
-    float* g_whh[2] = {g->lstm_rgb_whh, g->lstm_opfl_whh};
-    float* g_bih[2] = {g->lstm_rgb_bih, g->lstm_opfl_bih};
-    float* g_bhh[2] = {g->lstm_rgb_bhh, g->lstm_opfl_bhh};
-    float* g_bg[2] = {g->bn_rgb_g, g->bn_opfl_g};
-    float* g_bb[2] = {g->bn_rgb_b, g->bn_opfl_b};
-    float* g_ew[2] = {g->emb_rgb_w, g->emb_opfl_w};
-    float* g_eb[2] = {g->emb_rgb_b, g->emb_opfl_b};
+    EncMod mo[2], gm[2];         // the parameters, and where their gradients go
+    enc_mods(d, p, nullptr, fr, fo, mo);
+    enc_mods(d, g, nullptr, nullptr, nullptr, gm);
     XgptRun nd = *run;
     nd.drop_p = 0.f;
     // fusion: dVw = dV keep (V > 0), then its weight gradient and dHcat
@@ -1013,23 +1010,23 @@ int encoder_bwd(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgpP
         c ^= 1;
         if (i > 0)
             for (int m = 0; m < 2; ++m)
-                XG_TRY(product_nn(st, B, R, w.dHrec[m], R, false, w.dS[m] + (size_t)i * 4 * R, K * 4 * R, whh[m], 4 * R, nullptr));
+                XG_TRY(product_nn(st, B, R, w.dHrec[m], R, false, w.dS[m] + (size_t)i * 4 * R, K * 4 * R, mo[m].whh, 4 * R, nullptr));
     }
     for (int m = 0; m < 2; ++m) {
         const int64_t n = (int64_t)BK * R;
         hipLaunchKernelGGL(pos_shift_h_kernel, dim3((unsigned)xg_cdiv64(n, POS_TPB)), dim3(POS_TPB), 0, st, w.Hcat, m, K, R, n, w.Hprev);
         XG_CHECK_LAUNCH();
-        XG_TRY(wgrad(st, BK, 4 * R, R, w.dS[m], 4 * R, w.Hprev, R, g_whh[m], g_bih[m], g_bhh[m]));
-        XG_TRY(wgrad(st, BK, 4 * R, R, w.dS[m], 4 * R, w.Xe[m], R, g_wih[m], nullptr));
-        XG_TRY(dgrad(st, BK, R, 4 * R, w.dS[m], 4 * R, wih[m], w.dX, R, false));
+        XG_TRY(wgrad(st, BK, 4 * R, R, w.dS[m], 4 * R, w.Hprev, R, gm[m].whh, gm[m].bih, gm[m].bhh));
+        XG_TRY(wgrad(st, BK, 4 * R, R, w.dS[m], 4 * R, w.Xe[m], R, gm[m].wih, nullptr));
+        XG_TRY(dgrad(st, BK, R, 4 * R, w.dS[m], 4 * R, mo[m].wih, w.dX, R, false));
         // BatchNorm + ReLU + dropout + frame mask backward (sub_modules.py:121-123, :204)
         XG_TRY(xgk_fill(st, w.bn_s1, 0.f, R));
         XG_TRY(xgk_fill(st, w.bn_s2, 0.f, R));
         XG_TRY(xgk_bn_bwd_reduce(st, w.dX, w.Xe[m], w.Z[m], w.mean[m], w.var[m], fm, BK, R, POS_BN_EPS,
-                                 pos_drop(run, m == 0 ? XG_SITE_EMB_RGB : XG_SITE_EMB_OPFL, 0), w.bn_s1, w.bn_s2));
-        XG_TRY(xgk_bn_bwd_apply(st, w.dX, w.Z[m], w.mean[m], w.var[m], bg[m], w.bn_s1, w.bn_s2, BK, R, POS_BN_EPS, run->train != 0,
-                                g_bb[m], g_bg[m]));
-        XG_TRY(wgrad(st, BK, R, F[m], w.dX, R, feats[m], F[m], g_ew[m], g_eb[m]));
+                                 pos_drop(run, mo[m].site, 0), w.bn_s1, w.bn_s2));
+        XG_TRY(xgk_bn_bwd_apply(st, w.dX, w.Z[m], w.mean[m], w.var[m], mo[m].bg, w.bn_s1, w.bn_s2, BK, R, POS_BN_EPS, run->train != 0,
+                                gm[m].bb, gm[m].bg));
+        XG_TRY(wgrad(st, BK, R, mo[m].F, w.dX, R, mo[m].feats, mo[m].F, gm[m].ew, gm[m].eb));
     }
     return XG_OK;
 }
@@ -1107,10 +1104,8 @@ extern "C" size_t xgpt_workspace_bytes(const XgpDims* d) {
 extern "C" int xgpt_forward_train(void* stream, const XgpDims* d, const XgpParams* p, const XgBnState* bn, const XgptRun* run,
                                   const float* feats_rgb, const float* feats_opfl, const float* feat_mask, const int64_t* cap_classes,
                                   const float* new_mask, float* logp, int32_t* t_out, void* ws, size_t ws_bytes) {
-    if (!dims_ok(d, true) || !tk_ok(d->T, d->K) || !params_ok(p) || !bn_ok(bn) || !run_ok(run) || !feats_rgb || !feats_opfl ||
-        !feat_mask || !cap_classes || !new_mask || !logp || !t_out || !ws)
-        return XG_EINVAL;
-    if (ws_bytes < tws_layout(d, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
+    if (!dims_ok(d, true) || !tk_ok(d->T, d->K) || !run_ok(run) || !cap_classes || !new_mask || !logp || !t_out) return XG_EINVAL;
+    XG_TRY(args_gate(p, bn_ok(bn), feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, tws_layout(d, nullptr).floats));
     hipStream_t st = (hipStream_t)stream;
     XG_TRY(forward_train(st, d, p, bn, run, feats_rgb, feats_opfl, feat_mask, cap_classes, new_mask, logp, tws_layout(d, ws)));
     hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, cap_classes, nullptr, d->B, d->T, 0, t_out);
@@ -1121,10 +1116,8 @@ extern "C" int xgpt_forward_train(void* stream, const XgpDims* d, const XgpParam
 extern "C" int xgpt_backward(void* stream, const XgpDims* d, const XgpParams* p, const XgpParams* g, const XgptRun* run,
                              const float* feats_rgb, const float* feats_opfl, const float* feat_mask, int32_t Tp, const float* dlogp,
                              void* ws, size_t ws_bytes) {
-    if (!dims_ok(d, true) || !params_ok(p) || !params_ok(g) || !run_ok(run) || !feats_rgb || !feats_opfl || !feat_mask || !dlogp ||
-        !ws || Tp < 1 || Tp > d->T || !tk_ok(Tp, d->K))
-        return XG_EINVAL;
-    if (ws_bytes < tws_layout(d, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
+    if (!dims_ok(d, true) || !params_ok(g) || !run_ok(run) || !dlogp || Tp < 1 || Tp > d->T || !tk_ok(Tp, d->K)) return XG_EINVAL;
+    XG_TRY(args_gate(p, true, feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, tws_layout(d, nullptr).floats));   // (no running statistics)
     return backward((hipStream_t)stream, d, p, g, run, feats_rgb, feats_opfl, feat_mask, Tp, dlogp, tws_layout(d, ws));
 }
 
@@ -1412,19 +1405,17 @@ CWs cws_layout(const XgpDims* d, int S, void* base) {
     CWs w;
     w.v = ws_layout(d, base);
     const size_t M = (size_t)d->B * S, R = d->R, A = d->A;
-    float* p = (float*)base;
-    size_t off = w.v.floats;
-    auto take = [&](size_t n) { float* r = p ? p + off : nullptr; off += (n + 63) / 64 * 64; return r; };
-    w.X = take(M * 2 * R);           // [af ; h] of every row
-    w.P = take(M * A);
-    w.S = take(M * 4 * R);
-    w.c = take(M * R);
-    w.floats = off;
+    Carve cv{(float*)base, w.v.floats};
+    w.X = cv.take(M * 2 * R);           // [af ; h] of every row
+    w.P = cv.take(M * A);
+    w.S = cv.take(M * 4 * R);
+    w.c = cv.take(M * R);
+    w.floats = cv.off;
     return w;
 }
 
 // LDS floats of pos_attn_group_kernel<G>: the p-vectors / context parts, w, the scores
-// (restated as group_lds in tests/test_gpu_pos_control.py, with the 64 KiB limit of rollout_rows below, to name the cases that take
+// (restated as group_lds in tests/test_gpu_pos_control.py, with the 64 KiB limit of step_plan below, to name the cases that take
 // the one-template form: change them together)
 size_t attn_group_lds(int G, int K, int R, int A, int nsplit, int* pr_floats) {
     const size_t pr = ((size_t)G * (A > nsplit * R ? A : nsplit * R) + 3) / 4 * 4;
@@ -1439,42 +1430,68 @@ bool ctrl_dims_ok(const XgpDims* d, int S) {
     return M * 4 * 4096 < (1LL << 31) && M * d->T * d->R < (1LL << 31);
 }
 
+StepPlan step_plan(const XgpDims* d, int S) {
+    const int K = d->K, R = d->R, A = d->A;
+    StepPlan pl{};
+    pl.S = S;
+    pl.v4 = A % 4 == 0;
+    // the context parts of pos_attn_kernel / pos_attn_group_kernel: as many as fill the workgroup, at most one per frame
+    pl.nsplit = STEP_TPB / R < 1 ? 1 : (STEP_TPB / R > K ? K : STEP_TPB / R);
+    if (S == 1) {                // pos_attn_kernel itself: what makes a one-row call bit-identical to the greedy one
+        pl.lds = (size_t)(2 * A + K + pl.nsplit * R) * sizeof(float);
+        return pl;
+    }
+    // the full group while it fits the 64 KiB of LDS a workgroup gets without opting in; else (A or R near 4096) one template
+    pl.G = CTRL_G;
+    pl.lds = attn_group_lds(CTRL_G, K, R, A, pl.nsplit, &pl.pr_floats);
+    if (pl.lds > 64 * 1024) {
+        pl.G = 1;
+        pl.lds = attn_group_lds(1, K, R, A, pl.nsplit, &pl.pr_floats);
+    }
+    return pl;
+}
+
 template <int G>
-void launch_attn_group(hipStream_t st, int B, int S, bool v4, size_t lds, const float* P, const float* Q, const float* V,
-                       const float* w, float* X, int K, int R, int A, int nsplit, int pr_floats) {
-    const dim3 grid(B * xg_cdiv(S, G));
-    if (v4) hipLaunchKernelGGL((pos_attn_group_kernel<G, true>), grid, dim3(STEP_TPB), lds, st, P, Q, V, w, X, K, R, A, S, nsplit, pr_floats);
-    else    hipLaunchKernelGGL((pos_attn_group_kernel<G, false>), grid, dim3(STEP_TPB), lds, st, P, Q, V, w, X, K, R, A, S, nsplit, pr_floats);
+void launch_attn_group(hipStream_t st, int B, const StepPlan& pl, const float* P, const float* Q, const float* V, const float* w,
+                       float* X, int K, int R, int A) {
+    const dim3 grid(B * xg_cdiv(pl.S, G)), tpb(STEP_TPB);
+    if (pl.v4) hipLaunchKernelGGL((pos_attn_group_kernel<G, true>), grid, tpb, pl.lds, st, P, Q, V, w, X, K, R, A, pl.S, pl.nsplit, pl.pr_floats);
+    else       hipLaunchKernelGGL((pos_attn_group_kernel<G, false>), grid, tpb, pl.lds, st, P, Q, V, w, X, K, R, A, pl.S, pl.nsplit, pl.pr_floats);
+}
+
+int step_front(hipStream_t st, const XgpDims* d, const XgpParams* p, const StepPlan& pl, const Ws& v, float* X, float* P, float* S) {
+    const int B = d->B, K = d->K, R = d->R, A = d->A, M = B * pl.S;
+    const float* w = p->a2w_w;
+    XG_TRY(product(st, M, A, X + R, 2 * R, p->h2a_w, R, nullptr, 0, nullptr, 0, p->h2a_b, P, A, false, v.pk_h2a));
+    if (pl.G == CTRL_G) launch_attn_group<CTRL_G>(st, B, pl, P, v.Q, v.V, w, X, K, R, A);
+    else if (pl.G == 1) launch_attn_group<1>(st, B, pl, P, v.Q, v.V, w, X, K, R, A);
+    else launch_attn(st, B, pl, P, v.Q, v.V, w, X, K, R, A);
+    XG_CHECK_LAUNCH();
+    return product(st, M, 4 * R, X, 2 * R, p->a2h_w, R, X + R, 2 * R, p->h2h_w, R, nullptr, S, 4 * R, false, v.pk_a2h, v.pk_h2h);
+}
+
+// the prologue over the B videos, then each video's initial h and c copied to its S rows
+int rows_prologue(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
+                  const float* fm, const CWs& w) {
+    XG_TRY(prologue(st, d, p, bn, fr, fo, fm, w.v));
+    const int64_t n = (int64_t)d->B * S * d->R;
+    hipLaunchKernelGGL(pos_bcast_state_kernel, dim3((unsigned)xg_cdiv(n, POS_TPB)), dim3(POS_TPB), 0, st, w.v.X, w.v.c, w.X, w.c, S, d->R, n);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
 }
 
 // the rollout over the M = B S rows (fa: the caller's operands; the workspace's and the step are filled in here), then n_out from
 // the masks.  `draw` picks pos_cell_head_rows_kernel<true>, which needs C more floats of LDS for the weights of its serial head.
 int rollout_rows(hipStream_t st, const XgpDims* d, int S, const XgpParams* p, const XgBnState* bn, const float* fr, const float* fo,
                  const float* fm, RowsArgs fa, bool draw, int32_t* n_out, const CWs& w) {
-    const int B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, T = d->T, M = B * S;
-    XG_TRY(prologue(st, d, p, bn, fr, fo, fm, w.v));
-    const int64_t n = (int64_t)M * R;
-    hipLaunchKernelGGL(pos_bcast_state_kernel, dim3((unsigned)xg_cdiv(n, POS_TPB)), dim3(POS_TPB), 0, st, w.v.X, w.v.c, w.X, w.c, S, R, n);
-    XG_CHECK_LAUNCH();
+    const int R = d->R, C = d->C, T = d->T, M = d->B * S;
+    XG_TRY(rows_prologue(st, d, S, p, bn, fr, fo, fm, w));
     fa.S = w.S; fa.tab = w.v.tab; fa.logit_w = p->logit_w; fa.logit_b = p->logit_b;
     fa.X = w.X; fa.c = w.c; fa.R = R; fa.C = C; fa.T = T;
     const size_t lds_cell = (size_t)(R + (draw ? 2 : 1) * C) * sizeof(float);
-    const int nsplit = attn_nsplit(K, R);
-    // the full group while its p-vectors fit the 64 KiB of LDS a workgroup gets without opting in; beyond that (A or R near
-    // 4096) one template per workgroup
-    int pr_floats = 0;
-    size_t lds_group = attn_group_lds(CTRL_G, K, R, A, nsplit, &pr_floats);
-    const bool full = lds_group <= 64 * 1024;
-    if (!full) lds_group = attn_group_lds(1, K, R, A, nsplit, &pr_floats);
-    const bool v4 = A % 4 == 0;
+    const StepPlan pl = step_plan(d, S);
     for (int t = 0; t < T; ++t) {
-        XG_TRY(product(st, M, A, w.X + R, 2 * R, p->h2a_w, R, nullptr, 0, nullptr, 0, p->h2a_b, w.P, A, false, w.v.pk_h2a));
-        if (S == 1) launch_attn(st, B, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A);
-        else if (full) launch_attn_group<CTRL_G>(st, B, S, v4, lds_group, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit, pr_floats);
-        else launch_attn_group<1>(st, B, S, v4, lds_group, w.P, w.v.Q, w.v.V, p->a2w_w, w.X, K, R, A, nsplit, pr_floats);
-        XG_CHECK_LAUNCH();
-        XG_TRY(product(st, M, 4 * R, w.X, 2 * R, p->a2h_w, R, w.X + R, 2 * R, p->h2h_w, R, nullptr, w.S, 4 * R, false, w.v.pk_a2h,
-                       w.v.pk_h2h));
+        XG_TRY(step_front(st, d, p, pl, w.v, w.X, w.P, w.S));
         fa.t = t;
         if (draw) hipLaunchKernelGGL(pos_cell_head_rows_kernel<true>, dim3(M), dim3(STEP_TPB), lds_cell, st, fa);
         else      hipLaunchKernelGGL(pos_cell_head_rows_kernel<false>, dim3(M), dim3(STEP_TPB), lds_cell, st, fa);
@@ -1498,10 +1515,8 @@ extern "C" int xgpc_sample_forced(void* stream, const XgpDims* d, int32_t S, con
                                   const float* feats_rgb, const float* feats_opfl, const float* feat_mask, const int64_t* templates,
                                   float* tag_logp, float* states, float* masks, float* pos_feats, int32_t* n_out, void* ws,
                                   size_t ws_bytes) {
-    if (!ctrl_dims_ok(d, S) || !params_ok(p) || !bn_ok(bn) || !feats_rgb || !feats_opfl || !feat_mask || !templates || !tag_logp ||
-        !masks || !pos_feats || !n_out || !ws)
-        return XG_EINVAL;
-    if (ws_bytes < cws_layout(d, S, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
+    if (!ctrl_dims_ok(d, S) || !templates || !tag_logp || !masks || !pos_feats || !n_out) return XG_EINVAL;
+    XG_TRY(args_gate(p, bn_ok(bn), feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, cws_layout(d, S, nullptr).floats));
     RowsArgs fa{};
     fa.tmpl = templates; fa.tag_logp = tag_logp; fa.states = states; fa.masks = masks; fa.pos_feats = pos_feats;
     return rollout_rows((hipStream_t)stream, d, S, p, bn, feats_rgb, feats_opfl, feat_mask, fa, false, n_out, cws_layout(d, S, ws));
@@ -1522,10 +1537,10 @@ extern "C" int xgps_sample_templates(void* stream, const XgpDims* d, int32_t S, 
                                      const XgBnState* bn, const float* feats_rgb, const float* feats_opfl, const float* feat_mask,
                                      const float* uniforms, int64_t* templates, float* tag_logp, float* states, float* masks,
                                      float* pos_feats, int32_t* n_out, void* ws, size_t ws_bytes) {
-    if (!ctrl_dims_ok(d, S) || !(temperature > 0.0f) || temperature == INFINITY || !params_ok(p) || !bn_ok(bn) || !feats_rgb ||
-        !feats_opfl || !feat_mask || !uniforms || !templates || !tag_logp || !masks || !pos_feats || !n_out || !ws)
+    if (!ctrl_dims_ok(d, S) || !(temperature > 0.0f) || temperature == INFINITY || !uniforms || !templates || !tag_logp || !masks ||
+        !pos_feats || !n_out)
         return XG_EINVAL;
-    if (ws_bytes < cws_layout(d, S, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
+    XG_TRY(args_gate(p, bn_ok(bn), feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, cws_layout(d, S, nullptr).floats));
     RowsArgs sa{};
     sa.tmpl = templates; sa.tag_logp = tag_logp; sa.states = states; sa.masks = masks; sa.pos_feats = pos_feats;
     sa.tmpl_out = templates; sa.uniforms = uniforms; sa.temperature = temperature;
@@ -1534,8 +1549,8 @@ extern "C" int xgps_sample_templates(void* stream, const XgpDims* d, int32_t S, 
 
 // ==================================================================================================================================
 // Beam templates (include/xgate_pos_beam.h): the beam search of pos_src/SAModel.py:104-134 / pos_src/CaptionModel.py:22-125, W slots
-// for each of B videos, rows b W + slot.  The prologue, the copy of the initial state and the first three launches of the step are
-// those of rollout_rows over the M = B W rows (a video's W beams are one attention group).  The fourth launch is
+// for each of B videos, rows b W + slot.  The prologue with the copy of the initial state (rows_prologue) and the first three launches
+// of the step (step_front) are rollout_rows' own, over the M = B W rows (a video's W beams are one attention group).  The fourth launch is
 // pos_beam_merge_kernel, ONE workgroup per video: the C-way head is small enough that the whole merge of a video (W rows of C
 // log-probabilities, W * W candidates) fits in one workgroup, so no step needs the host.
 //   1. pos_cell of all W rows into LDS (mask 1: dead slots keep running, as the reference's get_logprobs_state does); every c and h
@@ -1748,17 +1763,15 @@ BWs bws_layout(const XgpDims* d, int W, void* base) {
     BWs w;
     w.c = cws_layout(d, W, base);
     const size_t B = d->B, M = B * W, L = d->T - 1;
-    float* p = (float*)base;
-    size_t off = w.c.floats;
-    auto take = [&](size_t n) { float* r = p ? p + off : nullptr; off += (n + 63) / 64 * 64; return r; };
-    w.sum = take(M);
-    w.tok = (int32_t*)take(M);
-    w.trace = (int32_t*)take(B * L * W * 2);
-    w.r = take(B * L * W);
-    w.done_score = take(M);
-    w.done_at = (int32_t*)take(M * 2);
-    w.done_n = (int32_t*)take(B);
-    w.floats = off;
+    Carve cv{(float*)base, w.c.floats};
+    w.sum = cv.take(M);
+    w.tok = (int32_t*)cv.take(M);
+    w.trace = (int32_t*)cv.take(B * L * W * 2);
+    w.r = cv.take(B * L * W);
+    w.done_score = cv.take(M);
+    w.done_at = (int32_t*)cv.take(M * 2);
+    w.done_n = (int32_t*)cv.take(B);
+    w.floats = cv.off;
     return w;
 }
 
@@ -1781,39 +1794,21 @@ extern "C" int xgpb_beam_templates(void* stream, const XgpDims* d, int32_t W, in
                                    const XgBnState* bn, const float* feats_rgb, const float* feats_opfl, const float* feat_mask,
                                    int64_t* templates, float* tag_logp, float* score, float* masks, int32_t* n_out, int32_t* trace,
                                    void* ws, size_t ws_bytes) {
-    if (!beam_dims_ok(d, W, suppress_tag) || !params_ok(p) || !bn_ok(bn) || !feats_rgb || !feats_opfl || !feat_mask || !templates ||
-        !tag_logp || !score || !masks || !n_out || !ws)
-        return XG_EINVAL;
-    if (ws_bytes < bws_layout(d, W, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
+    if (!beam_dims_ok(d, W, suppress_tag) || !templates || !tag_logp || !score || !masks || !n_out) return XG_EINVAL;
+    XG_TRY(args_gate(p, bn_ok(bn), feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, bws_layout(d, W, nullptr).floats));
     hipStream_t st = (hipStream_t)stream;
     const BWs w = bws_layout(d, W, ws);
-    const int B = d->B, K = d->K, R = d->R, A = d->A, C = d->C, L = d->T - 1, M = B * W;
-    XG_TRY(prologue(st, d, p, bn, feats_rgb, feats_opfl, feat_mask, w.c.v));
-    const int64_t n = (int64_t)M * R;
-    hipLaunchKernelGGL(pos_bcast_state_kernel, dim3((unsigned)xg_cdiv(n, POS_TPB)), dim3(POS_TPB), 0, st, w.c.v.X, w.c.v.c, w.c.X, w.c.c, W,
-                       R, n);
-    XG_CHECK_LAUNCH();
+    const int B = d->B, R = d->R, C = d->C, L = d->T - 1, M = B * W;
+    XG_TRY(rows_prologue(st, d, W, p, bn, feats_rgb, feats_opfl, feat_mask, w.c));
     BeamArgs a{};
     a.S = w.c.S; a.tab = w.c.v.tab; a.logit_w = p->logit_w; a.logit_b = p->logit_b; a.X = w.c.X; a.c = w.c.c;
     a.sum = w.sum; a.tok = w.tok; a.trace = w.trace; a.r = w.r; a.trace_out = trace;
     a.done_score = w.done_score; a.done_at = w.done_at; a.done_n = w.done_n;
     a.R = R; a.C = C; a.L = L; a.W = W; a.suppress = suppress_tag < 0 ? -1 : suppress_tag;
     const size_t lds_merge = XGPB_LDS_BYTES(W, R, C) - 1024;
-    // the attention of rollout_rows at S = W
-    const int nsplit = attn_nsplit(K, R);
-    int pr_floats = 0;
-    size_t lds_group = attn_group_lds(CTRL_G, K, R, A, nsplit, &pr_floats);
-    const bool full = lds_group <= 64 * 1024;
-    if (!full) lds_group = attn_group_lds(1, K, R, A, nsplit, &pr_floats);
-    const bool v4 = A % 4 == 0;
+    const StepPlan pl = step_plan(d, W);         // (a video's W beams are one attention group)
     for (int t = 0; t < L; ++t) {
-        XG_TRY(product(st, M, A, w.c.X + R, 2 * R, p->h2a_w, R, nullptr, 0, nullptr, 0, p->h2a_b, w.c.P, A, false, w.c.v.pk_h2a));
-        if (W == 1) launch_attn(st, B, w.c.P, w.c.v.Q, w.c.v.V, p->a2w_w, w.c.X, K, R, A);
-        else if (full) launch_attn_group<CTRL_G>(st, B, W, v4, lds_group, w.c.P, w.c.v.Q, w.c.v.V, p->a2w_w, w.c.X, K, R, A, nsplit, pr_floats);
-        else launch_attn_group<1>(st, B, W, v4, lds_group, w.c.P, w.c.v.Q, w.c.v.V, p->a2w_w, w.c.X, K, R, A, nsplit, pr_floats);
-        XG_CHECK_LAUNCH();
-        XG_TRY(product(st, M, 4 * R, w.c.X, 2 * R, p->a2h_w, R, w.c.X + R, 2 * R, p->h2h_w, R, nullptr, w.c.S, 4 * R, false,
-                       w.c.v.pk_a2h, w.c.v.pk_h2h));
+        XG_TRY(step_front(st, d, p, pl, w.c.v, w.c.X, w.c.P, w.c.S));
         a.t = t;
         hipLaunchKernelGGL(pos_beam_merge_kernel, dim3(B), dim3(STEP_TPB), lds_merge, st, a);
         XG_CHECK_LAUNCH();

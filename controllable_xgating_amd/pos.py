@@ -199,16 +199,11 @@ class PosModel(nn.Module):
         return self._tws
 
     def _params(self):
-        L = npos.lib()
-        named = dict(self.named_parameters())
-        ptrs = []
-        for n in npos.PARAM_NAMES:
-            p = named[n]
+        plist = self._plist()
+        for n, p in zip(npos.PARAM_NAMES, plist):
             if not p.is_contiguous():
                 raise nv.XgError("parameter %s is not contiguous" % n)
-            ptrs.append(p.data_ptr())
-        assert L is not None
-        return npos.XgpParams(*ptrs)
+        return npos.XgpParams(*[p.data_ptr() for p in plist])
 
     def _bn(self):
         e = self.two_fc_encoder
@@ -238,6 +233,32 @@ class PosModel(nn.Module):
         if f[0].dim() != 3 or f[1].shape[:2] != f[0].shape[:2] or tuple(f[2].shape) != tuple(f[0].shape[:2]):
             raise nv.XgError("feats_rgb (B,K,F1), feats_opfl (B,K,F2), feat_mask (B,K) expected")
         return f
+
+    def _rows_feats(self, feats_rgb, feats_opfl, feat_mask):
+        """The opening of the rows calls (sample_forced / sample_templates / beam_templates): (fr, fo, fm, B, K)."""
+        self._check_eval(feats_rgb, feats_opfl, feat_mask)
+        fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
+        return (fr, fo, fm) + tuple(fm.shape)
+
+    def _rows_setup(self, workspace_bytes, B, K, rows, dev, invalid):
+        """What every rows call passes to the library: (dims for seq_length + 1 steps, params, bn, the shared workspace grown to
+        `workspace_bytes(dims, rows)`, n_out).  `invalid`: the error text when the library refuses the dims."""
+        dims = self._dims(B, K, self.seq_length + 1)
+        nbytes = workspace_bytes(C.byref(dims), rows)
+        if nbytes == 0:
+            raise nv.XgError(invalid)
+        if self._cws is None or self._cws.device != dev or self._cws.numel() < nbytes:
+            self._cws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return dims, self._params(), self._bn(), self._cws, torch.empty(1, dtype=torch.int32, device=dev)
+
+    @staticmethod
+    def _rows_trim(trim, n_out, by_tag, by_step):
+        """`by_tag` (B,S,L) cut to n and `by_step` (B,S,L+1,...) to n + 1 (None stays None) when `trim`: the reference's n, one
+        host synchronisation."""
+        if not trim:
+            return by_tag, by_step
+        n = int(n_out.item())                       # the one host synchronisation of the call
+        return [t[:, :, :n] for t in by_tag], [None if t is None else t[:, :, :n + 1] for t in by_step]
 
     # ---- the reference's surface
     def init_hidden(self, feat, feat_mask):
@@ -301,8 +322,8 @@ class PosModel(nn.Module):
         seq_length + 1 steps run on the device (finished rows hold their state exactly), then the outputs are trimmed to the
         reference's n."""
         if opt.get("beam_size", 1) > 1:
-            raise NotImplementedError("POS beam search is not implemented (the reference's extraction runs --beam_size 1: "
-                                      "its sample_beam returns 2 values where eval_utils.py unpacks 4)")
+            raise NotImplementedError("sample() is the greedy rollout only: POS beam search is beam_templates (the reference's "
+                                      "extraction runs --beam_size 1: its sample_beam returns 2 values where eval_utils.py unpacks 4)")
         if not opt.get("sample_max", 1):
             raise NotImplementedError("sampled POS rollouts (sample_max = 0) are not implemented (nor are they in the reference)")
         self._check_eval(feats_rgb, feats_opfl, feat_mask)
@@ -337,37 +358,26 @@ class PosModel(nn.Module):
         skips storing the states."""
         from . import _native_pos_control as npc
         from .control import pad_templates
-        self._check_eval(feats_rgb, feats_opfl, feat_mask)
-        fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
-        B, K = fm.shape
+        fr, fo, fm, B, K = self._rows_feats(feats_rgb, feats_opfl, feat_mask)
         L = self.seq_length
         dev = fr.device
         tm = pad_templates(templates, L, self.category_size).to(dev)
         if tm.shape[0] != B:
             raise ValueError("templates for %d videos, features for %d" % (tm.shape[0], B))
         S = tm.shape[1]
-        dims = self._dims(B, K, L + 1)
         lib = npc.lib()
-        nbytes = lib.xgpc_workspace_bytes(C.byref(dims), S)
-        if nbytes == 0:
-            raise nv.XgError("xgpc_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S))
-        ws = self._cws
-        if ws is None or ws.device != dev or ws.numel() < nbytes:
-            ws = self._cws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        dims, P, bn, ws, n_out = self._rows_setup(lib.xgpc_workspace_bytes, B, K, S, dev,
+                                                  "xgpc_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S))
         tag_logp = torch.empty(B, S, L, device=dev)
         states = torch.empty(B, S, L + 1, self.rnn_size, device=dev) if collect_states else None
         masks = torch.empty(B, S, L + 1, device=dev)
         pos_feats = torch.empty(B * S, self.rnn_size, device=dev)
-        n_out = torch.empty(1, dtype=torch.int32, device=dev)
-        P, bn = self._params(), self._bn()
         nv.check(lib.xgpc_sample_forced(_stream(), C.byref(dims), S, C.byref(P), C.byref(bn), fr.data_ptr(), fo.data_ptr(),
                                         fm.data_ptr(), tm.data_ptr(), tag_logp.data_ptr(),
                                         None if states is None else states.data_ptr(), masks.data_ptr(), pos_feats.data_ptr(),
                                         n_out.data_ptr(), ws.data_ptr(), ws.numel()), "xgpc_sample_forced")
-        if not trim:
-            return tag_logp, states, masks, pos_feats
-        n = int(n_out.item())                       # the one host synchronisation of the call
-        return tag_logp[:, :, :n], None if states is None else states[:, :, :n + 1], masks[:, :, :n + 1], pos_feats
+        (tag_logp,), (states, masks) = self._rows_trim(trim, n_out, (tag_logp,), (states, masks))
+        return tag_logp, states, masks, pos_feats
 
     def sample_templates(self, feats_rgb, feats_opfl, feat_mask, S, temperature=1.0, uniforms=None, generator=None,
                          collect_states=False, trim=True):
@@ -382,9 +392,7 @@ class PosModel(nn.Module):
         `trim`: cut to the reference's n (one host synchronisation); trim=False returns the full seq_length and does not
         synchronise."""
         from . import _native_pos_sample as nps
-        self._check_eval(feats_rgb, feats_opfl, feat_mask)
-        fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
-        B, K = fm.shape
+        fr, fo, fm, B, K = self._rows_feats(feats_rgb, feats_opfl, feat_mask)
         L = self.seq_length
         dev = fr.device
         S = int(S)
@@ -400,31 +408,20 @@ class PosModel(nn.Module):
             if u.dtype != torch.float32 or tuple(u.shape) != (B, S, L):
                 raise ValueError("uniforms: float32 (%d,%d,%d) expected, got %s %s" % (B, S, L, u.dtype, tuple(u.shape)))
             u = u.to(dev).contiguous()
-        dims = self._dims(B, K, L + 1)
         lib = nps.lib()
-        nbytes = lib.xgps_workspace_bytes(C.byref(dims), S)
-        if nbytes == 0:
-            raise nv.XgError("xgps_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S))
-        ws = self._cws
-        if ws is None or ws.device != dev or ws.numel() < nbytes:
-            ws = self._cws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        dims, P, bn, ws, n_out = self._rows_setup(lib.xgps_workspace_bytes, B, K, S, dev,
+                                                  "xgps_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S))
         templates = torch.empty(B, S, L, dtype=torch.int64, device=dev)
         tag_logp = torch.empty(B, S, L, device=dev)
         states = torch.empty(B, S, L + 1, self.rnn_size, device=dev) if collect_states else None
         masks = torch.empty(B, S, L + 1, device=dev)
         pos_feats = torch.empty(B * S, self.rnn_size, device=dev)
-        n_out = torch.empty(1, dtype=torch.int32, device=dev)
-        P, bn = self._params(), self._bn()
         nv.check(lib.xgps_sample_templates(_stream(), C.byref(dims), S, temperature, C.byref(P), C.byref(bn), fr.data_ptr(),
                                            fo.data_ptr(), fm.data_ptr(), u.data_ptr(), templates.data_ptr(), tag_logp.data_ptr(),
                                            None if states is None else states.data_ptr(), masks.data_ptr(), pos_feats.data_ptr(),
                                            n_out.data_ptr(), ws.data_ptr(), ws.numel()), "xgps_sample_templates")
-        if not trim:
-            return templates, tag_logp, states, masks, pos_feats
-        n = int(n_out.item())                       # the one host synchronisation of the call
-        return (templates[:, :, :n], tag_logp[:, :, :n], None if states is None else states[:, :, :n + 1], masks[:, :, :n + 1],
-                pos_feats)
-
+        (templates, tag_logp), (states, masks) = self._rows_trim(trim, n_out, (templates, tag_logp), (states, masks))
+        return templates, tag_logp, states, masks, pos_feats
 
     def beam_templates(self, feats_rgb, feats_opfl, feat_mask, beam_size=5, suppress_tag=1, trim=True, return_trace=False):
         """The W = beam_size templates the generator itself finds most likely for each of the B videos (include/xgate_pos_beam.h:
@@ -438,9 +435,7 @@ class PosModel(nn.Module):
         synchronisation); trim=False returns the full seq_length and does not synchronise.  `return_trace`: also the (token, parent
         slot) of every slot and step.  beam_size may not exceed category_size or 8."""
         from . import _native_pos_beam as npb
-        self._check_eval(feats_rgb, feats_opfl, feat_mask)
-        fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
-        B, K = fm.shape
+        fr, fo, fm, B, K = self._rows_feats(feats_rgb, feats_opfl, feat_mask)
         L = self.seq_length
         dev = fr.device
         W, sup = int(beam_size), int(suppress_tag)
@@ -448,29 +443,20 @@ class PosModel(nn.Module):
             raise ValueError("1 <= beam_size <= min(category_size = %d, %d) expected, got %d" % (self.category_size, npb.XGPB_MAX_BEAM, W))
         if sup >= self.category_size:
             raise ValueError("suppress_tag must lie below category_size = %d (-1: none), got %d" % (self.category_size, sup))
-        dims = self._dims(B, K, L + 1)
         lib = npb.lib()
-        nbytes = lib.xgpb_workspace_bytes(C.byref(dims), W)
-        if nbytes == 0:
-            raise nv.XgError("xgpb_workspace_bytes: invalid dims, too many rows (B %d, W %d) or W * rnn_size beyond the merge "
-                             "kernel's LDS" % (B, W))
-        ws = self._cws
-        if ws is None or ws.device != dev or ws.numel() < nbytes:
-            ws = self._cws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        dims, P, bn, ws, n_out = self._rows_setup(lib.xgpb_workspace_bytes, B, K, W, dev,
+                                                  "xgpb_workspace_bytes: invalid dims, too many rows (B %d, W %d) or W * rnn_size beyond "
+                                                  "the merge kernel's LDS" % (B, W))
         templates = torch.empty(B, W, L, dtype=torch.int64, device=dev)
         tag_logp = torch.empty(B, W, L, device=dev)
         score = torch.empty(B, W, device=dev)
         masks = torch.empty(B, W, L + 1, device=dev)
         trace = torch.empty(B, L, W, 2, dtype=torch.int32, device=dev) if return_trace else None
-        n_out = torch.empty(1, dtype=torch.int32, device=dev)
-        P, bn = self._params(), self._bn()
         nv.check(lib.xgpb_beam_templates(_stream(), C.byref(dims), W, sup, C.byref(P), C.byref(bn), fr.data_ptr(), fo.data_ptr(),
                                          fm.data_ptr(), templates.data_ptr(), tag_logp.data_ptr(), score.data_ptr(), masks.data_ptr(),
                                          n_out.data_ptr(), None if trace is None else trace.data_ptr(), ws.data_ptr(), ws.numel()),
                  "xgpb_beam_templates")
-        if trim:
-            n = int(n_out.item())                   # the one host synchronisation of the call
-            templates, tag_logp, masks = templates[:, :, :n], tag_logp[:, :, :n], masks[:, :, :n + 1]
+        (templates, tag_logp), (masks,) = self._rows_trim(trim, n_out, (templates, tag_logp), (masks,))
         out = (templates, tag_logp, score, masks)
         return out + (trace,) if return_trace else out
 

@@ -91,9 +91,9 @@ def branches(d, mode, Tp=None):
     if B > POS_TPB:                             # xg_pos.hip pos_first_zero_col_kernel: `for (b = threadIdx.x; b < B; b += POS_TPB)`
         out.add("6")
     if mode == "eval":
-        if A % 4:                               # xg_pos.hip launch_attn: `A % 4 == 0`
+        if A % 4:                               # xg_pos.hip step_plan: `A % 4 == 0`
             out.add("1")
-        nsplit = min(max(STEP_TPB // R, 1), K)  # xg_pos.hip attn_nsplit
+        nsplit = min(max(STEP_TPB // R, 1), K)  # xg_pos.hip step_plan: nsplit
         if not (nsplit * R <= STEP_TPB and _cdiv(K, nsplit) <= 16):     # pos_attn_kernel: `vpre`
             out.add("2")
         if C > 64:                              # pos_cell_head_kernel: `if (C <= 64) ... else if (tid == 0)`
