@@ -1170,12 +1170,8 @@ int xgk_choose(hipStream_t st, const float* logp, int B, int V, int mode, const 
     XG_CHECK_LAUNCH();
     return XG_OK;
 }
-int xgk_rollout_step(hipStream_t st, int B, const float* logits, const float* uniforms, const int64_t* forced,
-                     int64_t fstride, const float* unf_prev, const float* table, int64_t* tok, float* tok_logp, float* unf,
-                     float* lse, int64_t* seq, float* seq_logp, int32_t* maxf, float* xt, float temperature, int V, int E,
-                     int t, int T, int mode, int split) {
-    RollStepArgs a{logits, uniforms, forced, fstride, unf_prev, table, tok, tok_logp, unf, lse, seq, seq_logp, maxf, xt,
-                   temperature, V, E, t, T, mode, split};
+int xgk_rollout_step(hipStream_t st, int B, const RollStepArgs& a) {
+    const int V = a.V, t = a.t;
     const size_t lds = (size_t)V * sizeof(float);
     if (t >= 1 && lds <= 150 * 1024) {
         static std::atomic<unsigned> optin{0};        // > 64 KiB of dynamic LDS is opted into once per device
@@ -1208,21 +1204,13 @@ int xgk_vocab_part(hipStream_t st, int B, int R, int V, const float* H, int ldh,
     XG_CHECK_LAUNCH();
     return XG_OK;
 }
-RollSelectArgs xgk_roll_select_args(const float* logits, const float* part, const float* uniforms, const int64_t* forced, int64_t fstride,
-                                    const float* unf_prev, const float* table, int64_t* tok, float* tok_logp, float* unf, float* lse,
-                                    int64_t* seq, float* seq_logp, int32_t* maxf, float* xt, float temperature, int V, int E, int t, int T,
-                                    int mode, int split) {
-    const int tw = xgk_vocab_tile_width(V);
-    return RollSelectArgs{{logits, uniforms, forced, fstride, unf_prev, table, tok, tok_logp, unf, lse, seq, seq_logp, maxf, xt,
-                           temperature, V, E, t, T, mode, split}, part, xg_cdiv(V, tw), tw};
+RollSelectArgs xgk_roll_select_args(const RollStepArgs& r, const float* part) {
+    const int tw = xgk_vocab_tile_width(r.V);
+    return RollSelectArgs{r, part, xg_cdiv(r.V, tw), tw};
 }
-int xgk_roll_select(hipStream_t st, int B, const float* logits, const float* part, const float* uniforms, const int64_t* forced,
-                    int64_t fstride, const float* unf_prev, const float* table, int64_t* tok, float* tok_logp, float* unf,
-                    float* lse, int64_t* seq, float* seq_logp, int32_t* maxf, float* xt, float temperature, int V, int E,
-                    int t, int T, int mode, int split) {
-    if (t < 1) return XG_EINVAL;
-    const RollSelectArgs q = xgk_roll_select_args(logits, part, uniforms, forced, fstride, unf_prev, table, tok, tok_logp, unf, lse, seq,
-                                                  seq_logp, maxf, xt, temperature, V, E, t, T, mode, split);
+int xgk_roll_select(hipStream_t st, int B, const RollStepArgs& r, const float* part) {
+    if (r.t < 1) return XG_EINVAL;
+    const RollSelectArgs q = xgk_roll_select_args(r, part);
     hipLaunchKernelGGL(roll_select_kernel, dim3(B), dim3(ST), 0, st, q);
     XG_CHECK_LAUNCH();
     return XG_OK;

@@ -11,12 +11,10 @@
 //   (T*B, .) matrices feed the batched head / weight-gradient GEMMs directly.
 #include "xg_common.h"
 #include <cstring>
-#include <ctime>
 #include "xg_kernels.h"
 
 #include <new>
 #include <cstdlib>
-#include <functional>
 
 namespace {
 
@@ -51,37 +49,14 @@ struct Streams {
         if (run) { grad_event = static_cast<hipEvent_t>(run->grad_event); grad_event_head = static_cast<hipEvent_t>(run->grad_event_head); }
     }
     bool overlap() const { return a != nullptr; }
-    // aux may start work that depends on everything enqueued on main so far
-    int fork() {
-        if (!a) return XG_OK;
-        hipEvent_t e = a->ev[next++ % XG_NRING];
-        if (hipEventRecord(e, main) != hipSuccess || hipStreamWaitEvent(aux, e, 0) != hipSuccess) return XG_EHIP;
-        forked = true;
-        return XG_OK;
-    }
-    // aux2 may start work that depends on everything enqueued on main so far
-    int fork2() {
-        if (!a) return XG_OK;
-        hipEvent_t e = a->ev[next++ % XG_NRING];
-        if (hipEventRecord(e, main) != hipSuccess || hipStreamWaitEvent(aux2, e, 0) != hipSuccess) return XG_EHIP;
-        forked2 = true;
-        return XG_OK;
-    }
-    // main waits for everything enqueued on aux2 so far
-    int join2() {
-        if (!a || !forked2) return XG_OK;
-        hipEvent_t e = a->ev[next++ % XG_NRING];
-        if (hipEventRecord(e, aux2) != hipSuccess || hipStreamWaitEvent(main, e, 0) != hipSuccess) return XG_EHIP;
-        return XG_OK;
-    }
+    // fork / fork2: aux / aux2 may start work that depends on everything enqueued on main so far
+    int fork() { if (!a) return XG_OK; XG_TRY(order(main, aux)); forked = true; return XG_OK; }
+    int fork2() { if (!a) return XG_OK; XG_TRY(order(main, aux2)); forked2 = true; return XG_OK; }
+    // join / join2: main waits for everything enqueued on aux / aux2 so far (nothing to wait for when it was never forked)
+    int join() { return (a && forked) ? order(aux, main) : XG_OK; }
+    int join2() { return (a && forked2) ? order(aux2, main) : XG_OK; }
     // aux waits for everything enqueued on aux2 so far (then a join() of aux covers both)
-    int chain2_into_aux() {
-        if (!a || !forked2) return XG_OK;
-        hipEvent_t e = a->ev[next++ % XG_NRING];
-        if (hipEventRecord(e, aux2) != hipSuccess || hipStreamWaitEvent(aux, e, 0) != hipSuccess) return XG_EHIP;
-        forked = true;
-        return XG_OK;
-    }
+    int chain2_into_aux() { if (!a || !forked2) return XG_OK; XG_TRY(order(aux2, aux)); forked = true; return XG_OK; }
     // record a point on aux that main can wait for later (returns an event slot, or -1 when not overlapping)
     // (marks live across many steps of a loop: they come from their own slots, not from the fork / join ring)
     int mark() {
@@ -98,12 +73,11 @@ struct Streams {
         if (!a || i < 0) return XG_OK;
         return hipStreamWaitEvent(aux2, a->ev[i], 0) == hipSuccess ? XG_OK : XG_EHIP;
     }
-    // main waits for everything enqueued on aux so far
-    int join() {
-        if (!a || !forked) return XG_OK;
+private:
+    // everything enqueued on `to` from here on runs after everything enqueued on `from` so far (one event of the ring)
+    int order(hipStream_t from, hipStream_t to) {
         hipEvent_t e = a->ev[next++ % XG_NRING];
-        if (hipEventRecord(e, aux) != hipSuccess || hipStreamWaitEvent(main, e, 0) != hipSuccess) return XG_EHIP;
-        return XG_OK;
+        return (hipEventRecord(e, from) == hipSuccess && hipStreamWaitEvent(to, e, 0) == hipSuccess) ? XG_OK : XG_EHIP;
     }
 };
 
@@ -212,8 +186,14 @@ bool dims_ok(const XgDims* d) {
            d->F1 > 0 && d->F2 > 0 && d->T > 0;
 }
 
-#define ZERO(ptr, nfloats) \
-    do { if (hipMemsetAsync((ptr), 0, sizeof(float) * (size_t)(nfloats), st) != hipSuccess) return XG_EHIP; } while (0)
+#define ZERO(st, ptr, nfloats) \
+    do { if (hipMemsetAsync((ptr), 0, sizeof(float) * (size_t)(nfloats), (st)) != hipSuccess) return XG_EHIP; } while (0)
+#define COPY(st, dst, src, nfloats) \
+    do { if (hipMemcpyAsync((dst), (src), sizeof(float) * (size_t)(nfloats), hipMemcpyDeviceToDevice, (st)) != hipSuccess) return XG_EHIP; } while (0)
+// XgRun.prof_event0 / prof_event1 (null: none)
+inline int record_prof(void* event, hipStream_t st) {
+    return (!event || hipEventRecord(static_cast<hipEvent_t>(event), st) == hipSuccess) ? XG_OK : XG_EHIP;
+}
 
 // NN data-gradient GEMM: dX[M,N] (+)= dY[M,Kc] * W[Kc,N]   (W row-major, ldw)
 inline int gemm_nn(hipStream_t st, int mode, int M, int N, int Kc, const float* dY, int lddy, const float* W, int ldw,
@@ -300,8 +280,11 @@ inline int zero_dsync(hipStream_t st, const Ws& w) {
 }
 // (the tile element type must fit the arithmetic: bf16 tiles for gemm_mode 1; fp32 tiles otherwise; pre-split planes -- dtype 2 --
 // for gemm_mode 3 only)
+inline int gemm_mode_of(const XgRun* run) { return run && (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0; }
+// the arithmetic mode and the packed weights of this call
 inline void attach_packed(Ws& w, const XgDims& d, const XgRun* run) {
     static const bool disabled = xg_diag_env("XG_NO_PACKED") != nullptr;
+    w.gm = gemm_mode_of(run);
     w.packed = !disabled && run && run->packed && (run->gemm_mode == 1) == (run->packed_dtype == 1) &&
                (run->packed_dtype != 2 || run->gemm_mode == 3) &&
                xgk_packed_view(d, run->packed, run->packed_dtype, &w.pk);
@@ -335,53 +318,59 @@ inline SkJob job_lstm(const LstmFwdArgs& a) {
 }
 
 // ================================================================== encoder
+// One modality of the CG encoder: its parameters (filled from the gradient struct: where their gradients go), its input, and which
+// bf16 weight copies, packed tiles and dropout site are its own
+struct EncMod {
+    const float* feats; int F;
+    float *emb_w, *emb_b, *bn_g, *bn_b, *wih, *whh, *bih, *bhh, *gate_w, *gate_b;
+    float *rmean, *rvar;                      // BatchNorm running statistics (null: none)
+    int w16_emb, w16_wih, w16_gate, pk, pkb, site;
+};
+void enc_mods(const XgDims& d, const XgParams& p, const XgBnState* bn, const XgBatch* x, EncMod mo[2]) {
+    mo[0] = EncMod{x ? x->feats_rgb : nullptr, d.F1, p.emb_rgb_w, p.emb_rgb_b, p.bn_rgb_g, p.bn_rgb_b, p.lstm_rgb_wih, p.lstm_rgb_whh,
+                   p.lstm_rgb_bih, p.lstm_rgb_bhh, p.gate_rgb_w, p.gate_rgb_b, bn ? bn->rgb_mean : nullptr, bn ? bn->rgb_var : nullptr,
+                   W16_EMB_RGB, W16_WIH_RGB, W16_GATE_RGB, PK_ENC_RGB, PKB_ENC_RGB, XG_SITE_EMB_RGB};
+    mo[1] = EncMod{x ? x->feats_opfl : nullptr, d.F2, p.emb_opfl_w, p.emb_opfl_b, p.bn_opfl_g, p.bn_opfl_b, p.lstm_opfl_wih, p.lstm_opfl_whh,
+                   p.lstm_opfl_bih, p.lstm_opfl_bhh, p.gate_opfl_w, p.gate_opfl_b, bn ? bn->opfl_mean : nullptr, bn ? bn->opfl_var : nullptr,
+                   W16_EMB_OPFL, W16_WIH_OPFL, W16_GATE_OPFL, PK_ENC_OPFL, PKB_ENC_OPFL, XG_SITE_EMB_OPFL};
+}
+
 int encoder_fwd(hipStream_t st, const XgDims& d, const XgParams& p, const XgBnState* bn, const XgBatch& x,
                 const XgRun& run, Ws& w, Streams* ss = nullptr) {
     const int B = d.B, K = d.K, R = d.R, N = B * K;
-    const float* feats[2] = {x.feats_rgb, x.feats_opfl};
-    const int F[2] = {d.F1, d.F2};
-    const float* emb_w[2] = {p.emb_rgb_w, p.emb_opfl_w};
-    const float* emb_b[2] = {p.emb_rgb_b, p.emb_opfl_b};
-    const float* bn_g[2] = {p.bn_rgb_g, p.bn_opfl_g};
-    const float* bn_b[2] = {p.bn_rgb_b, p.bn_opfl_b};
-    float* rmean[2] = {bn ? bn->rgb_mean : nullptr, bn ? bn->opfl_mean : nullptr};
-    float* rvar[2] = {bn ? bn->rgb_var : nullptr, bn ? bn->opfl_var : nullptr};
-    const float* wih[2] = {p.lstm_rgb_wih, p.lstm_opfl_wih};
-    const float* whh[2] = {p.lstm_rgb_whh, p.lstm_opfl_whh};
-    const float* bih[2] = {p.lstm_rgb_bih, p.lstm_opfl_bih};
-    const float* bhh[2] = {p.lstm_rgb_bhh, p.lstm_opfl_bhh};
+    EncMod mo[2];
+    enc_mods(d, p, bn, &x, mo);
     // the two modalities' embed -> BatchNorm -> W_ih pipelines are independent until the recurrence: the optical-flow one
     // runs on the second auxiliary stream
     const bool side = ss && ss->overlap();
     if (side) XG_TRY(ss->fork2());
-    hipStream_t st_main = st;
+    hipStream_t side_st = side ? ss->aux2 : st;
     for (int m = 0; m < 2; ++m) {
-        hipStream_t st = (m == 1 && side) ? ss->aux2 : st_main;
-        XG_TRY(lin16(st, w.gm, N, R, F[m], feats[m], nullptr, F[m], emb_w[m], w16(w, m == 0 ? W16_EMB_RGB : W16_EMB_OPFL), emb_b[m],
-                     w.Z[m], R));                                                                           // sub_modules.py:121,126
-        const XgDrop emb_drop = xg_make_drop(&run, m == 0 ? XG_SITE_EMB_RGB : XG_SITE_EMB_OPFL, 0);
+        const EncMod& e = mo[m];
+        hipStream_t sm = m == 1 ? side_st : st;
+        XG_TRY(lin16(sm, w.gm, N, R, e.F, e.feats, nullptr, e.F, e.emb_w, w16(w, e.w16_emb), e.emb_b, w.Z[m], R));     // sub_modules.py:121,126
+        const XgDrop emb_drop = xg_make_drop(&run, e.site, 0);
         bool applied = false;
         if (run.train) {
-            const bool upd = rmean[m] && rvar[m];                  // (running statistics: updated by the same launch)
+            const bool upd = e.rmean && e.rvar;                    // (running statistics: updated by the same launch)
             // statistics + running statistics + the layer's output in ONE launch when the shape allows
-            const int rc = xgk_bn_train_fwd(st, w.Z[m], N, R, w.bn_mean[m], w.bn_var[m], upd ? rmean[m] : nullptr, upd ? rvar[m] : nullptr,
-                                            run.bn_momentum, bn_g[m], bn_b[m], x.feat_mask, w.X[m], run.bn_eps, emb_drop);
+            const int rc = xgk_bn_train_fwd(sm, w.Z[m], N, R, w.bn_mean[m], w.bn_var[m], upd ? e.rmean : nullptr, upd ? e.rvar : nullptr,
+                                            run.bn_momentum, e.bn_g, e.bn_b, x.feat_mask, w.X[m], run.bn_eps, emb_drop);
             if (rc == XG_OK) applied = true;
             else if (rc != 1) return rc;
-            else XG_TRY(xgk_bn_stats(st, w.Z[m], N, R, w.bn_mean[m], w.bn_var[m], upd ? rmean[m] : nullptr, upd ? rvar[m] : nullptr,
+            else XG_TRY(xgk_bn_stats(sm, w.Z[m], N, R, w.bn_mean[m], w.bn_var[m], upd ? e.rmean : nullptr, upd ? e.rvar : nullptr,
                                      run.bn_momentum));
         } else {
-            if (!rmean[m] || !rvar[m]) return XG_EINVAL;
-            if (hipMemcpyAsync(w.bn_mean[m], rmean[m], sizeof(float) * R, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
-            if (hipMemcpyAsync(w.bn_var[m], rvar[m], sizeof(float) * R, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+            if (!e.rmean || !e.rvar) return XG_EINVAL;
+            COPY(sm, w.bn_mean[m], e.rmean, R);
+            COPY(sm, w.bn_var[m], e.rvar, R);
         }
         if (!applied)
-            XG_TRY(xgk_bn_apply(st, w.Z[m], w.bn_mean[m], w.bn_var[m], bn_g[m], bn_b[m], x.feat_mask, w.X[m], N, R, run.bn_eps, emb_drop));
-        XG_TRY(cvt16(st, w, w.X[m], (size_t)N * R));
-        XG_TRY(lin16(st, w.gm, N, 4 * R, R, w.X[m], m16(w, w.X[m]), R, wih[m], w16(w, m == 0 ? W16_WIH_RGB : W16_WIH_OPFL), bih[m],
-                     w.PRE[m], 4 * R));                                                                     // hoisted over all K frames
+            XG_TRY(xgk_bn_apply(sm, w.Z[m], w.bn_mean[m], w.bn_var[m], e.bn_g, e.bn_b, x.feat_mask, w.X[m], N, R, run.bn_eps, emb_drop));
+        XG_TRY(cvt16(sm, w, w.X[m], (size_t)N * R));
+        XG_TRY(lin16(sm, w.gm, N, 4 * R, R, w.X[m], m16(w, w.X[m]), R, e.wih, w16(w, e.w16_wih), e.bih, w.PRE[m], 4 * R));   // hoisted over all K frames
     }
-    if (hipMemsetAsync(w.zeroBR, 0, sizeof(float) * (size_t)B * R, (side ? ss->aux2 : st_main)) != hipSuccess) return XG_EHIP;   // (off the main chain)
+    ZERO(side_st, w.zeroBR, (size_t)B * R);                                                        // (off the main chain)
     if (side) XG_TRY(ss->join2());
     XgRun nodrop = run; nodrop.drop_p = 0.f;
     for (int i = 0; i < K; ++i) {                                                                  // sub_modules.py:132-148
@@ -402,11 +391,11 @@ int encoder_fwd(hipStream_t st, const XgDims& d, const XgParams& p, const XgBnSt
             a.drop = xg_make_drop(&nodrop, 0, 0);
             if (R % 8 == 0) {
                 sk.job[m] = job_lstm(a);
-                sk.job[m].nseg = 1; sk.job[m].seg[0] = seg_nt(w, m == 0 ? PK_ENC_RGB : PK_ENC_OPFL, hp, ldp, whh[m], R, R);
-                sk.job[m].bias[0] = bhh[m];
+                sk.job[m].nseg = 1; sk.job[m].seg[0] = seg_nt(w, mo[m].pk, hp, ldp, mo[m].whh, R, R);
+                sk.job[m].bias[0] = mo[m].bhh;
             } else {
                 float* S = m == 0 ? w.S : w.S2;
-                XG_TRY(xgk_linear(st, w.gm, B, 4 * R, R, hp, ldp, whh[m], bhh[m], S, 4 * R));
+                XG_TRY(xgk_linear(st, w.gm, B, 4 * R, R, hp, ldp, mo[m].whh, mo[m].bhh, S, 4 * R));
                 a.s = S; a.lds_ = 4 * R;
                 XG_TRY(xgk_lstm_fwd(st, a));
             }
@@ -432,22 +421,9 @@ int encoder_bwd(Streams& ss, const XgDims& d, const XgParams& p, const XgParams&
                 const XgRun& run, Ws& w, const float* dV_in) {
     hipStream_t st = ss.main, sx = ss.aux;     // sx: parameter-gradient work nothing downstream waits for
     const int B = d.B, K = d.K, R = d.R, N = B * K;
-    const float* feats[2] = {x.feats_rgb, x.feats_opfl};
-    const int F[2] = {d.F1, d.F2};
-    const float* wih[2] = {p.lstm_rgb_wih, p.lstm_opfl_wih};
-    const float* whh[2] = {p.lstm_rgb_whh, p.lstm_opfl_whh};
-    float* g_wih[2] = {g.lstm_rgb_wih, g.lstm_opfl_wih};
-    float* g_whh[2] = {g.lstm_rgb_whh, g.lstm_opfl_whh};
-    float* g_bih[2] = {g.lstm_rgb_bih, g.lstm_opfl_bih};
-    float* g_bhh[2] = {g.lstm_rgb_bhh, g.lstm_opfl_bhh};
-    const float* gate_w[2] = {p.gate_rgb_w, p.gate_opfl_w};
-    float* g_gate_w[2] = {g.gate_rgb_w, g.gate_opfl_w};
-    float* g_gate_b[2] = {g.gate_rgb_b, g.gate_opfl_b};
-    const float* bn_g[2] = {p.bn_rgb_g, p.bn_opfl_g};
-    float* g_bn_g[2] = {g.bn_rgb_g, g.bn_opfl_g};
-    float* g_bn_b[2] = {g.bn_rgb_b, g.bn_opfl_b};
-    float* g_emb_w[2] = {g.emb_rgb_w, g.emb_opfl_w};
-    float* g_emb_b[2] = {g.emb_rgb_b, g.emb_opfl_b};
+    EncMod mo[2], gr[2];                       // parameters, and where their gradients go
+    enc_mods(d, p, nullptr, &x, mo);
+    enc_mods(d, g, nullptr, nullptr, gr);
 
     XG_TRY(xgk_relu_drop_bwd(st, w.dVw, w.Venc, (int64_t)N * R, xg_make_drop(&run, XG_SITE_FUSION, 0), dV_in));   // dVw = f(dV_in)
     XG_TRY(cvt16(st, w, w.dVw, (size_t)N * R));
@@ -461,14 +437,13 @@ int encoder_bwd(Streams& ss, const XgDims& d, const XgParams& p, const XgParams&
     XG_TRY(ss.fork());
     for (int m = 0; m < 2; ++m) {   // gate m takes source = hidden of the OTHER modality
         const int o = 1 - m;
-        XG_TRY(tn16(sx, w.gm, N, R, R, w.dGG[m], m16(w, w.dGG[m]), R, w.Hs[o], m16(w, w.Hs[o]), R, g_gate_w[m], R, g_gate_b[m]));
-        XG_TRY(nn16(st, w.gm, N, R, R, w.dGG[m], m16(w, w.dGG[m]), R, gate_w[m], w16(w, m == 0 ? W16_GATE_RGB : W16_GATE_OPFL), R,
-                    w.dHs[o], R, true));
+        XG_TRY(tn16(sx, w.gm, N, R, R, w.dGG[m], m16(w, w.dGG[m]), R, w.Hs[o], m16(w, w.Hs[o]), R, gr[m].gate_w, R, gr[m].gate_b));
+        XG_TRY(nn16(st, w.gm, N, R, R, w.dGG[m], m16(w, w.dGG[m]), R, mo[m].gate_w, w16(w, mo[m].w16_gate), R, w.dHs[o], R, true));
     }
     XgRun nodrop = run; nodrop.drop_p = 0.f;
     int curc = 0;
     if (!w.zeroed) {
-        for (int m = 0; m < 2; ++m) { ZERO(w.dHrec[m], (size_t)B * R); ZERO(w.dCrec[m][0], (size_t)B * R); }
+        for (int m = 0; m < 2; ++m) { ZERO(st, w.dHrec[m], (size_t)B * R); ZERO(st, w.dCrec[m][0], (size_t)B * R); }
         XG_TRY(zero_tickets(st, w, 2));
     }
     // cell backward of frame i for modality m, reading / writing the carried dc of parity c.  Stand-alone it takes
@@ -504,7 +479,7 @@ int encoder_bwd(Streams& ss, const XgDims& d, const XgParams& p, const XgParams&
                 }
                 else sk.job[m] = job_store(B, R, w.dHrec[m], R, false);
                 sk.job[m].nseg = 1;
-                sk.job[m].seg[0] = seg_nn(w, m == 0 ? PKB_ENC_RGB : PKB_ENC_OPFL, w.dS[m] + (size_t)i * 4 * R, K * 4 * R, whh[m], R, 4 * R);
+                sk.job[m].seg[0] = seg_nn(w, mo[m].pkb, w.dS[m] + (size_t)i * 4 * R, K * 4 * R, mo[m].whh, R, 4 * R);
             }
             XG_TRY(xgk_skinny(st, sk, sk_mode(w)));
         }
@@ -513,27 +488,26 @@ int encoder_bwd(Streams& ss, const XgDims& d, const XgParams& p, const XgParams&
     const int gm_tail = w.gm | XGK_GEMM_ALONE;
     XG_TRY(ss.fork2());                          // before modality 0's work is enqueued on the main stream
     for (int m = 0; m < 2; ++m) {
+        const EncMod &e = mo[m], &ge = gr[m];
         // Hprev[b,k] = H[b,k-1], zero at k = 0 : one clean TN GEMM for dW_hh
         if (m == 0) XG_TRY(ss.fork());           // dS of both modalities is final after the loop
-        if (hipMemsetAsync(w.Hprev[m], 0, sizeof(float) * (size_t)N * R, sx) != hipSuccess) return XG_EHIP;
+        ZERO(sx, w.Hprev[m], (size_t)N * R);
         if (K > 1)   // one strided 2-D copy covers all videos: rows = B, cols = (K-1)*R
             XG_TRY(xgk_copy2d(sx, w.Hprev[m] + R, K * R, w.Hs[m], K * R, B, (K - 1) * R, false));
         XG_TRY(cvt16(sx, w, w.Hprev[m], (size_t)N * R));
         // (the recurrence is over: no launch chain runs beside these weight gradients -- XGK_GEMM_ALONE, xg_kernels.h)
-        XG_TRY(tn16(sx, gm_tail, N, 4 * R, R, w.dS[m], m16(w, w.dS[m]), 4 * R, w.Hprev[m], m16(w, w.Hprev[m]), R, g_whh[m], R, g_bih[m], g_bhh[m]));
-        XG_TRY(tn16(sx, gm_tail, N, 4 * R, R, w.dS[m], m16(w, w.dS[m]), 4 * R, w.X[m], m16(w, w.X[m]), R, g_wih[m], R));
+        XG_TRY(tn16(sx, gm_tail, N, 4 * R, R, w.dS[m], m16(w, w.dS[m]), 4 * R, w.Hprev[m], m16(w, w.Hprev[m]), R, ge.whh, R, ge.bih, ge.bhh));
+        XG_TRY(tn16(sx, gm_tail, N, 4 * R, R, w.dS[m], m16(w, w.dS[m]), 4 * R, w.X[m], m16(w, w.X[m]), R, ge.wih, R));
         // the optical-flow modality's input-side backward runs beside the rgb one (second auxiliary stream, forked above)
-        hipStream_t st_outer = st;
-        hipStream_t st = (m == 1 && ss.overlap()) ? ss.aux2 : st_outer;
-        XG_TRY(nn16(st, w.gm, N, R, 4 * R, w.dS[m], m16(w, w.dS[m]), 4 * R, wih[m], w16(w, m == 0 ? W16_WIH_RGB : W16_WIH_OPFL), R,
-                    w.dX[m], R, false));
+        hipStream_t sm = (m == 1 && ss.overlap()) ? ss.aux2 : st;
+        XG_TRY(nn16(sm, w.gm, N, R, 4 * R, w.dS[m], m16(w, w.dS[m]), 4 * R, e.wih, w16(w, e.w16_wih), R, w.dX[m], R, false));
         // BatchNorm + ReLU + dropout + mask backward (sub_modules.py:121-123)
-        if (!w.zeroed) { ZERO(w.bn_s1[m], R); ZERO(w.bn_s2[m], R); }
-        XG_TRY(xgk_bn_bwd_reduce(st, w.dX[m], w.X[m], w.Z[m], w.bn_mean[m], w.bn_var[m], x.feat_mask, N, R, run.bn_eps,
-                                 xg_make_drop(&run, m == 0 ? XG_SITE_EMB_RGB : XG_SITE_EMB_OPFL, 0), w.bn_s1[m], w.bn_s2[m]));
-        XG_TRY(xgk_bn_bwd_apply(st, w.dX[m], w.Z[m], w.bn_mean[m], w.bn_var[m], bn_g[m], w.bn_s1[m], w.bn_s2[m], N, R,
-                                run.bn_eps, run.train != 0, g_bn_b[m], g_bn_g[m]));     // (+ the two parameter gradients)
-        XG_TRY(gemm_tn_cs(st, gm_tail, N, R, F[m], w.dX[m], R, feats[m], F[m], g_emb_w[m], F[m], g_emb_b[m]));
+        if (!w.zeroed) { ZERO(sm, w.bn_s1[m], R); ZERO(sm, w.bn_s2[m], R); }
+        XG_TRY(xgk_bn_bwd_reduce(sm, w.dX[m], w.X[m], w.Z[m], w.bn_mean[m], w.bn_var[m], x.feat_mask, N, R, run.bn_eps,
+                                 xg_make_drop(&run, e.site, 0), w.bn_s1[m], w.bn_s2[m]));
+        XG_TRY(xgk_bn_bwd_apply(sm, w.dX[m], w.Z[m], w.bn_mean[m], w.bn_var[m], e.bn_g, w.bn_s1[m], w.bn_s2[m], N, R,
+                                run.bn_eps, run.train != 0, ge.bn_b, ge.bn_g));     // (+ the two parameter gradients)
+        XG_TRY(gemm_tn_cs(sm, gm_tail, N, R, e.F, w.dX[m], R, e.feats, e.F, ge.emb_w, e.F, ge.emb_b));
     }
     return ss.chain2_into_aux();              // the caller's join() of aux then covers the second side chain too
 }
@@ -587,6 +561,31 @@ struct StepIO {
 // the packed-weight form of the step needs 16-byte rows everywhere (R % 8 covers R; E and A are checked here)
 inline bool step_packed(const Ws& w, const XgDims& d) { return w.packed && d.R % 8 == 0 && d.E % 4 == 0 && d.A % 4 == 0; }
 
+// Step t of a time-major workspace: state t -> t + 1, the step's token rows, gated POS rows and saved tensors.  The caller adds
+// the mask and what its form of the step reads besides (pre1 / pos and gp / sel).
+inline StepIO step_io_at(const Ws& w, const XgDims& d, int t) {
+    const size_t tb = (size_t)t * d.B, BR = (size_t)d.B * d.R;
+    StepIO s{};
+    s.xt = w.Xe + tb * d.E; s.posg = w.POSG + t * BR;
+    s.h1 = w.H1 + t * BR; s.c1 = w.C1 + t * BR; s.h2 = w.H2 + t * BR; s.c2 = w.C2 + t * BR;
+    s.h1o = w.H1 + (t + 1) * BR; s.c1o = w.C1 + (t + 1) * BR; s.h2o = w.H2 + (t + 1) * BR; s.c2o = w.C2 + (t + 1) * BR;
+    s.P = w.P + tb * d.A; s.alpha = w.ALPHA + tb * d.K; s.af = w.AF + t * BR;
+    s.g1 = w.G1 + tb * 4 * d.R; s.g2 = w.G2 + tb * 4 * d.R; s.t = t;
+    return s;
+}
+
+// cell 1 / cell 2 of the step (the product that feeds it is the caller's)
+inline LstmFwdArgs cell_fwd_args(int layer, const StepIO& s, const XgRun& run, int B, int R) {
+    const bool l1 = layer == 1;
+    LstmFwdArgs a{};
+    a.add = l1 ? s.pre1 : nullptr; a.ldadd = l1 ? 4 * R : 0;
+    a.c_prev = l1 ? s.c1 : s.c2; a.ldcp = R; a.h_prev = l1 ? s.h1 : s.h2; a.ldhp = R; a.mask = s.mask; a.ldm = s.ldm;
+    a.gates = l1 ? s.g1 : s.g2; a.ldg = 4 * R; a.c_out = l1 ? s.c1o : s.c2o; a.ldco = R; a.h_out = l1 ? s.h1o : s.h2o; a.ldho = R;
+    a.B = B; a.R = R; a.order = XG_ORDER_IFOG; a.mask_mode = XG_MASK_HOLD;
+    a.drop = xg_make_drop(&run, l1 ? XG_SITE_L1 : XG_SITE_L2, s.t);
+    return a;
+}
+
 // attention + the two cells for one step (sub_modules.py:677-684).
 //
 // Packed form, 3 launches, every launch a multi-job skinny launch (xg_step.hip):
@@ -600,18 +599,7 @@ inline bool step_packed(const Ws& w, const XgDims& d) { return w.packed && d.R %
 int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& run, Ws& w, const float* V,
               const float* vproj, const StepIO& s) {
     const int B = d.B, R = d.R, A = d.A, E = d.E;
-    LstmFwdArgs a{};
-    a.add = s.pre1; a.ldadd = 4 * R;
-    a.c_prev = s.c1; a.ldcp = R; a.h_prev = s.h1; a.ldhp = R; a.mask = s.mask; a.ldm = s.ldm;
-    a.gates = s.g1; a.ldg = 4 * R; a.c_out = s.c1o; a.ldco = R; a.h_out = s.h1o; a.ldho = R;
-    a.B = B; a.R = R; a.order = XG_ORDER_IFOG; a.mask_mode = XG_MASK_HOLD;
-    a.drop = xg_make_drop(&run, XG_SITE_L1, s.t);
-    LstmFwdArgs c{};
-    c.add = nullptr; c.ldadd = 0;
-    c.c_prev = s.c2; c.ldcp = R; c.h_prev = s.h2; c.ldhp = R; c.mask = s.mask; c.ldm = s.ldm;
-    c.gates = s.g2; c.ldg = 4 * R; c.c_out = s.c2o; c.ldco = R; c.h_out = s.h2o; c.ldho = R;
-    c.B = B; c.R = R; c.order = XG_ORDER_IFOG; c.mask_mode = XG_MASK_HOLD;
-    c.drop = xg_make_drop(&run, XG_SITE_L2, s.t);
+    LstmFwdArgs a = cell_fwd_args(1, s, run, B, R), c = cell_fwd_args(2, s, run, B, R);
     // The step as ONE dataflow launch (xg_dstep.hip) exists for measurement only (-DXG_DIAG build, XG_DSTEP=1): at 128 rows it
     // takes 77 us against 46 us for the three launches below (DESIGN.md 4.3 has the in-kernel timeline); it is ahead only
     // below ~16 rows (30 vs 34 us at 8 rows).
@@ -641,13 +629,37 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
         return xgk_dstep(st, a2, w.gm);
     }
 #endif
-    if (step_packed(w, d)) {
-        // xt as a matrix operand: the materialised rows, or embed.weight gathered by token
-        auto xt_seg = [&](int which, const float* W) {
-            SkSeg g = seg_nt(w, which, s.xt ? s.xt : p.embed_w, E, W, E, E);
-            if (!s.xt) { g.gather = s.tok; g.gather_max = d.V - 1; }
-            return g;
-        };
+    // ---- jobs both skinny forms of the step share.  pk: the packed form (weights as packed tiles, token rows gathered by index)
+    const bool pk = step_packed(w, d);
+    auto wseg = [&](int which, const float* X, int ldx, const float* W, int ldw, int Kc) {
+        return pk ? seg_nt(w, which, X, ldx, W, ldw, Kc) : seg_nt(X, ldx, W, ldw, Kc);
+    };
+    // xt as a matrix operand: the materialised rows, or embed.weight gathered by token
+    auto xt_seg = [&](int which, const float* W) {
+        SkSeg g = wseg(which, s.xt ? s.xt : p.embed_w, E, W, E, E);
+        if (!s.xt) { g.gather = s.tok; g.gather_max = d.V - 1; }
+        return g;
+    };
+    auto s2_job = [&](SkJob& j) {                         // S2' = h2 W_h2h2 + b (gate-major, cell tiling) -> w.S2
+        j = job_store(B, 4 * R, w.S2, 4 * R, false);
+        j.cell_cols = 1; j.R = R; j.nseg = 1;
+        j.seg[0] = wseg(PK_L2_H2H, s.h2, R, p.l2_h2h_w, R, R); j.bias[0] = p.l2_h2h_b;
+    };
+    auto gate_job = [&](SkJob& j) {                       // POS gate: pos' = dropout(relu(W_g xt + b)) * pos + pos           :682
+        j = job_store(B, R, s.gp, R, false);
+        j.epi = SK_EPI_GATE; j.nseg = 1;
+        j.seg[0] = xt_seg(PK_DGATE, p.dgate_w); j.bias[0] = p.dgate_b;
+        j.gate_t = s.pos; j.ldt = R; j.gate_y = s.posg; j.ldy = R;
+        j.drop = xg_make_drop(&run, XG_SITE_DGATE, s.t);
+    };
+    auto p_job = [&](SkJob& j) {                          // p = h2a([h1 ; h2])                                               :677
+        j = job_store(B, A, s.P, A, false);
+        j.nseg = 2;
+        j.seg[0] = wseg(PK_H2A1, s.h1, R, p.h2a_w, 2 * R, R);
+        j.seg[1] = wseg(PK_H2A2, s.h2, R, p.h2a_w + R, 2 * R, R);
+        j.bias[0] = p.h2a_b;
+    };
+    if (pk) {
         // the attention rides in the second launch as two workgroups per video (SK_EPI_ATTN) when its shapes allow
         // (rollout form only: there cell 1 and S2' share the launch with it.  Under teacher forcing the three candidates --
         // B: S2' in launch 1 + stand-alone attention, D: cell 2 keeps its h2 segment (K = 3R) + stand-alone attention,
@@ -673,44 +685,22 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
         // Job order is dispatch order, and with two workgroups per CU resident at once a CU ends up with tile c of the first 256
         // and tile c of the next 256: the 256 S2' tiles (K = R) go FIRST so that every heavy p tile (K = 2R) is paired with a light
         // one instead of with another p tile (round 4: 45.3 -> 44.5 us per step at 128 rows)
-        auto s2_job_early = [&](SkJob& j) {
-            j = job_store(B, 4 * R, w.S2, 4 * R, false);
-            j.cell_cols = 1; j.R = R; j.nseg = 1;
-            j.seg[0] = seg_nt(w, PK_L2_H2H, s.h2, R, p.l2_h2h_w, R, R); j.bias[0] = p.l2_h2h_b;
-        };
-        if (s2_first) s2_job_early(k1.job[n1++]);
-        if (!s.pre1) {  // POS gate: pos' = dropout(relu(W_g xt + b)) * pos + pos                          :682
+        if (s2_first) s2_job(k1.job[n1++]);
+        if (!s.pre1) {
             SkJob& j = k1.job[n1++];
-            j = job_store(B, R, s.gp, R, false);
-            j.epi = SK_EPI_GATE; j.nseg = 1;
-            j.seg[0] = xt_seg(PK_DGATE, p.dgate_w); j.bias[0] = p.dgate_b;
-            j.gate_t = s.pos; j.ldt = R; j.gate_y = s.posg; j.ldy = R;
-            j.drop = xg_make_drop(&run, XG_SITE_DGATE, s.t);
+            gate_job(j);
             if (s.sel) {
                 if (s.xt) return XG_EINVAL;
                 j.select = 1; k1.sel = *s.sel;
             }
         }
-        {   // p = h2a([h1 ; h2])                                                                         :677
-            SkJob& j = k1.job[n1++];
-            j = job_store(B, A, s.P, A, false);
-            j.nseg = 2;
-            j.seg[0] = seg_nt(w, PK_H2A1, s.h1, R, p.h2a_w, 2 * R, R);
-            j.seg[1] = seg_nt(w, PK_H2A2, s.h2, R, p.h2a_w + R, 2 * R, R);
-            j.bias[0] = p.h2a_b;
-        }
+        p_job(k1.job[n1++]);
         if (s.pre1) {   // teacher forcing: cell 1 is only its recurrent product (token side hoisted)        :683
             SkJob& j = k1.job[n1++];
             j = job_lstm(a);
             j.nseg = 1;
             j.seg[0] = seg_nt(w, PK_L1_H2H, s.h1, R, p.l1_h2h_w, R, R); j.bias[0] = p.l1_h2h_b;
         }
-        auto s2_job = [&](SkJob& j) {                     // S2' = h2 W_h2h2 + b (gate-major, cell tiling) -> w.S2
-            j = job_store(B, 4 * R, w.S2, 4 * R, false);
-            j.cell_cols = 1; j.R = R;
-            j.nseg = 1;
-            j.seg[0] = seg_nt(w, PK_L2_H2H, s.h2, R, p.l2_h2h_w, R, R); j.bias[0] = p.l2_h2h_b;
-        };
         if (fused_attn) {   // the attention's accumulators start from zero
             SkJob& j = k1.job[n1++];
             j = SkJob{};
@@ -766,24 +756,16 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
     if (R % 8 == 0) {
         SkArgs k1{};
         k1.njobs = 2;
-        k1.job[0] = job_store(B, A, s.P, A, false);
-        k1.job[0].nseg = 2;
-        k1.job[0].seg[0] = seg_nt(s.h1, R, p.h2a_w, 2 * R, R);
-        k1.job[0].seg[1] = seg_nt(s.h2, R, p.h2a_w + R, 2 * R, R);
-        k1.job[0].bias[0] = p.h2a_b;
-        k1.job[1] = job_lstm(a);
+        p_job(k1.job[0]);
+        SkJob cell1 = job_lstm(a);
         if (s.pre1) {
-            k1.job[1].nseg = 1;
-            k1.job[1].seg[0] = seg_nt(s.h1, R, p.l1_h2h_w, R, R); k1.job[1].bias[0] = p.l1_h2h_b;
+            cell1.nseg = 1;
+            cell1.seg[0] = seg_nt(s.h1, R, p.l1_h2h_w, R, R); cell1.bias[0] = p.l1_h2h_b;
+            k1.job[1] = cell1;
             XG_TRY(xgk_skinny(st, k1, sk_mode(w)));
         } else {
             // rollout form: [p || POS gate] first (the gate feeds cell 1), then cell 1 with all three products
-            SkJob cell1 = k1.job[1];
-            k1.job[1] = job_store(B, R, s.gp, R, false);
-            k1.job[1].epi = SK_EPI_GATE; k1.job[1].nseg = 1;
-            k1.job[1].seg[0] = seg_nt(s.xt, E, p.dgate_w, E, E); k1.job[1].bias[0] = p.dgate_b;
-            k1.job[1].gate_t = s.pos; k1.job[1].ldt = R; k1.job[1].gate_y = s.posg; k1.job[1].ldy = R;
-            k1.job[1].drop = xg_make_drop(&run, XG_SITE_DGATE, s.t);
+            gate_job(k1.job[1]);
             XG_TRY(xgk_skinny(st, k1, sk_mode(w)));
             SkArgs k1b{};
             k1b.njobs = 1;
@@ -851,7 +833,7 @@ int decoder_tokens_xe(hipStream_t sx, const XgDims& d, const XgParams& p, const 
 int decoder_fwd_xe(Streams& ss, const XgDims& d, const XgParams& p, const XgBatch& x, const XgRun& run, Ws& w,
                    int* logit_rows_done, bool early_loss = false) {
     hipStream_t st = ss.main;
-    const int B = d.B, R = d.R, A = d.A, E = d.E, T = d.T;
+    const int B = d.B, R = d.R, T = d.T;
     const size_t BR = (size_t)B * R;
     XG_TRY(init_and_vproj(ss, d, p, x.feat_mask, w));
     XG_TRY(zero_dsync(st, w));
@@ -861,16 +843,10 @@ int decoder_fwd_xe(Streams& ss, const XgDims& d, const XgParams& p, const XgBatc
     // needs an EMPTY CU and waited for the whole persistent product (255 us: the chain simply stopped).  6.16 -> 6.10 ms.
     const bool fwd_bg = th > 0 && w.gm == 0;
     *logit_rows_done = 0;
-    if (run.prof_event0 && hipEventRecord(static_cast<hipEvent_t>(run.prof_event0), st) != hipSuccess) return XG_EHIP;
+    XG_TRY(record_prof(run.prof_event0, st));
     for (int t = 0; t < T; ++t) {
-        StepIO s{};
-        s.xt = w.Xe + (size_t)t * B * E; s.posg = w.POSG + t * BR; s.pre1 = w.PRE1 + (size_t)t * B * 4 * R;
-        s.mask = x.seq_mask + t; s.ldm = T;
-        s.h1 = w.H1 + t * BR; s.c1 = w.C1 + t * BR; s.h2 = w.H2 + t * BR; s.c2 = w.C2 + t * BR;
-        s.h1o = w.H1 + (t + 1) * BR; s.c1o = w.C1 + (t + 1) * BR; s.h2o = w.H2 + (t + 1) * BR; s.c2o = w.C2 + (t + 1) * BR;
-        s.P = w.P + (size_t)t * B * A; s.alpha = w.ALPHA + (size_t)t * B * d.K; s.af = w.AF + t * BR;
-        s.g1 = w.G1 + (size_t)t * B * 4 * R; s.g2 = w.G2 + (size_t)t * B * 4 * R; s.t = t;
-        s.half_attn = fwd_bg;
+        StepIO s = step_io_at(w, d, t);
+        s.pre1 = w.PRE1 + (size_t)t * B * 4 * R; s.mask = x.seq_mask + t; s.ldm = T; s.half_attn = fwd_bg;
         XG_TRY(core_step(st, d, p, run, w, w.Venc, w.vproj, s));
         if (th > 0 && t == th - 1) {
             XG_TRY(ss.fork());
@@ -882,22 +858,26 @@ int decoder_fwd_xe(Streams& ss, const XgDims& d, const XgParams& p, const XgBatc
                 XG_TRY(xgk_xent_fwd(ss.aux, w.LOGITS, d.V, x.seq, x.seq_mask, nullptr, B, T, d.V, 1, w.LSE, w.sums, 0, th * B, false));
         }
     }
-    if (run.prof_event1 && hipEventRecord(static_cast<hipEvent_t>(run.prof_event1), st) != hipSuccess) return XG_EHIP;
-    return XG_OK;
+    return record_prof(run.prof_event1, st);
+}
+
+// classifier head over the stacked outputs H2[1..T] -> w.CL (SAModel.py:110)
+int classifier_fwd(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& run, Ws& w, int rows) {
+    const float* Hout = w.H2 + (size_t)d.B * d.R;
+    XG_TRY(xgk_linear(st, w.gm, rows, d.H, d.R, Hout, d.R, p.cls0_w, p.cls0_b, w.HC, d.H, true));
+    XG_TRY(xgk_gate_fwd(st, w.HC, d.H, nullptr, 0, 0, nullptr, 0, rows, d.H, xg_make_drop(&run, XG_SITE_CLS, 0), d.B, 1 << 30, 1, d.B));
+    return xgk_linear(st, w.gm, rows, d.C, d.H, w.HC, d.H, p.cls3_w, p.cls3_b, w.CL, d.C);
 }
 
 // classifier hidden + logits for the stacked outputs H2[1..T] (SAModel.py:109-110)
 int heads_fwd_logits(Streams& ss, const XgDims& d, const XgParams& p, const XgRun& run, Ws& w, int rows, int rows_done) {
     hipStream_t st = ss.main;
-    const int B = d.B, R = d.R;
-    const float* Hout = w.H2 + (size_t)B * R;
-    XG_TRY(cvt16(st, w, Hout + (size_t)rows_done * R, (size_t)(rows - rows_done) * R));
-    XG_TRY(lin16(st, w.gm, rows - rows_done, d.V, R, Hout + (size_t)rows_done * R, m16(w, Hout + (size_t)rows_done * R), R, p.logit_w,
-                 w16(w, W16_LOGIT), p.logit_b, w.LOGITS + (size_t)rows_done * d.V, d.V));
-    XG_TRY(xgk_linear(st, w.gm, rows, d.H, R, Hout, R, p.cls0_w, p.cls0_b, w.HC, d.H, true));
-    XG_TRY(xgk_gate_fwd(st, w.HC, d.H, nullptr, 0, 0, nullptr, 0, rows, d.H, xg_make_drop(&run, XG_SITE_CLS, 0), B, 1 << 30,
-                        1, B));
-    XG_TRY(xgk_linear(st, w.gm, rows, d.C, d.H, w.HC, d.H, p.cls3_w, p.cls3_b, w.CL, d.C));
+    const int R = d.R;
+    const float* Hlate = w.H2 + (size_t)d.B * R + (size_t)rows_done * R;       // the rows whose logits are not under way yet
+    XG_TRY(cvt16(st, w, Hlate, (size_t)(rows - rows_done) * R));
+    XG_TRY(lin16(st, w.gm, rows - rows_done, d.V, R, Hlate, m16(w, Hlate), R, p.logit_w, w16(w, W16_LOGIT), p.logit_b,
+                 w.LOGITS + (size_t)rows_done * d.V, d.V));
+    XG_TRY(classifier_fwd(st, d, p, run, w, rows));
     return ss.join();                         // first-half logits from the auxiliary stream
 }
 
@@ -908,7 +888,6 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
                      int tok_bstride, int tok_tstride) {
     hipStream_t st = ss.main;
     const int B = d.B, K = d.K, R = d.R, A = d.A, E = d.E, T = d.T, TB = T * B, N = B * K;
-    (void)TB;
     const size_t BR = (size_t)B * R;
     // The reverse-time recurrence splits into two chains.  Chain 2 (cell 2 + attention: dh2, dc2) never reads anything
     // chain 1 (cell 1: dh1, dc1) produces, and only chain 2's products (dAF, dE) feed the encoder backward: it runs on
@@ -923,37 +902,28 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
     if (w.zeroed) {
         XG_TRY(ss.join2());                      // the zero block (zero_backward_block, second auxiliary stream)
     } else {
-        for (int j = 0; j < 4; ++j) ZERO(w.dst[0][j], BR);
-        ZERO(w.DAF, (size_t)T * BR);             // the dAF products accumulate (split-K across workgroups)
+        for (int j = 0; j < 4; ++j) ZERO(st, w.dst[0][j], BR);
+        ZERO(st, w.DAF, (size_t)T * BR);             // the dAF products accumulate (split-K across workgroups)
         XG_TRY(zero_tickets(st, w, SK_MAX_JOBS));
     }
-    auto cell2_bwd = [&](int t, int c) {          // backward of cell 2 at step t, reading the carried state of parity c
+    // backward of cell `layer` at step t, reading the carried dh / dc of parity c (dst[c][0..1]: cell 1, dst[c][2..3]: cell 2)
+    auto cell_bwd = [&](int layer, int t, int c, const float* dh_add) {
+        const bool l1 = layer == 1;
+        const int i = l1 ? 0 : 2;
+        const float* C = l1 ? w.C1 : w.C2;
         LstmBwdArgs a{};
-        a.gates = w.G2 + (size_t)t * B * 4 * R; a.ldg = 4 * R;
-        a.c_prev = w.C2 + t * BR; a.ldcp = R; a.c_out = w.C2 + (t + 1) * BR; a.ldco = R;
+        a.gates = (l1 ? w.G1 : w.G2) + (size_t)t * B * 4 * R; a.ldg = 4 * R;
+        a.c_prev = C + t * BR; a.ldcp = R; a.c_out = C + (t + 1) * BR; a.ldco = R;
         a.mask = mask + (size_t)t * mask_tstride; a.ldm = ldm;
-        a.dh_out = w.dst[c][2]; a.lddh = R; a.dh_add = w.DH2OUT + t * BR; a.lddha = R;
-        a.dc_out = w.dst[c][3]; a.lddc = R;
-        a.ds = w.DS2 + (size_t)t * B * 4 * R; a.ldds = 4 * R;
-        a.dc_prev = w.dst[c ^ 1][3]; a.lddcp = R; a.dh_prev = w.dst[c ^ 1][2]; a.lddhp = R;
+        a.dh_out = w.dst[c][i]; a.lddh = R; a.dh_add = dh_add; a.lddha = dh_add ? R : 0; a.dc_out = w.dst[c][i + 1]; a.lddc = R;
+        a.ds = (l1 ? w.DS1 : w.DS2) + (size_t)t * B * 4 * R; a.ldds = 4 * R;
+        a.dc_prev = w.dst[c ^ 1][i + 1]; a.lddcp = R; a.dh_prev = w.dst[c ^ 1][i]; a.lddhp = R;
         a.B = B; a.R = R; a.order = XG_ORDER_IFOG; a.mask_mode = XG_MASK_HOLD;
-        a.drop = xg_make_drop(&run, XG_SITE_L2, t);
+        a.drop = xg_make_drop(&run, l1 ? XG_SITE_L1 : XG_SITE_L2, t);
         return a;
     };
     hipStream_t s1 = ss.aux2;                 // chain 1 and what depends on it
     int cur1 = 0;
-    auto cell1_bwd = [&](int t, int c, const float* dh_add) {
-        LstmBwdArgs a{};
-        a.gates = w.G1 + (size_t)t * B * 4 * R; a.ldg = 4 * R;
-        a.c_prev = w.C1 + t * BR; a.ldcp = R; a.c_out = w.C1 + (t + 1) * BR; a.ldco = R;
-        a.mask = mask + (size_t)t * mask_tstride; a.ldm = ldm;
-        a.dh_out = w.dst[c][0]; a.lddh = R; a.dh_add = dh_add; a.lddha = dh_add ? R : 0; a.dc_out = w.dst[c][1]; a.lddc = R;
-        a.ds = w.DS1 + (size_t)t * B * 4 * R; a.ldds = 4 * R;
-        a.dc_prev = w.dst[c ^ 1][1]; a.lddcp = R; a.dh_prev = w.dst[c ^ 1][0]; a.lddhp = R;
-        a.B = B; a.R = R; a.order = XG_ORDER_IFOG; a.mask_mode = XG_MASK_HOLD;
-        a.drop = xg_make_drop(&run, XG_SITE_L1, t);
-        return a;
-    };
     // what cell 1's output at step t receives from chain 2, as segments:  ds2[t] W_i2h2 (+ dp[t+1] W_h2a[:, :R])
     auto from_chain2 = [&](SkJob& j, int first, int t) {
         j.seg[first] = seg_nn(w, PKB_L2_I2H, w.DS2 + (size_t)t * B * 4 * R, 4 * R, p.l2_i2h_w, R, 4 * R);
@@ -971,12 +941,12 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
             sk.job[0] = job_store(B, R, w.DH1X + t * BR, R, false);
             from_chain2(sk.job[0], 0, t);
             XG_TRY(xgk_skinny(s1, sk, sk_mode(w)));
-            XG_TRY(xgk_lstm_bwd(s1, cell1_bwd(t, cur1, w.DH1X + t * BR)));
+            XG_TRY(xgk_lstm_bwd(s1, cell_bwd(1, t, cur1, w.DH1X + t * BR)));
         }
         SkArgs sk{};
         sk.njobs = 1;
         SkJob& j = sk.job[0];
-        if (fuse && t > 0) j = job_lstm_bwd(cell1_bwd(t - 1, cur1 ^ 1, nullptr), dh1p, R);
+        if (fuse && t > 0) j = job_lstm_bwd(cell_bwd(1, t - 1, cur1 ^ 1, nullptr), dh1p, R);
         else j = job_store(B, R, dh1p, R, true);
         j.nseg = 1;
         j.seg[0] = seg_nn(w, PKB_L1_H2H, ds1, 4 * R, p.l1_h2h_w, R, 4 * R);
@@ -1047,7 +1017,7 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
         float* ds2 = w.DS2 + (size_t)t * B * 4 * R;
         float* dp = w.DP + (size_t)t * B * A;
         float* daf = w.DAF + t * BR;
-        if (!fuse || t == T - 1) XG_TRY(xgk_lstm_bwd(st, cell2_bwd(t, cur)));
+        if (!fuse || t == T - 1) XG_TRY(xgk_lstm_bwd(st, cell_bwd(2, t, cur, w.DH2OUT + t * BR)));
         {   // s2 = h1' Wi + af Wa + h2 Wh : the two data gradients chain 2 needs now
             SkArgs sk{};
             sk.njobs = 2;
@@ -1061,7 +1031,7 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
         {   // into step t-1: dh2 += dp Wh2a[:, R:]  (+ cell 2's backward at t-1 on the completed dh2)
             SkArgs sk{};
             sk.njobs = 1;
-            if (fuse && t > 0) sk.job[0] = job_lstm_bwd(cell2_bwd(t - 1, cur ^ 1), dh2p, R);
+            if (fuse && t > 0) sk.job[0] = job_lstm_bwd(cell_bwd(2, t - 1, cur ^ 1, w.DH2OUT + (t - 1) * BR), dh2p, R);
             else sk.job[0] = job_store(B, R, dh2p, R, true);
             sk.job[0].nseg = 1;
             sk.job[0].seg[0] = seg_nn(w, PKB_H2A2, dp, A, p.h2a_w + R, 2 * R, A);
@@ -1074,8 +1044,7 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
         constexpr int c1_lag = 7;
         bool boundary = false;                // t == ceil(k T / chunks) for some k in 1 .. chunks - 1
         for (int k = 1; k < wg_chunks; ++k) boundary = boundary || t == (k * T + wg_chunks - 1) / wg_chunks;
-        const int lag = c1_lag < 1 ? 1 : c1_lag;
-        if (t == 0 || (boundary && t < wg_hi) || (T - 1 - t) % lag == lag - 1) {
+        if (t == 0 || (boundary && t < wg_hi) || (T - 1 - t) % c1_lag == c1_lag - 1) {
             XG_TRY(ss.fork2());
             for (int tt = c1_next; tt >= t; --tt) XG_TRY(chain1_step(tt));
             c1_next = t - 1;
@@ -1091,7 +1060,6 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
             wg_hi = t;
         }
     }
-    const int cur2 = cur;
     XG_TRY(ss.fork());                        // chain 2 is complete: DS2, DP, DAF, DE
     hipStream_t sx = ss.aux;                  // parameter gradients that only need chain 2
     // ---- after the loop.  Main chain (the encoder backward waits for it): dVproj -> dV.  Everything else is a
@@ -1101,11 +1069,8 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
     XG_TRY(cvt16(st, w, w.DVPROJ, (size_t)N * A));
     XG_TRY(nn16(st, w.gm, N, R, A, w.DVPROJ, m16(w, w.DVPROJ), A, p.v2a_w, w16(w, W16_V2A), R, w.DV, R, true));
     // gradients wrt the initial state -> img_embed_* (init_hidden; vbar is detached: SAModel.py:59-62)
-    const int cur1_end = cur1, wg_hi_end = wg_hi, wg_mark_end = wg_mark;
-    auto tail = [=, &w, &ss]() -> int {
-    const int cur1 = cur1_end, wg_hi = wg_hi_end, wg_mark = wg_mark_end;
     {
-        float* gst[4] = {w.dst[cur1][0], w.dst[cur1][1], w.dst[cur2][2], w.dst[cur2][3]};
+        float* gst[4] = {w.dst[cur1][0], w.dst[cur1][1], w.dst[cur][2], w.dst[cur][3]};
         float* gw[4] = {g.ih1_w, g.ic1_w, g.ih2_w, g.ic2_w};
         float* gb[4] = {g.ih1_b, g.ic1_b, g.ih2_b, g.ic2_b};
         for (int j = 0; j < 4; ++j) {
@@ -1137,8 +1102,6 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
     // everything but two_spatial_encoder.* is final once the auxiliary stream gets here (it has waited for main above)
     if (ss.grad_event && hipEventRecord(ss.grad_event, sx) != hipSuccess) return XG_EHIP;
     return XG_OK;
-    };
-    return tail();
 }
 
 // heads backward from dlogits (rows,V) in w.LOGITS and dcl (rows,C) in w.DCL -> DH2OUT, head param grads
@@ -1164,7 +1127,7 @@ int heads_bwd(Streams& ss, const XgDims& d, const XgParams& p, const XgParams& g
     const int B = d.B, R = d.R, TB = d.T * B;
     const float* Hout = w.H2 + (size_t)B * R;
     XG_TRY(zero_backward_block(ss, w));       // (every caller continues with decoder_bwd_core, which joins it)
-    if (rows < TB) ZERO(w.DH2OUT + (size_t)rows * R, (size_t)(TB - rows) * R);
+    if (rows < TB) ZERO(st, w.DH2OUT + (size_t)rows * R, (size_t)(TB - rows) * R);
     // dH = dlogits * W: the reverse-time loop starts from the LAST step, so the rows of the late steps go first on the
     // main stream and the early steps' rows are produced on the auxiliary stream while the loop is already running.
     const int th = (ss.overlap() && !have_cls && rows == TB && d.T >= 4) ? d.T / 2 : 0;
@@ -1191,18 +1154,14 @@ int heads_bwd(Streams& ss, const XgDims& d, const XgParams& p, const XgParams& g
         if (ss.dh_mark == -2) return XG_EHIP;
     }
     // dW_logit / db: parameter gradients, under the loop as well
-    auto dwl = [=, &ss, &w, &g]() -> int {
-        XG_TRY(tn16(ss.aux, bgm, rows, d.V, R, w.LOGITS, m16(w, w.LOGITS), d.V, Hout, hout16, R, g.logit_w, R, g.logit_b));
-        // XgRun.grad_event_head: the vocabulary head's gradients are final, long before anything else, AND logit.* is not read
-        // any more in this backward (the product above was its last reader) -- a caller may all-reduce those gradients and
-        // even update logit.* from here on
-        if (ss.grad_event_head) {
-            XG_TRY(ss.fork());
-            if (hipEventRecord(ss.grad_event_head, ss.aux) != hipSuccess) return XG_EHIP;
-        }
-        return XG_OK;
-    };
-    XG_TRY(dwl());
+    XG_TRY(tn16(ss.aux, bgm, rows, d.V, R, w.LOGITS, m16(w, w.LOGITS), d.V, Hout, hout16, R, g.logit_w, R, g.logit_b));
+    // XgRun.grad_event_head: the vocabulary head's gradients are final, long before anything else, AND logit.* is not read
+    // any more in this backward (the product above was its last reader) -- a caller may all-reduce those gradients and
+    // even update logit.* from here on
+    if (ss.grad_event_head) {
+        XG_TRY(ss.fork());
+        if (hipEventRecord(ss.grad_event_head, ss.aux) != hipSuccess) return XG_EHIP;
+    }
     if (have_cls) {
         XG_TRY(gemm_tn_cs(st, w.gm, rows, d.C, d.H, w.DCL, d.C, w.HC, d.H, g.cls3_w, d.H, g.cls3_b));
         XG_TRY(gemm_nn(st, w.gm, rows, d.H, d.C, w.DCL, d.C, p.cls3_w, d.H, w.DHC, d.H, false));
@@ -1232,6 +1191,65 @@ int check(const XgDims* d, const void* ws, size_t ws_bytes, Ws* w) {
     }
     if ((uintptr_t)ws % 256 != 0) return XG_EINVAL;
     return XG_OK;
+}
+// The gate of an entry point that takes an XgRun: the workspace tests (check), then the call's arithmetic mode and packed weights.
+// The entry point's own pointer and scalar tests follow it.
+int open_ws(const XgDims* d, void* ws, size_t ws_bytes, const XgRun* run, Ws* w) {
+    XG_TRY(check(d, ws, ws_bytes, w));
+    if (!run) return XG_EINVAL;
+    attach_packed(*w, *d, run);
+    return XG_OK;
+}
+
+// teacher-forced forward up to the logits (time-major, w.LOGITS) and the classifier head (w.CL); *rows_done: the (t,b) rows whose
+// logits (early_loss: and cross-entropy) ran on the auxiliary stream under the remaining steps
+int forward_xe_front(Streams& ss, const XgDims& d, const XgParams& p, const XgBnState* bn, const XgBatch& x, const XgRun& run, Ws& w,
+                     bool early_loss, int* rows_done) {
+    XG_TRY(ss.fork());
+    XG_TRY(decoder_tokens_xe(ss.aux, d, p, x, run, w));
+    XG_TRY(encoder_fwd(ss.main, d, p, bn, x, run, w, &ss));
+    XG_TRY(decoder_fwd_xe(ss, d, p, x, run, w, rows_done, early_loss));
+    return heads_fwd_logits(ss, d, p, run, w, d.T * d.B, *rows_done);       // (joins the auxiliary stream)
+}
+
+// dlogits (in place, w.LOGITS) and dcl (w.DCL) from the gradients of the two log-prob outputs.  have_logp: LOGITS already holds
+// log-probs (scheduled sampling); otherwise they are recomputed from the saved logits first, in place
+int dlogits_from_dlogp(hipStream_t st, const XgDims& d, Ws& w, const float* dlogp, const float* dcat_logp, bool have_logp) {
+    const int B = d.B, T = d.T, TB = T * B;
+    if (dlogp) {
+        if (!have_logp) XG_TRY(xgk_log_softmax(st, w.LOGITS, d.V, w.LOGITS, d.V, TB, d.V, 1, 1, false));
+        XG_TRY(xgk_log_softmax_bwd(st, dlogp, w.LOGITS, d.V, w.LOGITS, d.V, TB, d.V, B, T, 2));
+    } else {
+        ZERO(st, w.LOGITS, (size_t)TB * d.V);
+    }
+    if (dcat_logp) {
+        XG_TRY(xgk_log_softmax(st, w.CL, d.C, w.CL, d.C, TB, d.C, 1, 1, false));
+        XG_TRY(xgk_log_softmax_bwd(st, dcat_logp, w.CL, d.C, w.DCL, d.C, TB, d.C, B, T, 2));
+    }
+    return XG_OK;
+}
+
+// What every full backward ends with, from dlogits in w.LOGITS (and dcl in w.DCL): heads, the reverse-time pass, the encoder.
+// dT: the steps the decoder ran (the rollouts': d.T - 1); mask / tok: see decoder_bwd_core
+int backward_tail(Streams& ss, const XgDims& d, const XgDims& dT, const XgParams& p, const XgParams& g, const XgBatch& x,
+                  const XgRun& run, Ws& w, bool have_cls, const XentBwd* xent, const float* mask, int ldm, int mask_tstride,
+                  const int64_t* tok, int tok_bstride, int tok_tstride) {
+    XG_TRY(heads_bwd(ss, dT, p, g, run, w, dT.T * dT.B, have_cls, xent));
+    XG_TRY(decoder_bwd_core(ss, dT, p, g, x, run, w, mask, ldm, mask_tstride, tok, tok_bstride, tok_tstride));
+    XG_TRY(encoder_bwd(ss, d, p, g, x, run, w, w.DV));
+    return ss.join();
+}
+
+// everything but B
+bool same_model_dims(const XgDims* a, const XgDims* b) {
+    return a->K == b->K && a->R == b->R && a->A == b->A && a->E == b->E && a->V == b->V && a->T == b->T && a->F1 == b->F1 &&
+           a->F2 == b->F2 && a->C == b->C && a->H == b->H;
+}
+// what the three paired-rollout entry points ask of their common arguments (n_sample: the rows that sample)
+bool pair_args_ok(const XgDims* d2, const XgParams* p, const XgBatch* x, const XgRun* run, int n_sample, const float* uniforms,
+                  float temperature, const int64_t* seq, const float* seq_logp, const int32_t* n_steps) {
+    return p && x && run && seq && seq_logp && n_steps && x->pos_feats && d2->T >= 2 && n_sample > 0 && n_sample < d2->B && uniforms &&
+           temperature > 0.f;
 }
 
 }  // namespace
@@ -1345,22 +1363,18 @@ extern "C" int xg_workspace_init(void* stream, void* ws, size_t ws_bytes) {
 
 extern "C" int xg_encoder_fwd(void* stream, const XgDims* d, const XgParams* p, const XgBnState* bn, const XgBatch* x,
                               const XgRun* run, void* ws, size_t ws_bytes, float* V) {
-    Ws w; XG_TRY(check(d, ws, ws_bytes, &w));
-    if (!p || !x || !run || !V || !x->feats_rgb || !x->feats_opfl || !x->feat_mask) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    attach_packed(w, *d, run);
+    Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
+    if (!p || !x || !V || !x->feats_rgb || !x->feats_opfl || !x->feat_mask) return XG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     Streams es(st, run);
     XG_TRY(encoder_fwd(st, *d, *p, bn, *x, *run, w, &es));
-    if (hipMemcpyAsync(V, w.Venc, sizeof(float) * (size_t)d->B * d->K * d->R, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+    COPY(st, V, w.Venc, (size_t)d->B * d->K * d->R);
     return XG_OK;
 }
 extern "C" int xg_encoder_bwd(void* stream, const XgDims* d, const XgParams* p, const XgParams* g, const XgBatch* x,
                               const XgRun* run, void* ws, size_t ws_bytes, const float* dV) {
-    Ws w; XG_TRY(check(d, ws, ws_bytes, &w));
-    if (!p || !g || !x || !run || !dV) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    attach_packed(w, *d, run);
+    Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
+    if (!p || !g || !x || !dV) return XG_EINVAL;
     Streams ss((hipStream_t)stream, run);
     XG_TRY(encoder_bwd(ss, *d, *p, *g, *x, *run, w, dV));
     return ss.join();
@@ -1405,31 +1419,26 @@ extern "C" int xg_aux_create(void** aux) {
 }
 extern "C" int xg_vproj(void* stream, const XgDims* d, const XgParams* p, const float* V, float* vproj, const XgRun* run) {
     if (!dims_ok(d) || !p || !V || !vproj) return XG_EINVAL;
-    const int mode = run && (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;     // same arithmetic as the rollouts' own v2a(V)
-    return xgk_linear((hipStream_t)stream, mode, d->B * d->K, d->A, d->R, V, d->R, p->v2a_w, p->v2a_b, vproj, d->A);
+    // (gemm_mode_of: the same arithmetic as the rollouts' own v2a(V))
+    return xgk_linear((hipStream_t)stream, gemm_mode_of(run), d->B * d->K, d->A, d->R, V, d->R, p->v2a_w, p->v2a_b, vproj, d->A);
 }
 
 extern "C" int xg_step_fwd(void* stream, const XgDims* d, const XgParams* p, const int64_t* tokens, const float* xt_mask,
                            const float* V, const float* vproj, const float* pos_feats, const XgRun* run, int step,
                            void* ws, size_t ws_bytes, float* state, float* logp, float* alpha) {
-    Ws w; XG_TRY(check(d, ws, ws_bytes, &w));
-    if (!p || !tokens || !V || !vproj || !pos_feats || !run || !state) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
+    Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
+    if (!p || !tokens || !V || !vproj || !pos_feats || !state) return XG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int B = d->B, R = d->R, E = d->E;
     const size_t BR = (size_t)B * R;
     if ((uintptr_t)state % 16) return XG_EINVAL;
-    attach_packed(w, *d, run);
     StepIO s{};
     s.pos = pos_feats; s.gp = w.GP; s.posg = w.POSG; s.pre1 = nullptr; s.mask = xt_mask; s.ldm = 1;
     s.h1o = state; s.c1o = state + BR; s.h2o = state + 2 * BR; s.c2o = state + 3 * BR;
     s.P = w.P; s.alpha = alpha ? alpha : w.ALPHA; s.af = w.AF; s.g1 = nullptr; s.g2 = nullptr; s.t = step;
     if (run->save) {
         // a following xg_step_bwd needs the OLD state (the step overwrites it in place), the activated gates and alpha
-        if (hipMemcpyAsync(w.H1, state, sizeof(float) * BR, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(w.C1, state + BR, sizeof(float) * BR, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(w.H2, state + 2 * BR, sizeof(float) * BR, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(w.C2, state + 3 * BR, sizeof(float) * BR, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+        COPY(st, w.H1, state, BR); COPY(st, w.C1, state + BR, BR); COPY(st, w.H2, state + 2 * BR, BR); COPY(st, w.C2, state + 3 * BR, BR);
         s.g1 = w.G1; s.g2 = w.G2; s.alpha = w.ALPHA;
     }
     if (step_packed(w, *d)) {
@@ -1443,8 +1452,7 @@ extern "C" int xg_step_fwd(void* stream, const XgDims* d, const XgParams* p, con
         s.h1 = w.state_tmp; s.c1 = w.state_tmp + BR; s.h2 = w.state_tmp + 2 * BR; s.c2 = w.state_tmp + 3 * BR;
     }
     XG_TRY(core_step(st, *d, *p, *run, w, V, vproj, s));
-    if (run->save && alpha &&
-        hipMemcpyAsync(alpha, w.ALPHA, sizeof(float) * (size_t)B * d->K, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+    if (run->save && alpha) COPY(st, alpha, w.ALPHA, (size_t)B * d->K);
     if (logp) {
         XG_TRY(xgk_linear(st, w.gm, B, d->V, R, state + 2 * BR, R, p->logit_w, p->logit_b, w.LOGITS, d->V));
         XG_TRY(xgk_log_softmax(st, w.LOGITS, d->V, logp, d->V, B, d->V, 1, 1, false));
@@ -1482,7 +1490,7 @@ extern "C" int xg_step_bwd(void* stream, const XgDims* d, const XgParams* p, con
     c2.ds = w.DS2; c2.ldds = 4 * R; c2.dc_prev = dc2; c2.lddcp = R; c2.dh_prev = dh2; c2.lddhp = R;
     c2.B = B; c2.R = R; c2.order = XG_ORDER_IFOG; c2.mask_mode = XG_MASK_HOLD; c2.drop = xg_make_drop(run, XG_SITE_L2, step);
     XG_TRY(xgk_lstm_bwd(st, c2));
-    if (hipMemcpyAsync(dh1n, dstate_new, sizeof(float) * BR, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+    COPY(st, dh1n, dstate_new, BR);
     XG_TRY(gemm_nn(st, 0, B, R, 4 * R, w.DS2, 4 * R, p->l2_i2h_w, R, dh1n, R, true));
     XG_TRY(gemm_nn(st, 0, B, R, 4 * R, w.DS2, 4 * R, p->l2_a2h_w, R, daf, R, false));
     XG_TRY(gemm_nn(st, 0, B, R, 4 * R, w.DS2, 4 * R, p->l2_h2h_w, R, dh2, R, true));
@@ -1526,19 +1534,13 @@ extern "C" int xg_step_bwd(void* stream, const XgDims* d, const XgParams* p, con
 
 extern "C" int xg_forward_xe(void* stream, const XgDims* d, const XgParams* p, const XgBnState* bn, const XgBatch* x,
                              const XgRun* run, void* ws, size_t ws_bytes, float* logp, float* cat_logp) {
-    Ws w; XG_TRY(check(d, ws, ws_bytes, &w));
-    if (!p || !x || !run || !logp || !x->seq || !x->seq_mask || !x->pos_feats) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    attach_packed(w, *d, run);
+    Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
+    if (!p || !x || !logp || !x->seq || !x->seq_mask || !x->pos_feats) return XG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int TB = d->T * d->B;
     Streams ss(st, run);
     int rows_done = 0;
-    XG_TRY(ss.fork());
-    XG_TRY(decoder_tokens_xe(ss.aux, *d, *p, *x, *run, w));
-    XG_TRY(encoder_fwd(st, *d, *p, bn, *x, *run, w, &ss));
-    XG_TRY(decoder_fwd_xe(ss, *d, *p, *x, *run, w, &rows_done));
-    XG_TRY(heads_fwd_logits(ss, *d, *p, *run, w, TB, rows_done));
+    XG_TRY(forward_xe_front(ss, *d, *p, bn, *x, *run, w, false, &rows_done));
     XG_TRY(xgk_log_softmax(st, w.LOGITS, d->V, logp, d->V, TB, d->V, d->B, d->T, true));
     if (cat_logp) XG_TRY(xgk_log_softmax(st, w.CL, d->C, cat_logp, d->C, TB, d->C, d->B, d->T, true));
     return XG_OK;
@@ -1546,41 +1548,23 @@ extern "C" int xg_forward_xe(void* stream, const XgDims* d, const XgParams* p, c
 
 extern "C" int xg_backward_xe(void* stream, const XgDims* d, const XgParams* p, const XgParams* g, const XgBatch* x,
                               const XgRun* run, void* ws, size_t ws_bytes, const float* dlogp, const float* dcat_logp) {
-    Ws w; XG_TRY(check(d, ws, ws_bytes, &w));
-    if (!p || !g || !x || !run || !x->seq || !x->seq_mask) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    attach_packed(w, *d, run);
+    Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
+    if (!p || !g || !x || !x->seq || !x->seq_mask) return XG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const int B = d->B, T = d->T, TB = T * B;
-    // log-softmax backward needs logp = logits - lse: recompute lse rows from the saved logits (in place)
-    if (dlogp) {
-        XG_TRY(xgk_log_softmax(st, w.LOGITS, d->V, w.LOGITS, d->V, TB, d->V, 1, 1, false));
-        XG_TRY(xgk_log_softmax_bwd(st, dlogp, w.LOGITS, d->V, w.LOGITS, d->V, TB, d->V, B, T, 2));
-    } else {
-        ZERO(w.LOGITS, (size_t)TB * d->V);
-    }
-    if (dcat_logp) {
-        XG_TRY(xgk_log_softmax(st, w.CL, d->C, w.CL, d->C, TB, d->C, 1, 1, false));
-        XG_TRY(xgk_log_softmax_bwd(st, dcat_logp, w.CL, d->C, w.DCL, d->C, TB, d->C, B, T, 2));
-    }
+    XG_TRY(dlogits_from_dlogp(st, *d, w, dlogp, dcat_logp, false));
     Streams ss(st, run);
-    XG_TRY(heads_bwd(ss, *d, *p, *g, *run, w, TB, dcat_logp != nullptr));
-    XG_TRY(decoder_bwd_core(ss, *d, *p, *g, *x, *run, w, x->seq_mask, T, 1, x->seq, T, 1));
-    XG_TRY(encoder_bwd(ss, *d, *p, *g, *x, *run, w, w.DV));
-    return ss.join();
+    return backward_tail(ss, *d, *d, *p, *g, *x, *run, w, dcat_logp != nullptr, nullptr, x->seq_mask, d->T, 1, x->seq, d->T, 1);
 }
 
 extern "C" int xg_forward_ss(void* stream, const XgDims* d, const XgParams* p, const XgBnState* bn, const XgBatch* x,
                              const XgRun* run, float ss_prob, const float* u_sel, const float* u_tok, void* ws,
                              size_t ws_bytes, float* logp, float* cat_logp) {
-    Ws w; XG_TRY(check(d, ws, ws_bytes, &w));
-    if (!p || !x || !run || !logp || !x->seq || !x->seq_mask || !x->pos_feats) return XG_EINVAL;
+    Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
+    if (!p || !x || !logp || !x->seq || !x->seq_mask || !x->pos_feats) return XG_EINVAL;
     const bool ss = run->train && ss_prob > 0.f;
     if (ss && (!u_sel || !u_tok)) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    attach_packed(w, *d, run);
     hipStream_t st = (hipStream_t)stream;
-    const int B = d->B, R = d->R, E = d->E, A = d->A, T = d->T, TB = T * B;
+    const int B = d->B, R = d->R, E = d->E, T = d->T, TB = T * B;
     const size_t BR = (size_t)B * R;
     Streams es(st, run);
     XG_TRY(encoder_fwd(st, *d, *p, bn, *x, *run, w, &es));
@@ -1596,13 +1580,8 @@ extern "C" int xg_forward_ss(void* stream, const XgDims* d, const XgParams* p, c
         XG_TRY(xgk_ss_select(st, x->seq, T, t, B, draw ? u_sel + (size_t)t * B : nullptr, ss_prob, draw ? sampled : nullptr, tok));
         float* xt = w.Xe + (size_t)t * B * E;
         XG_TRY(xgk_embed_gather(st, p->embed_w, E, tok, B, 1, 0, B, d->V, xt, E));
-        StepIO s{};
-        s.xt = xt; s.pos = x->pos_feats; s.gp = w.GP + t * BR; s.posg = w.POSG + t * BR; s.pre1 = nullptr;
-        s.mask = x->seq_mask + t; s.ldm = T;
-        s.h1 = w.H1 + t * BR; s.c1 = w.C1 + t * BR; s.h2 = w.H2 + t * BR; s.c2 = w.C2 + t * BR;
-        s.h1o = w.H1 + (t + 1) * BR; s.c1o = w.C1 + (t + 1) * BR; s.h2o = w.H2 + (t + 1) * BR; s.c2o = w.C2 + (t + 1) * BR;
-        s.P = w.P + (size_t)t * B * A; s.alpha = w.ALPHA + (size_t)t * B * d->K; s.af = w.AF + t * BR;
-        s.g1 = w.G1 + (size_t)t * B * 4 * R; s.g2 = w.G2 + (size_t)t * B * 4 * R; s.t = t;
+        StepIO s = step_io_at(w, *d, t);
+        s.pos = x->pos_feats; s.gp = w.GP + t * BR; s.mask = x->seq_mask + t; s.ldm = T;
         XG_TRY(core_step(st, *d, *p, *run, w, w.Venc, w.vproj, s));
         float* lg = w.LOGITS + (size_t)t * B * d->V;
         XG_TRY(xgk_linear(st, w.gm, B, d->V, R, s.h2o, R, p->logit_w, p->logit_b, lg, d->V));
@@ -1610,60 +1589,36 @@ extern "C" int xg_forward_ss(void* stream, const XgDims* d, const XgParams* p, c
     }
     // (T*B,V) time-major log-probs -> (B,T,V); classifier head batched over T as in xg_forward_xe
     XG_TRY(xgk_log_softmax(st, w.LOGITS, d->V, logp, d->V, TB, d->V, B, T, true));    // log_softmax of log-probs = identity
-    const float* Hout = w.H2 + BR;
-    XG_TRY(xgk_linear(st, w.gm, TB, d->H, R, Hout, R, p->cls0_w, p->cls0_b, w.HC, d->H, true));
-    XG_TRY(xgk_gate_fwd(st, w.HC, d->H, nullptr, 0, 0, nullptr, 0, TB, d->H, xg_make_drop(run, XG_SITE_CLS, 0), B, 1 << 30, 1, B));
-    XG_TRY(xgk_linear(st, w.gm, TB, d->C, d->H, w.HC, d->H, p->cls3_w, p->cls3_b, w.CL, d->C));
+    XG_TRY(classifier_fwd(st, *d, *p, *run, w, TB));
     if (cat_logp) XG_TRY(xgk_log_softmax(st, w.CL, d->C, cat_logp, d->C, TB, d->C, B, T, true));
     return XG_OK;
 }
 
 extern "C" int xg_backward_ss(void* stream, const XgDims* d, const XgParams* p, const XgParams* g, const XgBatch* x,
                               const XgRun* run, void* ws, size_t ws_bytes, const float* dlogp, const float* dcat_logp) {
-    Ws w; XG_TRY(check(d, ws, ws_bytes, &w));
-    if (!p || !g || !x || !run || !x->seq || !x->seq_mask) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    attach_packed(w, *d, run);
+    Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
+    if (!p || !g || !x || !x->seq || !x->seq_mask) return XG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const int B = d->B, T = d->T, TB = T * B;
-    if (dlogp) {   // LOGITS already holds the time-major log-probs
-        XG_TRY(xgk_log_softmax_bwd(st, dlogp, w.LOGITS, d->V, w.LOGITS, d->V, TB, d->V, B, T, 2));
-    } else {
-        ZERO(w.LOGITS, (size_t)TB * d->V);
-    }
-    if (dcat_logp) {
-        XG_TRY(xgk_log_softmax(st, w.CL, d->C, w.CL, d->C, TB, d->C, 1, 1, false));
-        XG_TRY(xgk_log_softmax_bwd(st, dcat_logp, w.CL, d->C, w.DCL, d->C, TB, d->C, B, T, 2));
-    }
+    XG_TRY(dlogits_from_dlogp(st, *d, w, dlogp, dcat_logp, true));      // LOGITS already holds the time-major log-probs
     Streams ss(st, run);
-    XG_TRY(heads_bwd(ss, *d, *p, *g, *run, w, TB, dcat_logp != nullptr));
-    XG_TRY(decoder_bwd_core(ss, *d, *p, *g, *x, *run, w, x->seq_mask, T, 1, w.TOK, 1, B));
-    XG_TRY(encoder_bwd(ss, *d, *p, *g, *x, *run, w, w.DV));
-    return ss.join();
+    return backward_tail(ss, *d, *d, *p, *g, *x, *run, w, dcat_logp != nullptr, nullptr, x->seq_mask, d->T, 1, w.TOK, 1, d->B);
 }
 
 extern "C" int xg_xe_loss_fwd(void* stream, const XgDims* d, const XgParams* p, const XgBnState* bn, const XgBatch* x,
                               const int64_t* cap_classes, const float* class_mask, float weight_class, const XgRun* run,
                               void* ws, size_t ws_bytes, float* losses) {
-    Ws w; XG_TRY(check(d, ws, ws_bytes, &w));
-    if (!p || !x || !run || !losses || !x->seq || !x->seq_mask || !x->pos_feats) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    attach_packed(w, *d, run);
+    Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
+    if (!p || !x || !losses || !x->seq || !x->seq_mask || !x->pos_feats) return XG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const int TB = d->T * d->B;
     Streams ss(st, run);
     int rows_done = 0;
-    ZERO(w.sums, 2);                           // both halves of the cross-entropy add into it
-    XG_TRY(ss.fork());
-    XG_TRY(decoder_tokens_xe(ss.aux, *d, *p, *x, *run, w));
-    XG_TRY(encoder_fwd(st, *d, *p, bn, *x, *run, w, &ss));
-    XG_TRY(decoder_fwd_xe(ss, *d, *p, *x, *run, w, &rows_done, true));
-    XG_TRY(heads_fwd_logits(ss, *d, *p, *run, w, TB, rows_done));       // (joins the auxiliary stream)
+    ZERO(st, w.sums, 2);                       // both halves of the cross-entropy add into it
+    XG_TRY(forward_xe_front(ss, *d, *p, bn, *x, *run, w, true, &rows_done));
     XG_TRY(xgk_xent_fwd(st, w.LOGITS, d->V, x->seq, x->seq_mask, nullptr, d->B, d->T, d->V, 1, w.LSE, w.sums, rows_done, -1, false));
     if (cap_classes) {
         XG_TRY(xgk_xent_fwd(st, w.CL, d->C, cap_classes, x->seq_mask, class_mask, d->B, d->T, d->C, 0, w.LSEC, w.sums + 2));
     } else {
-        ZERO(w.sums + 2, 2);
+        ZERO(st, w.sums + 2, 2);
     }
     hipLaunchKernelGGL(losses_kernel, dim3(1), dim3(1), 0, st, w.sums, cap_classes ? weight_class : 0.f, losses);
     XG_CHECK_LAUNCH();
@@ -1672,24 +1627,19 @@ extern "C" int xg_xe_loss_fwd(void* stream, const XgDims* d, const XgParams* p, 
 extern "C" int xg_xe_loss_bwd(void* stream, const XgDims* d, const XgParams* p, const XgParams* g, const XgBatch* x,
                               const int64_t* cap_classes, const float* class_mask, float weight_class,
                               const float* dloss_dev, const XgRun* run, void* ws, size_t ws_bytes) {
-    Ws w; XG_TRY(check(d, ws, ws_bytes, &w));
-    if (!p || !g || !x || !run || !x->seq || !x->seq_mask) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    attach_packed(w, *d, run);
+    Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
+    if (!p || !g || !x || !x->seq || !x->seq_mask) return XG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const int B = d->B, T = d->T, TB = T * B;
+    const int B = d->B, T = d->T;
     const XentBwd xent{x->seq, x->seq_mask, dloss_dev};
     const bool cls = cap_classes != nullptr && weight_class != 0.f;
     if (cls) {
-        if (hipMemcpyAsync(w.DCL, w.CL, sizeof(float) * (size_t)TB * d->C, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+        COPY(st, w.DCL, w.CL, (size_t)T * B * d->C);
         XG_TRY(xgk_xent_bwd(st, w.DCL, d->C, cap_classes, x->seq_mask, class_mask, B, T, d->C, 0, w.LSEC, w.sums + 2,
                             dloss_dev, weight_class));
     }
     Streams ss(st, run);
-    XG_TRY(heads_bwd(ss, *d, *p, *g, *run, w, TB, cls, &xent));
-    XG_TRY(decoder_bwd_core(ss, *d, *p, *g, *x, *run, w, x->seq_mask, T, 1, x->seq, T, 1));
-    XG_TRY(encoder_bwd(ss, *d, *p, *g, *x, *run, w, w.DV));
-    return ss.join();
+    return backward_tail(ss, *d, *d, *p, *g, *x, *run, w, cls, &xent, x->seq_mask, T, 1, x->seq, T, 1);
 }
 
 // One rollout over d.B rows.  split < d.B (SAMPLE mode only): rows [0, split) sample with uniforms (T, split), rows
@@ -1707,7 +1657,6 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
                         int64_t* seq, float* seq_logp, int32_t* n_steps, int split, float* logits_alt = nullptr,
                         bool* used_alt = nullptr, const XgDims* d1 = nullptr, Ws* enc = nullptr) {
     const int B = d->B, R = d->R, E = d->E, A = d->A, T = d->T;
-    const size_t BR = (size_t)B * R;
     Streams es(st, run);
     const float* pos_rows = x->pos_feats;
     if (enc) {
@@ -1734,7 +1683,7 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
     }
     XG_TRY(zero_dsync(st, w));
     if (hipMemsetAsync(w.alive, 0, sizeof(int32_t) * 4, st) != hipSuccess) return XG_EHIP;   // alive[i] = running max finishing step
-    if (run->prof_event0 && hipEventRecord(static_cast<hipEvent_t>(run->prof_event0), st) != hipSuccess) return XG_EHIP;
+    XG_TRY(record_prof(run->prof_event0, st));
     // Rollout steps of <= 128 rows, fp32: the vocabulary product leaves per-tile row statistics and the token choice reads those
     // (xg_heads.hip: vocab_part_kernel / roll_select_kernel) -- 10 MB of logits per step are neither written (greedy rows) nor read
     // back three times.  Rows whose logits are needed afterwards are still stored: sampled rows (the draw re-reads one tile; the
@@ -1745,16 +1694,6 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
     const bool alt = logits_alt != nullptr && fused_select && mode == XG_ROLLOUT_SAMPLE && split < B;
     if (used_alt) *used_alt = alt;
     auto logits_of = [&](int t) { return alt ? logits_alt + (size_t)t * split * d->V : w.LOGITS + (size_t)t * B * d->V; };
-    auto step_io = [&](int t) {
-        StepIO s{};
-        s.xt = w.Xe + (size_t)t * B * E; s.pos = pos_rows; s.gp = w.GP + t * BR; s.posg = w.POSG + t * BR; s.pre1 = nullptr;
-        s.mask = w.UNF + (size_t)t * B; s.ldm = 1;
-        s.h1 = w.H1 + t * BR; s.c1 = w.C1 + t * BR; s.h2 = w.H2 + t * BR; s.c2 = w.C2 + t * BR;
-        s.h1o = w.H1 + (t + 1) * BR; s.c1o = w.C1 + (t + 1) * BR; s.h2o = w.H2 + (t + 1) * BR; s.c2o = w.C2 + (t + 1) * BR;
-        s.P = w.P + (size_t)t * B * A; s.alpha = w.ALPHA + (size_t)t * B * d->K; s.af = w.AF + t * BR;
-        s.g1 = w.G1 + (size_t)t * B * 4 * R; s.g2 = w.G2 + (size_t)t * B * 4 * R; s.t = t;
-        return s;
-    };
     // Steps t >= 1 on the packed fp32 path CHOOSE their tokens themselves: the choice is the prologue of the step's first launch
     // (its POS-gate tiles: xg_step.hip SEL, xg_select.h) instead of a launch of its own between the vocabulary product and the step
     // -- four dependent launches per step instead of five.  The last choice of a rollout (no step follows) keeps its launch.
@@ -1767,24 +1706,16 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
         const float* prev_logits = t >= 1 ? logits_of(t - 1) : nullptr;
         // token choice from the previous step's raw logits + bookkeeping + embedding gather: one launch (:183-215)
         const bool in_step = step_select && t >= 1 && t + 1 < T;
+        // (nothing was chosen before t = 1: no forced token, no log-sum-exp row; no `unfinished` row before t = 2)
+        const RollStepArgs ra{prev_logits, uniforms ? uniforms + (size_t)t * split : nullptr, (forced && t >= 1) ? forced + (t - 1) : nullptr,
+                              T - 1, t >= 2 ? unf - B : nullptr, p->embed_w, tok, w.TOKLP + (size_t)t * B, unf,
+                              t >= 1 ? w.LSE + (size_t)(t - 1) * B : nullptr, seq, seq_logp, w.alive, xt, temperature, d->V, E, t, T, mode, split};
         RollSelectArgs sel{};
-        if (in_step)
-            sel = xgk_roll_select_args(prev_logits, w.VPART, uniforms ? uniforms + (size_t)t * split : nullptr,
-                                       forced ? forced + (t - 1) : nullptr, T - 1, t >= 2 ? unf - B : nullptr, p->embed_w, tok,
-                                       w.TOKLP + (size_t)t * B, unf, w.LSE + (size_t)(t - 1) * B, seq, seq_logp, w.alive, xt, temperature,
-                                       d->V, E, t, T, mode, split);
-        else if (t >= 1 && fused_select)
-            XG_TRY(xgk_roll_select(st, B, prev_logits, w.VPART, uniforms ? uniforms + (size_t)t * split : nullptr,
-                                   forced ? forced + (t - 1) : nullptr, T - 1, t >= 2 ? unf - B : nullptr, p->embed_w, tok,
-                                   w.TOKLP + (size_t)t * B, unf, w.LSE + (size_t)(t - 1) * B, seq, seq_logp, w.alive, xt, temperature,
-                                   d->V, E, t, T, mode, split));
-        else
-            XG_TRY(xgk_rollout_step(st, B, prev_logits,
-                                    uniforms ? uniforms + (size_t)t * split : nullptr, (forced && t >= 1) ? forced + (t - 1) : nullptr,
-                                    T - 1, t >= 2 ? unf - B : nullptr, p->embed_w, tok, w.TOKLP + (size_t)t * B, unf,
-                                    t >= 1 ? w.LSE + (size_t)(t - 1) * B : nullptr, seq, seq_logp, w.alive, xt, temperature, d->V, E,
-                                    t, T, mode, split));
-        StepIO s = step_io(t);
+        if (in_step) sel = xgk_roll_select_args(ra, w.VPART);
+        else if (t >= 1 && fused_select) XG_TRY(xgk_roll_select(st, B, ra, w.VPART));
+        else XG_TRY(xgk_rollout_step(st, B, ra));
+        StepIO s = step_io_at(w, *d, t);
+        s.pos = pos_rows; s.gp = w.GP + (size_t)t * B * R; s.mask = unf; s.ldm = 1;
         if (in_step) { s.sel = &sel; s.xt = nullptr; s.tok = tok; }
         // The reference runs the core once more at t = L and discards what it computes (SAModel.py:182,217: the loop ends before
         // those logits are ever read, and no state is returned): that step feeds neither an output nor a gradient and is not run.
@@ -1802,31 +1733,25 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
     // compaction) reads is made here for all of them at once, off the token's path
     if (step_select && T >= 3)
         XG_TRY(xgk_embed_gather(st, p->embed_w, E, w.TOK + B, (T - 2) * B, 1, 0, (T - 2) * B, d->V, w.Xe + (size_t)B * E, E));
-    if (run->prof_event1 && hipEventRecord(static_cast<hipEvent_t>(run->prof_event1), st) != hipSuccess) return XG_EHIP;
-    XG_TRY(xgk_rollout_finalize(st, w.alive, n_steps, T - 1, split < B ? 2 : 1));
-    return XG_OK;
+    XG_TRY(record_prof(run->prof_event1, st));
+    return xgk_rollout_finalize(st, w.alive, n_steps, T - 1, split < B ? 2 : 1);
 }
 
 extern "C" int xg_rollout(void* stream, const XgDims* d, const XgParams* p, const XgBnState* bn, const XgBatch* x,
                           const XgRun* run, int mode, const float* uniforms, const int64_t* forced, float temperature,
                           void* ws, size_t ws_bytes, int64_t* seq, float* seq_logp, int32_t* n_steps) {
-    Ws w; XG_TRY(check(d, ws, ws_bytes, &w));
-    if (!p || !x || !run || !seq || !seq_logp || !n_steps || !x->pos_feats || d->T < 2) return XG_EINVAL;
+    Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
+    if (!p || !x || !seq || !seq_logp || !n_steps || !x->pos_feats || d->T < 2) return XG_EINVAL;
     if (mode == XG_ROLLOUT_SAMPLE && (!uniforms || !(temperature > 0.f))) return XG_EINVAL;
     if (mode == XG_ROLLOUT_REPLAY && !forced) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    attach_packed(w, *d, run);
     return rollout_impl((hipStream_t)stream, d, p, bn, x, run, mode, uniforms, forced, temperature, w, seq, seq_logp, n_steps, d->B);
 }
 
 extern "C" int xg_rollout_pair(void* stream, const XgDims* d2, const XgParams* p, const XgBnState* bn, const XgBatch* x2,
                                const XgRun* run, int n_sample, const float* uniforms, float temperature, void* ws2,
                                size_t ws2_bytes, int64_t* seq, float* seq_logp, int32_t* n_steps) {
-    Ws w; XG_TRY(check(d2, ws2, ws2_bytes, &w));
-    if (!p || !x2 || !run || !seq || !seq_logp || !n_steps || !x2->pos_feats || d2->T < 2) return XG_EINVAL;
-    if (n_sample <= 0 || n_sample >= d2->B || !uniforms || !(temperature > 0.f)) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    attach_packed(w, *d2, run);
+    Ws w; XG_TRY(open_ws(d2, ws2, ws2_bytes, run, &w));
+    if (!pair_args_ok(d2, p, x2, run, n_sample, uniforms, temperature, seq, seq_logp, n_steps)) return XG_EINVAL;
     return rollout_impl((hipStream_t)stream, d2, p, bn, x2, run, XG_ROLLOUT_SAMPLE, uniforms, nullptr, temperature, w, seq,
                         seq_logp, n_steps, n_sample);
 }
@@ -1834,8 +1759,7 @@ extern "C" int xg_rollout_pair(void* stream, const XgDims* d2, const XgParams* p
 // Everything xg_rollout_bwd reads, for the FIRST d1->B rows of a rollout that ran over d2->B >= d1->B rows: encoder-side
 // tensors are row prefixes, decoder-side tensors are per-step blocks (pitch B2 -> B1).
 static int compact_impl(hipStream_t st, const XgDims* d2, const Ws& a, const XgDims* d1, Ws& b, bool skip_logits, bool skip_encoder = false) {
-    if (d1->B > d2->B || d1->K != d2->K || d1->R != d2->R || d1->A != d2->A || d1->E != d2->E || d1->V != d2->V ||
-        d1->T != d2->T || d1->F1 != d2->F1 || d1->F2 != d2->F2 || d1->C != d2->C || d1->H != d2->H) return XG_EINVAL;
+    if (d1->B > d2->B || !same_model_dims(d1, d2)) return XG_EINVAL;
     const size_t B1 = d1->B, B2 = d2->B, K = d1->K, R = d1->R, A = d1->A, E = d1->E, V = d1->V, T = d1->T, N1 = B1 * K;
     CompactArgs ca{};
     auto prefix = [&](void* dst, const void* src, size_t nfloats) -> int {
@@ -1869,7 +1793,7 @@ static int compact_impl(hipStream_t st, const XgDims* d2, const Ws& a, const XgD
     XG_TRY(blocks(b.TOK, a.TOK, 2, T));                       // int64 = 2 floats wide
     XG_TRY(blocks(b.TOKLP, a.TOKLP, 1, T)); XG_TRY(blocks(b.UNF, a.UNF, 1, T));
     XG_TRY(xgk_compact(st, ca));
-    ZERO(b.zeroBR, B1 * R);                                   // the encoder's initial state (read by its backward)
+    ZERO(st, b.zeroBR, B1 * R);                                 // the encoder's initial state (read by its backward)
     return XG_OK;
 }
 
@@ -1891,9 +1815,7 @@ extern "C" int xg_rollout_pair_compact(void* stream, const XgDims* d2, const XgP
     Ws w, b;
     XG_TRY(check(d2, ws2, ws2_bytes, &w));
     XG_TRY(check(d1, ws1, ws1_bytes, &b));
-    if (!p || !x2 || !run || !seq || !seq_logp || !n_steps || !x2->pos_feats || d2->T < 2) return XG_EINVAL;
-    if (n_sample <= 0 || n_sample >= d2->B || n_sample != d1->B || !uniforms || !(temperature > 0.f)) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
+    if (!pair_args_ok(d2, p, x2, run, n_sample, uniforms, temperature, seq, seq_logp, n_steps) || n_sample != d1->B) return XG_EINVAL;
     attach_packed(w, *d2, run);
     bool used_alt = false;
     XG_TRY(rollout_impl((hipStream_t)stream, d2, p, bn, x2, run, XG_ROLLOUT_SAMPLE, uniforms, nullptr, temperature, w, seq, seq_logp,
@@ -1908,13 +1830,8 @@ extern "C" int xg_rollout_pair_videos(void* stream, const XgDims* d2, const XgPa
     Ws w, b;
     XG_TRY(check(d2, ws2, ws2_bytes, &w));
     XG_TRY(check(d1, ws1, ws1_bytes, &b));
-    if (!p || !x1 || !run || !seq || !seq_logp || !n_steps || !x1->pos_feats || !x1->feats_rgb || !x1->feats_opfl || !x1->feat_mask ||
-        d2->T < 2) return XG_EINVAL;
-    if (d2->B != 2 * d1->B || !uniforms || !(temperature > 0.f) || ws1 == ws2) return XG_EINVAL;
-    if (d1->K != d2->K || d1->R != d2->R || d1->A != d2->A || d1->E != d2->E || d1->V != d2->V || d1->T != d2->T ||
-        d1->F1 != d2->F1 || d1->F2 != d2->F2 || d1->C != d2->C || d1->H != d2->H) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    b.gm = w.gm;
+    if (!pair_args_ok(d2, p, x1, run, d1->B, uniforms, temperature, seq, seq_logp, n_steps)) return XG_EINVAL;
+    if (!x1->feats_rgb || !x1->feats_opfl || !x1->feat_mask || d2->B != 2 * d1->B || ws1 == ws2 || !same_model_dims(d1, d2)) return XG_EINVAL;
     attach_packed(w, *d2, run);
     attach_packed(b, *d1, run);
     bool used_alt = false;
@@ -1926,10 +1843,8 @@ extern "C" int xg_rollout_pair_videos(void* stream, const XgDims* d2, const XgPa
 
 extern "C" int xg_rollout_bwd(void* stream, const XgDims* d, const XgParams* p, const XgParams* g, const XgBatch* x,
                               const XgRun* run, void* ws, size_t ws_bytes, const float* dseq_logp) {
-    Ws w; XG_TRY(check(d, ws, ws_bytes, &w));
-    if (!p || !g || !x || !run || !dseq_logp || d->T < 2) return XG_EINVAL;
-    w.gm = (run->gemm_mode == 1 || run->gemm_mode == 3) ? run->gemm_mode : 0;
-    attach_packed(w, *d, run);
+    Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
+    if (!p || !g || !x || !dseq_logp || d->T < 2) return XG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int B = d->B, T = d->T;
     // dlogits of step t-1's output from the token drawn at step t (SAModel.py:195)
@@ -1945,13 +1860,10 @@ extern "C" int xg_rollout_bwd(void* stream, const XgDims* d, const XgParams* p, 
     // the rollout ran T - 1 core steps (the reference's last one is dead, rollout_impl): the reverse-time pass covers those.
     // All per-step buffers are time-major, so the first T - 1 blocks of the T-step workspace are the (T - 1)-step problem.
     // (What that relies on: LOGITS / H2 / the saved gates, states, p, alpha, af, xt and the gate values are (T, B, .) blocks with
-    //  t outermost -- carve_workspace -- so rows [0, (T - 1) B) of each are exactly what a (T - 1)-step workspace would hold, and
+    //  t outermost -- carve -- so rows [0, (T - 1) B) of each are exactly what a (T - 1)-step workspace would hold, and
     //  heads_bwd's split of dH into an early and a late half plus its background product see rows == dT.T * B as in the
     //  teacher-forced backward: the same code path, covered by the SCST gradient tests at configs[2]'s full size.)
     XgDims dT = *d;
     dT.T = T - 1;
-    XG_TRY(heads_bwd(ss, dT, *p, *g, *run, w, (T - 1) * B, false));
-    XG_TRY(decoder_bwd_core(ss, dT, *p, *g, *x, *run, w, w.UNF, 1, B, w.TOK, 1, B));
-    XG_TRY(encoder_bwd(ss, *d, *p, *g, *x, *run, w, w.DV));
-    return ss.join();
+    return backward_tail(ss, *d, dT, *p, *g, *x, *run, w, false, nullptr, w.UNF, 1, B, w.TOK, 1, B);
 }

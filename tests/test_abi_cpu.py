@@ -174,3 +174,148 @@ def test_product_library_has_no_low_lane_operand_select_on_packed_fp32(built):
     assert len(objs) >= 8, "no gfx950 code objects found in %s" % built      # one per .hip translation unit
     low = [(sym, ins) for sym, ins in chk.packed_opsel_sites(built) if re.search(r"\bop_sel:\[", ins)]
     assert not low, "packed fp32 with low-lane operand select in the product library: %s" % low[:4]
+
+
+# ---- the argument gate of every workspace-taking entry point (no call below gets past it, so nothing is enqueued)
+_FAKE = 0x7F0000000000                # stands in for every pointer: 256-byte aligned, never dereferenced
+_HUGE = 1 << 40
+_DIMS = ("B", "K", "R", "A", "E", "V", "C", "H", "F1", "F2", "T")
+# arguments in ABI order.  d / d2 / d1: XgDims; p / g: XgParams; bn, x, run: the structs; ws* / bytes*: a workspace and its size;
+# a name of _SCALARS: that value; every other name: a device pointer
+_ENTRY = {
+    "xg_encoder_fwd": "stream d p bn x run ws bytes V",
+    "xg_encoder_bwd": "stream d p g x run ws bytes dV",
+    "xg_init_hidden": "stream d p V feat_mask ws bytes state",
+    "xg_step_fwd": "stream d p tokens xt_mask V vproj pos_feats run step ws bytes state logp alpha",
+    "xg_step_bwd": "stream d p g tokens xt_mask V vproj pos_feats run step ws bytes state_new dstate_new dstate dV_out dvproj dpos",
+    "xg_forward_xe": "stream d p bn x run ws bytes logp cat_logp",
+    "xg_backward_xe": "stream d p g x run ws bytes dlogp dcat_logp",
+    "xg_forward_ss": "stream d p bn x run ss_prob u_sel u_tok ws bytes logp cat_logp",
+    "xg_backward_ss": "stream d p g x run ws bytes dlogp dcat_logp",
+    "xg_xe_loss_fwd": "stream d p bn x cap_classes class_mask weight_class run ws bytes losses",
+    "xg_xe_loss_bwd": "stream d p g x cap_classes class_mask weight_class dloss run ws bytes",
+    "xg_rollout": "stream d p bn x run mode uniforms forced temperature ws bytes seq seq_logp n_steps",
+    "xg_rollout_pair": "stream d2 p bn x run n_sample uniforms temperature ws2 bytes2 seq seq_logp n_steps",
+    "xg_rollout_compact": "stream d2 ws2 bytes2 d1 ws1 bytes1",
+    "xg_rollout_pair_compact": "stream d2 p bn x run n_sample uniforms temperature ws2 bytes2 d1 ws1 bytes1 seq seq_logp n_steps",
+    "xg_rollout_pair_videos": "stream d2 p bn x run uniforms temperature ws2 bytes2 d1 ws1 bytes1 compact seq seq_logp n_steps",
+    "xg_rollout_bwd": "stream d p g x run ws bytes dseq_logp",
+}
+_SCALARS = dict(step=0, ss_prob=0.5, weight_class=1.0, mode=0, temperature=1.0, n_sample=5, compact=1)
+# what each entry point tests after its workspace(s): (arguments, XgBatch fields) that must not be NULL
+_REQUIRED = {
+    "xg_encoder_fwd": ("p x run V", "feats_rgb feats_opfl feat_mask"),
+    "xg_encoder_bwd": ("p g x run dV", ""),
+    "xg_init_hidden": ("p V feat_mask state", ""),
+    "xg_step_fwd": ("p tokens V vproj pos_feats run state", ""),
+    "xg_step_bwd": ("p g tokens V vproj pos_feats run state_new dstate_new dstate", ""),
+    "xg_forward_xe": ("p x run logp", "seq seq_mask pos_feats"),
+    "xg_backward_xe": ("p g x run", "seq seq_mask"),
+    "xg_forward_ss": ("p x run logp u_sel u_tok", "seq seq_mask pos_feats"),      # (u_*: run.train and ss_prob > 0 here)
+    "xg_backward_ss": ("p g x run", "seq seq_mask"),
+    "xg_xe_loss_fwd": ("p x run losses", "seq seq_mask pos_feats"),
+    "xg_xe_loss_bwd": ("p g x run", "seq seq_mask"),
+    "xg_rollout": ("p x run seq seq_logp n_steps", "pos_feats"),
+    "xg_rollout_pair": ("p x run seq seq_logp n_steps uniforms", "pos_feats"),
+    "xg_rollout_compact": ("", ""),
+    "xg_rollout_pair_compact": ("p x run seq seq_logp n_steps uniforms", "pos_feats"),
+    "xg_rollout_pair_videos": ("p x run seq seq_logp n_steps uniforms", "pos_feats feats_rgb feats_opfl feat_mask"),
+    "xg_rollout_bwd": ("p g x run dseq_logp", ""),
+}
+
+
+def _gate_call(nv, L, name, dims=None, batch=None, **over):
+    """Call `name` with fake pointers everywhere.  dims: {"d": {"B": 0}} changes fields of that XgDims argument; batch: fields of the
+    XgBatch; over: an argument by name (None = NULL)."""
+    t = pg.make_dims(**CFG["tiny"])
+    keep, args = [], []
+    for a in _ENTRY[name].split():
+        if a in over:
+            v = over[a]
+        elif a == "stream":
+            v = None
+        elif a in ("d", "d1", "d2"):
+            f = dict(zip(_DIMS, (t.B, t.K, t.R, t.A, t.E, t.V, t.C, t.H, t.F1, t.F2, t.L + 1)))
+            if a == "d2":
+                f["B"] = 2 * t.B
+            f.update((dims or {}).get(a, {}))
+            v = nv.XgDims(*[f[k] for k in _DIMS])
+        elif a in ("p", "g"):
+            v = nv.XgParams()
+            for fld, _ in v._fields_:
+                setattr(v, fld, _FAKE)
+        elif a == "bn":
+            v = nv.XgBnState(_FAKE, _FAKE, _FAKE, _FAKE)
+        elif a == "x":
+            f = dict.fromkeys((n for n, _ in nv.XgBatch._fields_), _FAKE)
+            f.update(batch or {})
+            v = nv.XgBatch(*[f[n] for n, _ in nv.XgBatch._fields_])
+        elif a == "run":
+            v = nv.XgRun(train=1, drop_p=0.0, seed=1, save=0, bn_momentum=0.1, bn_eps=1e-5)
+        elif a.startswith("ws"):
+            v = _FAKE + (_HUGE << 1 if a == "ws1" else 0)
+        elif a.startswith("bytes"):
+            v = _HUGE
+        elif a in _SCALARS:
+            v = _SCALARS[a]
+        else:
+            v = _FAKE
+        if isinstance(v, ctypes.Structure):
+            keep.append(v)
+            v = ctypes.byref(v)
+        args.append(v)
+    return getattr(L, name)(*args)
+
+
+def test_entry_points_gate_their_arguments_without_a_gpu(built):
+    """Every workspace-taking export answers in this order: bad dims or a NULL workspace -1, a workspace that is too small -4,
+    a misaligned workspace -1, and only then its own pointer and scalar tests -1.  Every call here carries one such defect."""
+    from controllable_xgating_amd import _native as nv
+    L = nv.lib()
+    assert set(_ENTRY) == set(_REQUIRED) and all(hasattr(L, n) for n in _ENTRY)
+    B = CFG["tiny"]["B"]
+    for name, spec in _ENTRY.items():
+        names = spec.split()
+
+        def call(**kw):
+            return _gate_call(nv, L, name, **kw)
+        req_args, req_x = (s.split() for s in _REQUIRED[name])
+        nulls = [{a: None} for a in req_args] + [{"batch": {f: None}} for f in req_x]
+        for dn in (a for a in names if a in ("d", "d1", "d2")):
+            for k in _DIMS:
+                assert call(dims={dn: {k: 0}}) == -1, (name, dn, k)
+            assert call(dims={dn: {"V": 1}}) == -1, (name, dn, "V = 1")
+            assert call(**{dn: None}) == -1, (name, dn, "NULL")
+        for wn in (a for a in names if a.startswith("ws")):
+            bn_ = "bytes" + wn[2:]
+            assert call(**{wn: None}) == -1, (name, wn, "NULL")
+            assert call(**{bn_: 8}) == -4, (name, bn_)
+            assert call(**{bn_: 8, wn: _FAKE + 4}) == -4, (name, bn_, "too small and misaligned")
+            for kw in nulls:
+                assert call(**{bn_: 8}, **kw) == -4, (name, bn_, kw)
+            assert call(**{wn: _FAKE + 4}) == -1, (name, wn, "misaligned")
+        for kw in nulls:
+            assert call(**kw) == -1, (name, kw)
+    # ---- the entry points' own scalar tests
+    call = lambda name, **kw: _gate_call(nv, L, name, **kw)      # noqa: E731
+    assert call("xg_step_fwd", state=_FAKE + 4) == -1                                  # the in-place state needs 16-byte rows
+    SAMPLE, REPLAY = nv.XG_ROLLOUT_SAMPLE, nv.XG_ROLLOUT_REPLAY
+    assert call("xg_rollout", mode=SAMPLE, uniforms=None) == -1
+    assert call("xg_rollout", mode=REPLAY, forced=None) == -1
+    for temp in (0.0, -1.0, float("nan")):
+        assert call("xg_rollout", mode=SAMPLE, temperature=temp) == -1, temp
+        for name in ("xg_rollout_pair", "xg_rollout_pair_compact", "xg_rollout_pair_videos"):
+            assert call(name, temperature=temp) == -1, (name, temp)
+    for name, dn in (("xg_rollout", "d"), ("xg_rollout_pair", "d2"), ("xg_rollout_pair_compact", "d2"),
+                     ("xg_rollout_pair_videos", "d2"), ("xg_rollout_bwd", "d")):
+        assert call(name, dims={dn: {"T": 1}, "d1": {"T": 1}}) == -1, (name, "T < 2")
+    for name in ("xg_rollout_pair", "xg_rollout_pair_compact"):
+        for n in (0, -1, 2 * B, 2 * B + 1):                                            # (d2.B = 2 B here)
+            assert call(name, n_sample=n) == -1, (name, n)
+    assert call("xg_rollout_pair_compact", n_sample=B - 1) == -1                       # n_sample != d1->B
+    assert call("xg_rollout_pair_videos", dims={"d2": {"B": 2 * B + 1}}) == -1         # d2->B != 2 * d1->B
+    assert call("xg_rollout_pair_videos", ws1=_FAKE) == -1                             # ws1 == ws2
+    assert call("xg_rollout_pair_videos", dims={"d1": {"R": 32}}) == -1                # d1 differs from d2 in R
+    # xg_rollout_compact has no pointer of its own: what it refuses behind its two workspaces are dims that do not fit
+    assert call("xg_rollout_compact", dims={"d1": {"R": 32}}) == -1
+    assert call("xg_rollout_compact", dims={"d1": {"B": 2 * B + 1}}) == -1             # more rows than the rollout had
