@@ -181,6 +181,17 @@ def test_tempered_sampling_vs_oracle(path, temperature):
     # scale, cosine 0.997)
     kw = dict(lp_tol=1e-2, loss_tol=1e-2, grad_kw=dict(rtol=5e-2, rtol_elem=5e-2, cos_min=0.997)) if bf16 else {}
     check_sampled_rollout(model, d, Pn, xn, u, reward, seq, slp, loss, 0, 0.0, temperature, **kw)
+    if bf16:
+        # ... and against the oracle that rounds where the kernels of this mode round (tests/bf16_oracle.py).  At `mid` only the
+        # per-step products do (forward and data gradient; nothing reaches the 256 / 64 / 256 rule of the large products), the
+        # float32 and the float64 emulation draw the same tokens at both temperatures and differ by 1e-5 in the log-probs and 1e-7
+        # in the loss: the bounds are the fp32 path's own -- draws up to CDF-boundary ones against the EMULATED log-probs,
+        # log-probs 3e-4, loss 1e-4, every gradient 2e-3 / 2e-6 and cosine 1 - 1e-5.
+        from tests import bf16_oracle as bo
+        tab = bo.policy_table(d, "rollout")
+        sites = bo.rounding_sites(d, "rollout")
+        assert len(sites) == 21 and all(tab[k][4] == "step" and k[1] in ("fwd", "dx") for k in sites), sites
+        check_sampled_rollout(model, d, Pn, xn, u, reward, seq, slp, loss, 0, 0.0, temperature, policy=bo.hip_bf16_policy(d, "rollout"))
 
 
 @pytest.mark.parametrize("temperature", [0.7, 1.3])

@@ -164,11 +164,12 @@ def flip_exemptions(trace64, trace32, shapes, c=FLIP_C, share_max=FLIP_SHARE_MAX
 ZERO_GRAD_PARAMS = ("two_spatial_encoder.visual_emb_rgb.0.bias", "two_spatial_encoder.visual_emb_opfl.0.bias", "lstmcore.a2w.bias")
 
 
-def grad_misses(grads, ref, rtol=2e-3, atol=2e-6, skip=(), cos_min=1 - 1e-5, rtol_elem=None, report=None, exempt=None):
+def grad_misses(grads, ref, rtol=2e-3, atol=2e-6, skip=(), cos_min=1 - 1e-5, rtol_elem=None, report=None, exempt=None, elem_share=0.1):
     """Three bounds per parameter (round 5: the max-norm bound alone lets a defect confined to a gradient's small entries through):
     (1) max |g - r| <= atol + rtol * max |r|; (2) direction: cosine(g, r) >= cos_min; (3) element-wise: |g_i - r_i| <=
     atol + rtol |r_i| + (rtol / 10) max |r| -- the share of the bound that does not scale with the element itself is a tenth
-    of (1)'s.  `grads` / `ref`: {name: ndarray}.  `exempt`: optional {name: bool mask} (flip_exemptions) -- the masked elements are
+    of (1)'s (`elem_share`; 1.0 leaves (3) to (1): for errors that do not scale with the element they land on -- tests/bf16_oracle.py).
+    `grads` / `ref`: {name: ndarray}.  `exempt`: optional {name: bool mask} (flip_exemptions) -- the masked elements are
     left out of all three bounds, every other element keeps them; max |r| is still taken over the whole parameter.
     Parameters whose true gradient is exactly zero (ZERO_GRAD_PARAMS) only make sense under (1) with their own scale and are
     passed in `skip` by the callers.  `report`: optional dict filled with (max error / scale, cosine, worst element-wise
@@ -193,7 +194,7 @@ def grad_misses(grads, ref, rtol=2e-3, atol=2e-6, skip=(), cos_min=1 - 1e-5, rto
         # (a gradient whose norm is itself at round-off level has no direction to speak of)
         if nr > 50 * atol * np.sqrt(rd.size) and not cos >= cos_min:
             bad.append((name, "cosine", cos, float(scale)))
-        ratio = np.abs(g - r) / (atol + rt_e * np.abs(r) + 0.1 * rtol * scale)
+        ratio = np.abs(g - r) / (atol + rt_e * np.abs(r) + elem_share * rtol * scale)
         if g.size and not ratio.max() <= 1:
             i = int(np.argmax(ratio))
             bad.append((name, "element", float(np.abs(g - r).ravel()[i]), float(np.abs(r).ravel()[i]), float(scale)))
@@ -261,8 +262,24 @@ def assert_greedy_tokens_match(g_h, g_o, logps_o, margin=1e-3):
         assert top2[1] - top2[0] < margin, (b, k, int(g_h[b, k]), int(g_o[b, k]), top2[1] - top2[0])
 
 
-def oracle_rollouts(d, Pn, xn, u, seed, p, temperature=1.0, train=True):
-    """The oracle's own sampled (from `u`) and greedy rollouts under dropout seed `seed`: ((seq, logps), (seq, logps))."""
+def oracle_rollouts(d, Pn, xn, u, seed, p, temperature=1.0, train=True, policy=None, dtype=torch.float32):
+    """The oracle's own sampled (from `u`) and greedy rollouts under dropout seed `seed`: ((seq, logps), (seq, logps)).
+    `policy`: the oracle's bf16 rounding policy (tests/bf16_oracle.py); `dtype`: the arithmetic of the oracle."""
+    if policy is not None or dtype != torch.float32:
+        old = torch.get_default_dtype()
+        torch.set_default_dtype(dtype)
+        try:
+            P = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dtype) for k, v in Pn.items()}
+            xi = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in xo.to_torch_inputs(xn).items()}
+            args = (P, xi["feats_rgb"], xi["feats_opfl"], xi["feat_mask"], xi["pos_feats"], d.L)
+            with torch.no_grad():
+                s, _, lps = xo.sample(*args, mode="sample", uniforms=u, temperature=temperature, train=train, p=p, seed=seed,
+                                      running=xo.new_running(d), return_logp=True, policy=policy)
+                g, _, lpg = xo.sample(*args, mode="greedy", train=train, p=p, seed=seed, running=xo.new_running(d), return_logp=True,
+                                      policy=policy)
+        finally:
+            torch.set_default_dtype(old)
+        return (s.numpy(), lps), (g.numpy(), lpg)
     P = xo.to_torch_params(Pn)
     xi = xo.to_torch_inputs(xn)
     args = (P, xi["feats_rgb"], xi["feats_opfl"], xi["feat_mask"], xi["pos_feats"], d.L)
@@ -274,14 +291,15 @@ def oracle_rollouts(d, Pn, xn, u, seed, p, temperature=1.0, train=True):
 
 
 def check_sampled_rollout(model, d, Pn, xn, u, reward, seq, slp, loss, seed, p, temperature=1.0, lp_tol=3e-4, loss_tol=1e-4,
-                          grad_kw=None, bn_updates=1, counts=None, report=None):
+                          grad_kw=None, bn_updates=1, counts=None, report=None, policy=None):
     """A kernel's sampled rollout (`seq`, `slp`: trimmed; `loss`: its RewardCriterion with `reward`, already backpropagated into
     `model`) vs
     the oracle under dropout seed `seed`: tokens up to CDF-boundary draws (assert_sampled_tokens_match); then the oracle replays
     the kernel's tokens in float64 (oracle_f64_with_flips) -- seqLogprobs (the UNTEMPERED log-probs: SAModel.py:189-195) within
     `lp_tol`, the loss within `loss_tol`, every gradient with grad_misses, and the BatchNorm running statistics after
-    `bn_updates` train-mode updates."""
-    (s_o, lps), _ = oracle_rollouts(d, Pn, xn, u, seed, p, temperature)
+    `bn_updates` train-mode updates.  `policy`: the oracle's bf16 rounding policy -- the draw (in float64) and the replay then
+    round where the kernels of precision="bf16" round (tests/bf16_oracle.py)."""
+    (s_o, lps), _ = oracle_rollouts(d, Pn, xn, u, seed, p, temperature, policy=policy, dtype=torch.float32 if policy is None else torch.float64)
     seq, slp = seq.cpu().numpy(), slp.detach().cpu().numpy()
     assert_sampled_tokens_match(seq, s_o, lps, u, temperature)
     n = seq.shape[1]
@@ -290,10 +308,10 @@ def check_sampled_rollout(model, d, Pn, xn, u, reward, seq, slp, loss, seed, p, 
     def fn(P, xi, tr):
         running = xo.new_running(d)
         so, lp = xo.sample(P, xi["feats_rgb"], xi["feats_opfl"], xi["feat_mask"], xi["pos_feats"], d.L, mode="replay",
-                           forced=forced, train=True, p=p, seed=seed, running=running, relu_trace=tr)
+                           forced=forced, train=True, p=p, seed=seed, running=running, relu_trace=tr, policy=policy)
         for _ in range(bn_updates - 1):
             xo.encoder_fwd(P, xi["feats_rgb"], xi["feats_opfl"], xi["feat_mask"], True, p, seed, running)
-        return xo.reward_criterion(lp, so, torch.from_numpy(reward[:, :n])), (lp.detach().numpy(), running)
+        return xo.reward_criterion(lp, so, torch.from_numpy(reward[:, :n]).to(lp.dtype)), (lp.detach().numpy(), running)
 
     loss_o, (lp_o, running), g64, ex = oracle_f64_with_flips(Pn, xn, fn, counts)
     m = np.concatenate([np.ones((d.B, 1), bool), seq[:, :-1] > 0], 1)
