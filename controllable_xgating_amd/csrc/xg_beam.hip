@@ -1,0 +1,342 @@
+// Kernels of the captioner's beam search (include/xgate_beam.h; the host loop is xgcb_beam_search in xg_model.hip).
+//
+// Per step, after the decoder step (core_step) and the vocabulary product over the M = B W rows:
+//   cap_beam_topw_kernel   one workgroup per row: log-sum-exp of the row's V logits and its W best (lp, word) pairs.  The (M,V)
+//                          log-softmax is never written.  The row is read from memory ONCE and staged in LDS (80 KB at V = 20000);
+//                          a row beyond 150 KiB is read three times instead.  Ranking is on lp = logit - lse itself, so two
+//                          logits that round to one lp are ordered by word index like the host search's torch.topk over lp.
+//   cap_beam_merge_kernel  one workgroup per video: wave 0 ranks the rows * W candidates by counting (stable), thread 0 writes the
+//                          step's (token, parent, r), the sums, the next tokens and the video's best-W done list, and every thread
+//                          gathers h1, c1, h2, c2 of slot v from its parent out of the step's OUTPUT buffer into its INPUT buffer.
+// After the loop cap_beam_backtrace_kernel follows each done entry's parents back.  cap_beam_repeat_kernel row-repeats what was
+// computed once per video (xgk_compact copies contiguous blocks: rows b W + slot of video b are not one).
+// Plain stores, no atomics, one fixed order for every sum.
+#include "xg_common.h"
+#include "xg_kernels.h"
+#include "../../include/xgate_beam.h"
+
+namespace {
+
+constexpr int CB_TPB = 256;
+// the top-W kernel's workgroup: a row of V = 20000 is 20 elements a thread (38 -> 31 us over 320 rows against 256 threads;
+// docs/CAPTION_BEAM.md has what else was measured)
+constexpr int TW_TPB = 1024, TW_WAVES = TW_TPB / 64;
+constexpr int CB_MAX = XGCB_MAX_BEAM;
+constexpr int CB_EMPTY = 0x7fffffff;                      // word index of a list entry that holds nothing
+constexpr int CB_STAGE_BYTES = 150 * 1024;                // the most dynamic LDS a row may take (as xgk_rollout_step)
+static_assert(CB_MAX * CB_MAX <= 64, "one wave ranks a video's candidates");
+static_assert(TW_WAVES * CB_MAX <= TW_TPB, "one thread per entry of the last ranking");
+
+// the order of the search: larger value first, lower word index first on exact ties.  Total on non-NaN values; a NaN is
+// better than nothing and nothing is better than it, so it is never kept.
+__device__ __forceinline__ bool cb_better(float v, int i, float ov, int oi) { return v > ov || (v == ov && i < oi); }
+
+template <int W, bool STAGE>
+__global__ void __launch_bounds__(TW_TPB) cap_beam_topw_kernel(const float* __restrict__ logits, int64_t ld, int V, int suppress,
+                                                               float* __restrict__ topv, int32_t* __restrict__ topi) {
+    extern __shared__ float4 cb_lds4[];
+    __shared__ float red[TW_WAVES], cv[TW_WAVES * W];
+    __shared__ int ci[TW_WAVES * W];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* g = logits + (size_t)blockIdx.x * ld;
+    // rows of a V that is no multiple of 4 start off the 16-byte grid: `head` scalars, `nvec` float4, the rest scalars
+    const int mis = (int)((reinterpret_cast<uintptr_t>(g) >> 2) & 3);
+    const int head = min(V, (4 - mis) & 3);
+    const int nvec = (V - head) >> 2;
+    const int tail0 = head + 4 * nvec;
+    const float4* g4 = reinterpret_cast<const float4*>(g + head);
+    float* row = reinterpret_cast<float*>(cb_lds4) + mis;         // (row + head is on the 16-byte grid like g + head)
+    auto each_global = [&](auto&& f) {
+        if (tid < head) f(g[tid], tid);
+        for (int j = tid; j < nvec; j += TW_TPB) {
+            const float4 x = g4[j];
+            const int i = head + 4 * j;
+            f(x.x, i); f(x.y, i + 1); f(x.z, i + 2); f(x.w, i + 3);
+        }
+        if (tail0 + tid < V) f(g[tail0 + tid], tail0 + tid);
+    };
+    auto each = [&](auto&& f) {
+        if constexpr (STAGE) { for (int i = tid; i < V; i += TW_TPB) f(row[i], i); }
+        else each_global(f);
+    };
+    // ---- the row's maximum (and, staged, its one trip from memory)
+    float mx = -INFINITY;
+    if constexpr (STAGE) {
+        if (tid < head) { const float x = g[tid]; row[tid] = x; mx = fmaxf(mx, x); }
+        for (int j = tid; j < nvec; j += TW_TPB) {
+            const float4 x = g4[j];
+            *reinterpret_cast<float4*>(row + head + 4 * j) = x;
+            mx = fmaxf(fmaxf(mx, fmaxf(x.x, x.y)), fmaxf(x.z, x.w));
+        }
+        if (tail0 + tid < V) { const float x = g[tail0 + tid]; row[tail0 + tid] = x; mx = fmaxf(mx, x); }
+    } else {
+        each_global([&](float x, int) { mx = fmaxf(mx, x); });
+    }
+    mx = wave_max(mx);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = red[0];
+#pragma unroll
+    for (int k = 1; k < TW_WAVES; ++k) mx = fmaxf(mx, red[k]);
+    __syncthreads();
+    // ---- log-sum-exp: thread, wave (DPP), then the waves in one fixed order
+    float s = 0.f;
+    each([&](float x, int) { s += __expf(x - mx); });
+    s = wave_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int k = 0; k < TW_WAVES; ++k) tot += red[k];
+    const float lse = mx + logf(tot);
+    // ---- each thread's W best in registers (a descending list; unrolled insertion, no indexing by a variable)
+    float bv[W];
+    int bi[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) { bv[k] = -INFINITY; bi[k] = CB_EMPTY; }
+    each([&](float x, int i) {
+        float v = x - lse;
+        if (i == suppress) v -= 1000.0f;
+        int ix = i;
+        if (cb_better(v, ix, bv[W - 1], bi[W - 1])) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                if (cb_better(v, ix, bv[k], bi[k])) {           // from here on v is what the list pushes down
+                    const float tv = bv[k]; const int ti = bi[k];
+                    bv[k] = v; bi[k] = ix; v = tv; ix = ti;
+                }
+            }
+        }
+    });
+    // ---- the wave's W best: W rounds of (best head of any lane, that lane pops)
+#pragma unroll
+    for (int r = 0; r < W; ++r) {
+        float v = bv[0];
+        int ix = bi[0];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(v, off);
+            const int oi = __shfl_xor(ix, off);
+            if (cb_better(ov, oi, v, ix)) { v = ov; ix = oi; }
+        }
+        if (lane == 0) { cv[wave * W + r] = v; ci[wave * W + r] = ix; }
+        if (bi[0] == ix) {
+#pragma unroll
+            for (int k = 0; k + 1 < W; ++k) { bv[k] = bv[k + 1]; bi[k] = bi[k + 1]; }
+            bv[W - 1] = -INFINITY; bi[W - 1] = CB_EMPTY;
+        }
+    }
+    __syncthreads();
+    // ---- the last waves * W entries by counting; the position breaks ties among empty entries, so every rank is taken once and
+    // every output is written (an empty entry, which only a row with NaNs leaves, becomes word 0 at -inf)
+    if (tid < TW_WAVES * W) {
+        const float v = cv[tid];
+        const int ix = ci[tid];
+        int rank = 0;
+        for (int j = 0; j < TW_WAVES * W; ++j) {
+            const float ov = cv[j];
+            const int oi = ci[j];
+            rank += (cb_better(ov, oi, v, ix) || (ov == v && oi == ix && j < tid)) ? 1 : 0;
+        }
+        if (rank < W) {
+            topv[(size_t)blockIdx.x * W + rank] = v;
+            topi[(size_t)blockIdx.x * W + rank] = (ix >= 0 && ix < V) ? ix : 0;
+        }
+    }
+}
+
+template <int W>
+int launch_topw(hipStream_t st, const float* logits, int64_t ld, int M, int V, int suppress, float* topv, int32_t* topi) {
+    const size_t lds = ((size_t)V + 8) * sizeof(float);
+    if (lds <= (size_t)CB_STAGE_BYTES) {
+        if (lds > 64 * 1024) {                                 // > 64 KiB of dynamic LDS is opted into once per kernel and device
+            static std::atomic<unsigned> optin{0};
+            XG_TRY(xg_lds_optin(optin, reinterpret_cast<const void*>(&cap_beam_topw_kernel<W, true>), CB_STAGE_BYTES));
+        }
+        hipLaunchKernelGGL((cap_beam_topw_kernel<W, true>), dim3(M), dim3(TW_TPB), lds, st, logits, ld, V, suppress, topv, topi);
+    } else {
+        hipLaunchKernelGGL((cap_beam_topw_kernel<W, false>), dim3(M), dim3(TW_TPB), 0, st, logits, ld, V, suppress, topv, topi);
+    }
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+
+__global__ void __launch_bounds__(CB_TPB) cap_beam_merge_kernel(CapBeamMergeArgs a) {
+    __shared__ float c_lp[CB_MAX * CB_MAX], c_p[CB_MAX * CB_MAX], s_lp[CB_MAX], s_p[CB_MAX];
+    __shared__ int c_tok[CB_MAX * CB_MAX], s_q[CB_MAX], s_tok[CB_MAX];
+    const int tid = threadIdx.x;
+    const int R = a.R, W = a.W, t = a.t, L = a.L;
+    const size_t b = blockIdx.x, row0 = b * W;
+    const int rows = t == 0 ? 1 : W;          // (every slot holds the video's initial state at t = 0)
+    // (a NaN ranks nowhere: whatever stays unwritten below is slot 0 / word 0, never an index out of range)
+    if (tid < CB_MAX * CB_MAX) {
+        const int q = tid / CB_MAX, k = tid - q * CB_MAX;
+        float lp = 0.f;
+        int tk = 0;
+        if (q < rows && k < W) {
+            lp = a.topv[(row0 + q) * W + k];
+            tk = a.topi[(row0 + q) * W + k];
+            tk = tk < 0 ? 0 : (tk >= a.V ? a.V - 1 : tk);
+        }
+        c_lp[tid] = lp; c_tok[tid] = tk; c_p[tid] = 0.f;
+    }
+    if (tid < CB_MAX) { s_lp[tid] = 0.f; s_p[tid] = 0.f; s_q[tid] = 0; s_tok[tid] = 0; }
+    __syncthreads();
+    const int ncand = W * rows;               // candidate i = c_rank * rows + q
+    int cq = 0, cr = 0;
+    float p = 0.f;
+    if (tid < ncand) {
+        cr = tid / rows;
+        cq = tid - cr * rows;
+        p = (t == 0 ? 0.f : a.sum[row0 + cq]) + c_lp[cq * CB_MAX + cr];
+        c_p[tid] = p;
+    }
+    __syncthreads();
+    if (tid < ncand) {                        // stable descending rank; the first W are the new slots
+        int rank = 0;
+        for (int i = 0; i < ncand; ++i) {
+            const float o = c_p[i];
+            rank += (o > p || (o == p && i < tid)) ? 1 : 0;
+        }
+        if (rank < W) {
+            s_q[rank] = cq;
+            s_tok[rank] = c_tok[cq * CB_MAX + cr];
+            s_lp[rank] = c_lp[cq * CB_MAX + cr];
+            s_p[rank] = p;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float* ds = a.done_score + row0;
+        int32_t* da = a.done_at + row0 * 2;
+        int n = t == 0 ? 0 : a.done_n[b];
+        n = n < 0 ? 0 : (n > W ? W : n);
+        for (int v = 0; v < W; ++v) {
+            const size_t e = (b * L + t) * W + v;
+            a.trace[2 * e] = s_tok[v];
+            a.trace[2 * e + 1] = s_q[v];
+            if (a.trace_out) { a.trace_out[2 * e] = s_tok[v]; a.trace_out[2 * e + 1] = s_q[v]; }
+            a.r[e] = s_lp[v];
+            a.tok[row0 + v] = s_tok[v];
+            float sm = s_p[v];
+            if (s_tok[v] == 0 || t == L - 1) {
+                int pos = n;
+                while (pos > 0 && ds[pos - 1] < sm) --pos;         // after entries of equal score
+                if (pos < W) {
+                    const int last = n < W ? n : W - 1;
+                    for (int i = last; i > pos; --i) { ds[i] = ds[i - 1]; da[2 * i] = da[2 * i - 2]; da[2 * i + 1] = da[2 * i - 1]; }
+                    ds[pos] = sm; da[2 * pos] = t; da[2 * pos + 1] = v;
+                    if (n < W) ++n;
+                }
+                sm = -1000.0f;
+            }
+            a.sum[row0 + v] = sm;
+        }
+        a.done_n[b] = n;
+    }
+    // slot v takes h1, c1, h2, c2 of its parent: out of the buffer the step wrote, into the buffer the next step reads
+    if (a.vec) {
+        const int R4 = R >> 2;
+        for (int i = tid; i < 4 * W * R4; i += CB_TPB) {
+            const int k = i / (W * R4), rem = i - k * (W * R4);
+            const int v = rem / R4, j = rem - v * R4;
+            reinterpret_cast<float4*>(a.dst[k] + (row0 + v) * R)[j] = reinterpret_cast<const float4*>(a.src[k] + (row0 + s_q[v]) * R)[j];
+        }
+    } else {
+        for (int i = tid; i < 4 * W * R; i += CB_TPB) {
+            const int k = i / (W * R), rem = i - k * (W * R);
+            const int v = rem / R, j = rem - v * R;
+            a.dst[k][(row0 + v) * R + j] = a.src[k][(row0 + s_q[v]) * R + j];
+        }
+    }
+}
+
+// one thread per (video, rank): the done entry's beam, read back along its parents
+__global__ void __launch_bounds__(CB_TPB) cap_beam_backtrace_kernel(const int32_t* __restrict__ trace, const float* __restrict__ r,
+                                                                    const float* __restrict__ done_score,
+                                                                    const int32_t* __restrict__ done_at, int64_t* seq,
+                                                                    float* seq_logp, float* score, int M, int W, int L) {
+    const int i = blockIdx.x * CB_TPB + threadIdx.x;
+    if (i >= M) return;
+    const size_t b = i / W;
+    int tf = done_at[2 * (size_t)i], s = done_at[2 * (size_t)i + 1];
+    tf = tf < 0 ? 0 : (tf >= L ? L - 1 : tf);
+    int64_t* sq = seq + (size_t)i * L;
+    float* lp = seq_logp + (size_t)i * L;
+    score[i] = done_score[i];
+    for (int t = L - 1; t > tf; --t) { sq[t] = 0; lp[t] = 0.f; }
+    for (int t = tf; t >= 0; --t) {
+        s = s < 0 ? 0 : (s >= W ? W - 1 : s);
+        const size_t e = (b * L + t) * W + s;
+        sq[t] = trace[2 * e];
+        lp[t] = r[e];
+        s = trace[2 * e + 1];
+    }
+}
+
+// dst row b W + slot = src row b, for every entry in one launch (blockIdx.y: the entry)
+__global__ void __launch_bounds__(CB_TPB) cap_beam_repeat_kernel(CapBeamRepeatArgs a, int B, int W) {
+    const CapBeamRepeatEntry e = a.e[blockIdx.y];
+    const int64_t n = e.n, total = (int64_t)B * W * n;
+    const bool vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(e.dst) | reinterpret_cast<uintptr_t>(e.src)) % 16 == 0);
+    const int64_t step = (int64_t)gridDim.x * CB_TPB;
+    if (vec) {
+        for (int64_t i = ((int64_t)blockIdx.x * CB_TPB + threadIdx.x) * 4; i < total; i += step * 4) {
+            const int64_t m = i / n, j = i - m * n;
+            *reinterpret_cast<float4*>(e.dst + i) = *reinterpret_cast<const float4*>(e.src + (m / W) * n + j);
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * CB_TPB + threadIdx.x; i < total; i += step) {
+            const int64_t m = i / n, j = i - m * n;
+            e.dst[i] = e.src[(m / W) * n + j];
+        }
+    }
+}
+
+}  // namespace
+
+int xgk_cap_beam_repeat(hipStream_t st, const CapBeamRepeatArgs& a, int B, int W) {
+    if (a.n <= 0 || a.n > XG_CAP_BEAM_REPEAT_MAX || B <= 0 || W <= 0) return XG_EINVAL;
+    int64_t most = 0;
+    for (int i = 0; i < a.n; ++i) {
+        if (!a.e[i].dst || !a.e[i].src || a.e[i].n <= 0) return XG_EINVAL;
+        most = a.e[i].n > most ? a.e[i].n : most;
+    }
+    const int64_t blocks = xg_cdiv64((int64_t)B * W * most, (int64_t)CB_TPB * 4);
+    hipLaunchKernelGGL(cap_beam_repeat_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048), a.n), dim3(CB_TPB), 0, st, a, B, W);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+
+int xgk_cap_beam_topw(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, float* topv, int32_t* topi) {
+    if (M <= 0 || V <= 0 || W < 1 || W > CB_MAX || W > V || ld < V || suppress >= V) return XG_EINVAL;
+    if (suppress < 0) suppress = -1;
+    switch (W) {
+        case 1: return launch_topw<1>(st, logits, ld, M, V, suppress, topv, topi);
+        case 2: return launch_topw<2>(st, logits, ld, M, V, suppress, topv, topi);
+        case 3: return launch_topw<3>(st, logits, ld, M, V, suppress, topv, topi);
+        case 4: return launch_topw<4>(st, logits, ld, M, V, suppress, topv, topi);
+        case 5: return launch_topw<5>(st, logits, ld, M, V, suppress, topv, topi);
+        case 6: return launch_topw<6>(st, logits, ld, M, V, suppress, topv, topi);
+        case 7: return launch_topw<7>(st, logits, ld, M, V, suppress, topv, topi);
+        default: return launch_topw<8>(st, logits, ld, M, V, suppress, topv, topi);
+    }
+}
+
+int xgk_cap_beam_merge(hipStream_t st, int B, CapBeamMergeArgs a) {
+    if (B <= 0 || a.W < 1 || a.W > CB_MAX || a.R <= 0 || a.L <= 0 || a.t < 0 || a.t >= a.L) return XG_EINVAL;
+    uintptr_t bits = 0;
+    for (int k = 0; k < 4; ++k) bits |= reinterpret_cast<uintptr_t>(a.src[k]) | reinterpret_cast<uintptr_t>(a.dst[k]);
+    a.vec = (a.R % 4 == 0 && bits % 16 == 0) ? 1 : 0;
+    hipLaunchKernelGGL(cap_beam_merge_kernel, dim3(B), dim3(CB_TPB), 0, st, a);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+
+int xgk_cap_beam_backtrace(hipStream_t st, const int32_t* trace, const float* r, const float* done_score, const int32_t* done_at,
+                           int64_t* seq, float* seq_logp, float* score, int M, int W, int L) {
+    hipLaunchKernelGGL(cap_beam_backtrace_kernel, dim3(xg_cdiv(M, CB_TPB)), dim3(CB_TPB), 0, st, trace, r, done_score, done_at, seq,
+                       seq_logp, score, M, W, L);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}

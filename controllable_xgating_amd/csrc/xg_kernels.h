@@ -358,6 +358,32 @@ int xgk_rollout_book(hipStream_t st, int t, int B, int Tm1, int replay, const in
 int xgk_rollout_dlogits(hipStream_t st, const float* logp, const int64_t* tok, const float* dslp, int64_t dstride,
                         float* dlogits, int B, int V);
 
+// ---- xg_beam.hip: the captioner's beam search (include/xgate_beam.h)
+// dst row b W + slot = src row b (rows of n floats), every entry in one launch
+constexpr int XG_CAP_BEAM_REPEAT_MAX = 8;
+struct CapBeamRepeatEntry { float* dst; const float* src; int64_t n; };
+struct CapBeamRepeatArgs { int n; CapBeamRepeatEntry e[XG_CAP_BEAM_REPEAT_MAX]; };
+int xgk_cap_beam_repeat(hipStream_t st, const CapBeamRepeatArgs& a, int B, int W);
+// per row of (M,V) raw logits: the W largest log_softmax values (the one at `suppress` >= 0 less 1000) in descending order, lower
+// word first on exact ties, into topv / topi (M,W)
+int xgk_cap_beam_topw(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, float* topv, int32_t* topi);
+struct CapBeamMergeArgs {
+    const float* topv; const int32_t* topi;   // (M,W) of this step
+    float* sum;                   // (M) running sums (not read at t = 0)
+    int64_t* tok;                 // (M) the step's tokens, fed by the next step
+    int32_t* trace;               // (B,L,W,2) (token, parent) of every slot and step
+    float* r;                     // (B,L,W) the log-probability of that token
+    int32_t* trace_out;           // the caller's copy of trace, or null
+    float* done_score;            // (B,W) the best completions so far, descending
+    int32_t* done_at;             // (B,W,2) their (step, slot)
+    int32_t* done_n;              // (B) how many (not read at t = 0)
+    const float* src[4]; float* dst[4];       // h1, c1, h2, c2 (M,R): what the step wrote -> what the next step reads
+    int R, V, L, W, t, vec;       // (vec: set by the launcher)
+};
+int xgk_cap_beam_merge(hipStream_t st, int B, CapBeamMergeArgs a);
+int xgk_cap_beam_backtrace(hipStream_t st, const int32_t* trace, const float* r, const float* done_score, const int32_t* done_at,
+                           int64_t* seq, float* seq_logp, float* score, int M, int W, int L);
+
 // ---- xg_optim.hip
 int xgk_clip_adam(hipStream_t st, int64_t n, float* p, float* g, float* m, float* v, float lr, float b1, float b2,
                   float eps, float wd, int step, float clip, bool zero_grad = false);

@@ -12,6 +12,7 @@
 #include "xg_common.h"
 #include <cstring>
 #include "xg_kernels.h"
+#include "../../include/xgate_beam.h"
 
 #include <new>
 #include <cstdlib>
@@ -1839,6 +1840,117 @@ extern "C" int xg_rollout_pair_videos(void* stream, const XgDims* d2, const XgPa
                         n_steps, d1->B, compact ? b.LOGITS : nullptr, &used_alt, d1, &b));
     if (!compact) return XG_OK;
     return compact_impl((hipStream_t)stream, d2, w, d1, b, used_alt, true);
+}
+
+// ================================================================== the captioner's beam search (include/xgate_beam.h)
+// The W most likely captions of each of d->B videos, rows b W + slot.  The encoder, init_hidden and v2a(V) run ONCE on the B videos
+// (in the `enc` part of the workspace) and are row-repeated for the M = B W rows of the decoder loop.  A step is core_step from one
+// state buffer into the other, the vocabulary product, cap_beam_topw_kernel (log-sum-exp and the W best of every row; no (M,V)
+// log-softmax) and cap_beam_merge_kernel, which also permutes the state back into the first buffer: six launches, no host step.
+namespace {
+
+struct BeamWs {
+    Ws enc;                        // the B videos: encoder, initial state, v2a(V)   (a whole workspace at T = 1)
+    Ws step;                       // what core_step touches, over M rows (every other field stays null)
+    float *Venc, *vproj, *pos;     // row-repeated (M,K,R), (M,K,A), (M,R)
+    float* st[2][4];               // h1, c1, h2, c2 (M,R): [0] read by the step, [1] written by it
+    float *topv, *sum, *r, *done_score;
+    int32_t *topi, *trace, *done_at, *done_n;
+    int64_t* tok;
+    size_t bytes;
+};
+
+inline XgDims beam_dims(const XgDims& d, int B) { XgDims e = d; e.B = B; e.T = 1; return e; }
+
+BeamWs beam_carve(const XgDims& d, int W, void* base) {
+    BeamWs w{};
+    w.enc = carve(beam_dims(d, d.B), base);
+    w.enc.sh16 = nullptr; w.enc.bytes = w.enc.core_bytes;          // fp32 only: no bf16 mirror region
+    Carver c{static_cast<char*>(base), w.enc.core_bytes};
+    const size_t B = d.B, M = B * W, K = d.K, R = d.R, A = d.A, E = d.E, V = d.V, L = d.T - 1;
+    Ws& s = w.step;
+    s.S = c.take<float>(M * 4 * R); s.S2 = c.take<float>(M * 4 * R); s.state_tmp = c.take<float>(4 * M * R);
+    s.AFU = c.take<float>(M * R + ((M + 3) & ~(size_t)3)); s.ATS = s.AFU + M * R;
+    s.Xe = c.take<float>(M * E); s.GP = c.take<float>(M * R); s.POSG = c.take<float>(M * R);
+    s.P = c.take<float>(M * A); s.ALPHA = c.take<float>(M * K); s.AF = c.take<float>(M * R);
+    s.LOGITS = c.take<float>(M * V);
+    s.dsync = c.take<int32_t>(XGK_DSTEP_SYNC_BYTES / sizeof(int32_t));
+    w.Venc = c.take<float>(M * K * R); w.vproj = c.take<float>(M * K * A); w.pos = c.take<float>(M * R);
+    for (int i = 0; i < 2; ++i) for (int k = 0; k < 4; ++k) w.st[i][k] = c.take<float>(M * R);
+    w.topv = c.take<float>(M * W); w.topi = c.take<int32_t>(M * W);
+    w.sum = c.take<float>(M); w.tok = c.take<int64_t>(M);
+    w.trace = c.take<int32_t>(B * L * W * 2); w.r = c.take<float>(B * L * W);
+    w.done_score = c.take<float>(M); w.done_at = c.take<int32_t>(M * 2); w.done_n = c.take<int32_t>(B);
+    w.bytes = (c.off + 255) & ~(size_t)255;
+    return w;
+}
+
+bool beam_dims_ok(const XgDims* d, int W, int suppress) {
+    if (!dims_ok(d) || d->T < 2) return false;
+    if (W < 1 || W > XGCB_MAX_BEAM || W > d->V || suppress >= d->V) return false;
+    return (int64_t)d->B * W <= (1 << 20);                         // (row indices and launch grids stay far inside int)
+}
+
+}  // namespace
+
+extern "C" int xgcb_version(void) { return XGCB_VERSION; }
+
+extern "C" size_t xgcb_workspace_bytes(const XgDims* d, int32_t W) {
+    if (!beam_dims_ok(d, W, -1)) return 0;
+    return beam_carve(*d, W, nullptr).bytes;
+}
+
+extern "C" int xgcb_beam_search(void* stream, const XgDims* d, int32_t W, int32_t suppress_token, const XgParams* p,
+                                const XgBnState* bn, const XgBatch* x, const XgRun* run, int64_t* seq, float* seq_logp,
+                                float* score, int32_t* trace, void* ws, size_t ws_bytes) {
+    if (!beam_dims_ok(d, W, suppress_token) || !p || !x || !run || !seq || !seq_logp || !score || !ws) return XG_EINVAL;
+    if (!bn || !bn->rgb_mean || !bn->rgb_var || !bn->opfl_mean || !bn->opfl_var) return XG_EINVAL;
+    if (!x->feats_rgb || !x->feats_opfl || !x->feat_mask || !x->pos_feats) return XG_EINVAL;
+    if (run->train || run->save || run->gemm_mode != 0 || (uintptr_t)ws % 256 != 0) return XG_EINVAL;
+    BeamWs w = beam_carve(*d, W, ws);
+    if (ws_bytes < w.bytes) return XG_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = d->B, R = d->R, A = d->A, E = d->E, K = d->K, V = d->V, L = d->T - 1, M = B * W;
+    const XgDims de = beam_dims(*d, B), dm = beam_dims(*d, M);
+    attach_packed(w.enc, de, run);
+    attach_packed(w.step, dm, run);
+    // ---- once per call, on the B videos
+    Streams es(st, run);
+    XG_TRY(encoder_fwd(st, de, *p, bn, *x, *run, w.enc, &es));
+    XG_TRY(init_and_vproj(es, de, *p, x->feat_mask, w.enc));
+    {
+        CapBeamRepeatArgs ra{};
+        auto rep = [&](float* dst, const float* src, size_t n) { ra.e[ra.n++] = CapBeamRepeatEntry{dst, src, (int64_t)n}; };
+        rep(w.Venc, w.enc.Venc, (size_t)K * R); rep(w.vproj, w.enc.vproj, (size_t)K * A); rep(w.pos, x->pos_feats, R);
+        rep(w.st[0][0], w.enc.H1, R); rep(w.st[0][1], w.enc.C1, R); rep(w.st[0][2], w.enc.H2, R); rep(w.st[0][3], w.enc.C2, R);
+        XG_TRY(xgk_cap_beam_repeat(st, ra, B, W));
+    }
+    XG_TRY(zero_dsync(st, w.step));
+    if (hipMemsetAsync(w.tok, 0, sizeof(int64_t) * (size_t)M, st) != hipSuccess) return XG_EHIP;        // BOS
+    CapBeamMergeArgs ma{};
+    ma.topv = w.topv; ma.topi = w.topi; ma.sum = w.sum; ma.tok = w.tok; ma.trace = w.trace; ma.r = w.r; ma.trace_out = trace;
+    ma.done_score = w.done_score; ma.done_at = w.done_at; ma.done_n = w.done_n;
+    for (int k = 0; k < 4; ++k) { ma.src[k] = w.st[1][k]; ma.dst[k] = w.st[0][k]; }
+    ma.R = R; ma.V = V; ma.L = L; ma.W = W;
+    const bool pk = step_packed(w.step, dm);
+    for (int t = 0; t < L; ++t) {
+        StepIO s{};
+        if (pk) s.tok = w.tok;                    // token rows gathered by index inside the products
+        else {
+            XG_TRY(xgk_embed_gather(st, p->embed_w, E, w.tok, M, 1, 0, M, V, w.step.Xe, E));
+            s.xt = w.step.Xe;
+        }
+        s.pos = w.pos; s.gp = w.step.GP; s.posg = w.step.POSG; s.pre1 = nullptr; s.mask = nullptr; s.ldm = 1;
+        s.h1 = w.st[0][0]; s.c1 = w.st[0][1]; s.h2 = w.st[0][2]; s.c2 = w.st[0][3];
+        s.h1o = w.st[1][0]; s.c1o = w.st[1][1]; s.h2o = w.st[1][2]; s.c2o = w.st[1][3];
+        s.P = w.step.P; s.alpha = w.step.ALPHA; s.af = w.step.AF; s.g1 = nullptr; s.g2 = nullptr; s.t = t;
+        XG_TRY(core_step(st, dm, *p, *run, w.step, w.Venc, w.vproj, s));
+        XG_TRY(xgk_linear(st, 0, M, V, R, s.h2o, R, p->logit_w, p->logit_b, w.step.LOGITS, V));
+        XG_TRY(xgk_cap_beam_topw(st, w.step.LOGITS, V, M, V, W, suppress_token, w.topv, w.topi));
+        ma.t = t;
+        XG_TRY(xgk_cap_beam_merge(st, B, ma));
+    }
+    return xgk_cap_beam_backtrace(st, w.trace, w.r, w.done_score, w.done_at, seq, seq_logp, score, M, W, L);
 }
 
 extern "C" int xg_rollout_bwd(void* stream, const XgDims* d, const XgParams* p, const XgParams* g, const XgBatch* x,

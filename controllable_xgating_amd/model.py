@@ -563,6 +563,10 @@ class SAModel(nn.Module):
         beam_size = opt.get("beam_size", 1)
         temperature = opt.get("temperature", 1.0)
         if beam_size > 1:
+            if opt.get("beam_on_device", False):        # the whole search on the device; done_beams stays as it is
+                seq, slp, _ = self.beam_captions(feats_rgb, feats_opfl, feat_mask, pos_feats, beam_size=beam_size,
+                                                 suppress_token=opt.get("suppress_token", 1))
+                return seq[:, 0], slp[:, 0]
             from .beam import sample_beam
             feats = self.encode(feats_rgb, feats_opfl, feat_mask)
             return sample_beam(self, feats, feat_mask, pos_feats, opt)
@@ -584,6 +588,53 @@ class SAModel(nn.Module):
     def sample_beam(self, feats, feat_masks, pos_feats, opt={}):
         from .beam import sample_beam
         return sample_beam(self, feats, feat_masks, pos_feats, opt)
+
+    def beam_captions(self, feats_rgb, feats_opfl, feat_mask, pos_feats, beam_size=5, suppress_token=1, return_trace=False):
+        """The W = beam_size captions the model finds most likely for each of the B videos (include/xgate_beam.h: the search of
+        beam.py / the reference's sample_beam, SAModel.py:129-161, as ONE enqueue with no host work per step).  Returns (seq
+        (B,W,L) int64, seq_logp (B,W,L), score (B,W)[, trace (B,L,W,2) int32]); nothing here synchronises with the host.
+
+        A video's beams come best first, each ranked by its summed log-probability `score` at the moment it finished; seq and
+        seq_logp are zero after a beam's finish.  `suppress_token`: the word whose log-probability is lowered by 1000 before every
+        merge (the reference does this for UNK, index 1); -1 turns it off.  `return_trace`: also the (token, parent slot) of every
+        slot and step.  Eval mode, fp32 and device tensors only; beam_size may not exceed vocab_size or 8."""
+        from . import _native_beam as nb
+        if self.training:
+            raise NotImplementedError("beam_captions runs in eval mode only: call model.eval() first")
+        if self.precision != "fp32":
+            raise NotImplementedError("beam_captions is fp32 only (precision = %r)" % (self.precision,))
+        W, sup = int(beam_size), int(suppress_token)
+        if W < 1 or W > self.vocab_size or W > nb.XGCB_MAX_BEAM:
+            raise ValueError("1 <= beam_size <= min(vocab_size = %d, %d) expected, got %d" % (self.vocab_size, nb.XGCB_MAX_BEAM, W))
+        if sup >= self.vocab_size:
+            raise ValueError("suppress_token must lie below vocab_size = %d (-1: none), got %d" % (self.vocab_size, sup))
+        for t in (feats_rgb, feats_opfl, feat_mask, pos_feats):
+            if not t.is_cuda:
+                raise NotImplementedError("beam_captions needs device tensors: there is no CPU path")
+        B, K = feats_rgb.shape[0], feats_rgb.shape[1]
+        L = self.seq_length
+        dev = feats_rgb.device
+        lib = nb.lib()
+        d = self._dims(B, K, L + 1)
+        key = (B, K, L, W, str(dev))
+        ws = getattr(self, "_beam_ws", {}).get(key)
+        if ws is None:
+            n = lib.xgcb_workspace_bytes(C.byref(d), W)
+            if n == 0:
+                raise nv.XgError("xgcb_workspace_bytes: invalid dims or too many rows (B %d, W %d)" % (B, W))
+            ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+            self._beam_ws = {key: ws}                   # (one shape at a time: an evaluation runs one batch shape)
+        wp, wn = _ws_ptr(ws)
+        b, keep = self._batch(feats_rgb, feats_opfl, feat_mask, pos_feats)
+        ps, bn, run = self._params_struct(), self._bn_struct(), self._run(False)
+        seq = torch.empty(B, W, L, dtype=torch.int64, device=dev)
+        seq_logp = torch.empty(B, W, L, dtype=torch.float32, device=dev)
+        score = torch.empty(B, W, dtype=torch.float32, device=dev)
+        trace = torch.empty(B, L, W, 2, dtype=torch.int32, device=dev) if return_trace else None
+        nv.check(lib.xgcb_beam_search(_stream(), C.byref(d), W, sup, C.byref(ps), C.byref(bn), C.byref(b), C.byref(run),
+                                      nv.ptr(seq), nv.ptr(seq_logp), nv.ptr(score), nv.ptr(trace), wp, wn), "xgcb_beam_search")
+        out = (seq, seq_logp, score)
+        return out + (trace,) if return_trace else out
 
 
 # ====================================================================== autograd glue
