@@ -6,8 +6,9 @@ choice (include/xgate_pos_control.h), S templates for each of B videos; ``captio
 captioner without leaving the device.  ``PosModel.sample_templates`` (include/xgate_pos_sample.h) lets the generator draw the templates
 itself, ``caption_sampled`` captions under them and ``first_occurrences`` marks a video's distinct draws.
 ``PosModel.beam_templates`` (include/xgate_pos_beam.h) finds the W templates the generator thinks most likely and ``caption_beam``
-captions under them.  Eval mode, fp32, one GPU;
-sharing the captioner's encoder across a video's templates is not done (the video inputs are repeated per template).
+captions under them.  Eval mode, fp32, one GPU.  By default the captioner runs over the B*S rows with the video inputs repeated per
+template; ``share_encoder=True`` hands the videos over once (``SAModel.sample_per_video``, include/xgate_control.h): the captioner's
+encoder, init_hidden and v2a(V) then run once per video and a step's attention reads them once per group of a video's templates.
 """
 from __future__ import annotations
 
@@ -62,20 +63,33 @@ def pad_templates(templates, seq_length, category_size):
     return t.contiguous()
 
 
-def caption_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, opt={}):
+def _caption_rows(cap_model, feats_rgb, feats_opfl, feat_mask, pos_feats, B, S, opt, share_encoder):
+    """The captioner over the (B*S,R) `pos_feats` rows of B videos: (seq (B,S,n), seqLogprobs (B,S,n)).  share_encoder: the videos
+    once through ``sample_per_video``; otherwise ``sample`` on the inputs repeated per template."""
+    if share_encoder:
+        return cap_model.sample_per_video(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(B, S, -1), opt)
+    seq, slp = cap_model.sample(feats_rgb.repeat_interleave(S, 0), feats_opfl.repeat_interleave(S, 0),
+                                feat_mask.repeat_interleave(S, 0), pos_feats, opt)
+    return seq.reshape(B, S, -1), slp.reshape(B, S, -1)
+
+
+def caption_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, opt={}, share_encoder=False):
     """Caption each of the B videos under each of its S POS templates: (seq (B,S,n) int64, seqLogprobs (B,S,n), template_score
     (B,S)).  The forced POS rollout (``pos_model.sample_forced``) leaves `pos_feats` (B*S,R) on the device and the captioner's
     ``sample`` (``opt`` as there: greedy, sampled, or beam search with beam_size > 1) runs over the B*S rows, the video inputs
     repeated per template; nothing is read back between the two.  template_score is the log-probability the POS generator gives
     the template (end tag included).  Inference only: both models run under ``torch.no_grad()``, so nothing returned carries a
-    gradient (a sampled captioner rollout that is to be trained on goes through ``cap_model.sample`` directly)."""
+    gradient (a sampled captioner rollout that is to be trained on goes through ``cap_model.sample`` directly).
+    ``share_encoder=True``: the captioner takes the B videos once (``cap_model.sample_per_video``; greedy or sampled, no beam search:
+    beam_size > 1 raises NotImplementedError) instead of the repeated inputs; the two paths agree up to the last bits of fp32."""
+    if share_encoder and opt.get("beam_size", 1) > 1:
+        raise NotImplementedError("share_encoder=True has no beam search: beam_size must be 1")
     with torch.no_grad():
         tag_logp, _, _, pos_feats = pos_model.sample_forced(feats_rgb, feats_opfl, feat_mask, templates, collect_states=False,
                                                             trim=False)
         B, S = tag_logp.shape[:2]
-        seq, slp = cap_model.sample(feats_rgb.repeat_interleave(S, 0), feats_opfl.repeat_interleave(S, 0),
-                                    feat_mask.repeat_interleave(S, 0), pos_feats, opt)
-    return seq.reshape(B, S, -1), slp.reshape(B, S, -1), tag_logp.sum(2)
+        seq, slp = _caption_rows(cap_model, feats_rgb, feats_opfl, feat_mask, pos_feats, B, S, opt, share_encoder)
+    return seq, slp, tag_logp.sum(2)
 
 
 def first_occurrences(templates):
@@ -92,34 +106,40 @@ def first_occurrences(templates):
 
 
 def caption_sampled(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, S, temperature=1.0, uniforms=None, generator=None,
-                    opt={}):
+                    opt={}, share_encoder=False):
     """Caption each of the B videos under S POS templates the generator draws itself: (seq (B,S,n) int64, seqLogprobs (B,S,n),
     templates (B,S,L) int64, template_score (B,S), first (B,S) bool).  The sampled POS rollout (``pos_model.sample_templates``:
     `temperature`, `uniforms`, `generator` as there) leaves `pos_feats` (B*S,R) on the device and the captioner's ``sample``
     (``opt`` as there) runs over the B*S rows exactly as in ``caption_with_templates``; nothing is read back between the two.
     template_score is the untempered log-probability the POS generator gives the drawn template (end tag included); `first`
-    marks each video's distinct templates (``first_occurrences``).  Inference only: both models run under ``torch.no_grad()``."""
+    marks each video's distinct templates (``first_occurrences``).  Inference only: both models run under ``torch.no_grad()``.
+    `share_encoder` as in ``caption_with_templates``."""
+    if share_encoder and opt.get("beam_size", 1) > 1:
+        raise NotImplementedError("share_encoder=True has no beam search: beam_size must be 1")
     with torch.no_grad():
         templates, tag_logp, _, _, pos_feats = pos_model.sample_templates(feats_rgb, feats_opfl, feat_mask, S, temperature=temperature,
                                                                           uniforms=uniforms, generator=generator,
                                                                           collect_states=False, trim=False)
         B, S = tag_logp.shape[:2]
-        seq, slp = cap_model.sample(feats_rgb.repeat_interleave(S, 0), feats_opfl.repeat_interleave(S, 0),
-                                    feat_mask.repeat_interleave(S, 0), pos_feats, opt)
+        seq, slp = _caption_rows(cap_model, feats_rgb, feats_opfl, feat_mask, pos_feats, B, S, opt, share_encoder)
         first = first_occurrences(templates)
-    return seq.reshape(B, S, -1), slp.reshape(B, S, -1), templates, tag_logp.sum(2), first
+    return seq, slp, templates, tag_logp.sum(2), first
 
 
-def caption_beam(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, beam_size=5, suppress_tag=1, opt={}):
+def caption_beam(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, beam_size=5, suppress_tag=1, opt={}, share_encoder=False):
     """Caption each of the B videos under the W = beam_size POS templates the generator itself finds most likely: (seq (B,W,n)
     int64, seqLogprobs (B,W,n), templates (B,W,L) int64, score (B,W)), a video's templates best first.  The beam search
     (``pos_model.beam_templates``: `beam_size`, `suppress_tag` as there) runs without a host synchronisation and its templates go
     through ``caption_with_templates``.  `pos_feats` come from that forced replay: the search permutes its slots at every step and
     overwrites dead ones, so it ends with no held state per returned beam to hand over.  `score` is the beam's summed
     log-probability at its finish (with the -1000 of a suppressed tag, should the beam hold one), not the replay's template score.
-    Inference only: both models run under ``torch.no_grad()``."""
+    Inference only: both models run under ``torch.no_grad()``.  `share_encoder` as in ``caption_with_templates`` (it is the
+    CAPTIONER's beam search, opt["beam_size"] > 1, that it does not serve; `beam_size` here is the POS generator's)."""
+    if share_encoder and opt.get("beam_size", 1) > 1:
+        raise NotImplementedError("share_encoder=True has no beam search: beam_size must be 1")
     with torch.no_grad():
         templates, _, score, _ = pos_model.beam_templates(feats_rgb, feats_opfl, feat_mask, beam_size=beam_size,
                                                           suppress_tag=suppress_tag, trim=False)
-        seq, slp, _ = caption_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, opt)
+        seq, slp, _ = caption_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, opt,
+                                             share_encoder=share_encoder)
     return seq, slp, templates, score

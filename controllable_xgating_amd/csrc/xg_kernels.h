@@ -295,6 +295,10 @@ bool xgk_packed_view(const XgDims& d, const void* packed, int dtype, PackedView*
 // per-sample additive attention: e_k = w . tanh(p + q_k), alpha = softmax_k(e), af = sum_k alpha_k V_k
 int xgk_attn_fwd(hipStream_t st, const float* p, const float* vproj, const float* V, const float* w, float* alpha,
                  float* af, int B, int K, int R, int A, bool half_cu = false);   // half_cu: <= 64 VGPRs, fits beside a background GEMM workgroup
+// xg_control.hip: the same for S rows per video -- p (B*S,A), alpha (B*S,K) or null and af (B*S,R) per row b S + s, vproj (B,K,A)
+// and V (B,K,R) per video, read once per group of XGCC_TEMPLATE_GROUP rows of a video (include/xgate_control.h)
+int xgk_attn_fwd_group(hipStream_t st, const float* p, const float* vproj, const float* V, const float* w, float* alpha,
+                       float* af, int B, int S, int K, int R, int A);
 // de[b][k], dp[b][a] from daf[b][r]
 int xgk_attn_bwd(hipStream_t st, const float* daf, int lddaf, const float* p, const float* vproj, const float* V,
                  const float* w, const float* alpha, float* de, float* dp, int B, int K, int R, int A);

@@ -13,6 +13,7 @@
 #include <cstring>
 #include "xg_kernels.h"
 #include "../../include/xgate_beam.h"
+#include "../../include/xgate_control.h"
 
 #include <new>
 #include <cstdlib>
@@ -556,6 +557,7 @@ struct StepIO {
     float *P, *alpha, *af, *g1, *g2;  // saved per-step tensors (alpha / gates may be scratch)
     int t;
     bool half_attn;       // stand-alone attention in its half-CU form (a background product runs beside the steps)
+    int rows_per_video;   // 0: V / vproj hold one (K,.) block per row.  S > 0 (include/xgate_control.h): one per VIDEO, row / S; the attention is then the stand-alone group launch (xg_control.hip) in every tier
     const RollSelectArgs* sel;   // rollout steps t >= 1 (packed form, xt == null): the step's first launch CHOOSES the tokens (xg_select.h) and writes tok / mask / xt rows itself
 };
 
@@ -587,6 +589,14 @@ inline LstmFwdArgs cell_fwd_args(int layer, const StepIO& s, const XgRun& run, i
     return a;
 }
 
+// the stand-alone attention launch of a step: per row, or per group of a video's rows (StepIO.rows_per_video)
+inline int step_attn(hipStream_t st, const XgDims& d, const XgParams& p, const float* V, const float* vproj, const StepIO& s,
+                     bool half_cu = false) {
+    if (s.rows_per_video > 0)
+        return xgk_attn_fwd_group(st, s.P, vproj, V, p.a2w_w, s.alpha, s.af, d.B / s.rows_per_video, s.rows_per_video, d.K, d.R, d.A);
+    return xgk_attn_fwd(st, s.P, vproj, V, p.a2w_w, s.alpha, s.af, d.B, d.K, d.R, d.A, half_cu);
+}
+
 // attention + the two cells for one step (sub_modules.py:677-684).
 //
 // Packed form, 3 launches, every launch a multi-job skinny launch (xg_step.hip):
@@ -606,7 +616,7 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
     // below ~16 rows (30 vs 34 us at 8 rows).
 #ifdef XG_DIAG
     static const bool use_dstep = xg_diag_env("XG_DSTEP") != nullptr;
-    if (use_dstep && !s.sel && w.pk.dtype != 2 && step_packed(w, d) && xgk_dstep_ok(d) && ((uintptr_t)V % 16 == 0) && ((uintptr_t)vproj % 16 == 0) &&
+    if (use_dstep && !s.sel && s.rows_per_video == 0 && w.pk.dtype != 2 && step_packed(w, d) && xgk_dstep_ok(d) && ((uintptr_t)V % 16 == 0) && ((uintptr_t)vproj % 16 == 0) &&
         ((uintptr_t)p.a2w_w % 16 == 0)) {
         DStepArgs a2{};
         a2.B = B; a2.R = R; a2.A = A; a2.E = E; a2.K = d.K; a2.V1 = d.V - 1;
@@ -668,7 +678,7 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
         // throughput-bound across three streams, not bound by this chain); D is the simplest and the default.)
         // (at hidden 1024 / 40 frames E wins instead: 8.51 vs 8.63 ms -- the stand-alone attention is then 24 us per step)
         const char xe_form = R >= 1024 ? 'E' : 'D';
-        const bool fused_attn = (!s.pre1 || xe_form == 'E') && A <= 2048 && d.K <= 128 && ((uintptr_t)V % 8 == 0) &&
+        const bool fused_attn = s.rows_per_video == 0 && (!s.pre1 || xe_form == 'E') && A <= 2048 && d.K <= 128 && ((uintptr_t)V % 8 == 0) &&
                                 ((uintptr_t)vproj % 16 == 0) && ((uintptr_t)p.a2w_w % 16 == 0);
         // S2' = h2 W_h2h2 + b rides in launch 1 (teacher forcing form B; the rollout form beyond 64 rows, where the three
         // launches are then 512 / 512 / 256 workgroups, one round each, instead of 256 / 768 / 256: 49.4 -> 46.5 us per step
@@ -729,7 +739,7 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
         if (!s2_first && !s2_in_cell2) s2_job(k2.job[n2++]);
         k2.njobs = n2;
         if (n2 > 0) XG_TRY(xgk_skinny(st, k2, sk_mode(w)));
-        if (!fused_attn) XG_TRY(xgk_attn_fwd(st, s.P, vproj, V, p.a2w_w, s.alpha, s.af, B, d.K, R, A, s.half_attn));
+        if (!fused_attn) XG_TRY(step_attn(st, d, p, V, vproj, s, s.half_attn));
         // ---- launch 3: cell 2 = h1' W_i2h + af W_a2h + S2'                                                :684
         if (!s2_in_cell2) { c.add = w.S2; c.ldadd = 4 * R; }
         {
@@ -777,7 +787,7 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
             k1b.job[0].seg[2] = seg_nt(s.h1, R, p.l1_h2h_w, R, R); k1b.job[0].bias[2] = p.l1_h2h_b;
             XG_TRY(xgk_skinny(st, k1b, sk_mode(w)));
         }
-        XG_TRY(xgk_attn_fwd(st, s.P, vproj, V, p.a2w_w, s.alpha, s.af, B, d.K, R, A));
+        XG_TRY(step_attn(st, d, p, V, vproj, s));
         SkArgs k2{};
         k2.njobs = 1;
         k2.job[0] = job_lstm(c);
@@ -795,7 +805,7 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
     }
     XG_TRY(xgk_gemm(st, w.gm, false, true, B, A, R, s.h1, R, p.h2a_w, 2 * R, s.P, A, p.h2a_b, false, false));
     XG_TRY(xgk_gemm(st, w.gm, false, true, B, A, R, s.h2, R, p.h2a_w + R, 2 * R, s.P, A, nullptr, false, true));
-    XG_TRY(xgk_attn_fwd(st, s.P, vproj, V, p.a2w_w, s.alpha, s.af, B, d.K, R, A));
+    XG_TRY(step_attn(st, d, p, V, vproj, s));
     XG_TRY(xgk_linear(st, w.gm, B, 4 * R, R, s.h1, R, p.l1_h2h_w, p.l1_h2h_b, w.S, 4 * R));
     if (!s.pre1) {
         XG_TRY(xgk_linear(st, w.gm, B, 4 * R, E, s.xt, E, p.l1_i2h_w, p.l1_i2h_b, w.S, 4 * R, false, true));
@@ -1656,11 +1666,25 @@ extern "C" int xg_xe_loss_bwd(void* stream, const XgDims* d, const XgParams* p, 
 static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, const XgBnState* bn, const XgBatch* x,
                         const XgRun* run, int mode, const float* uniforms, const int64_t* forced, float temperature, Ws& w,
                         int64_t* seq, float* seq_logp, int32_t* n_steps, int split, float* logits_alt = nullptr,
-                        bool* used_alt = nullptr, const XgDims* d1 = nullptr, Ws* enc = nullptr) {
+                        bool* used_alt = nullptr, const XgDims* d1 = nullptr, Ws* enc = nullptr, int rows_per_video = 0) {
     const int B = d->B, R = d->R, E = d->E, A = d->A, T = d->T;
     Streams es(st, run);
     const float* pos_rows = x->pos_feats;
-    if (enc) {
+    // rows_per_video = S > 0 (xgcc_rollout): `x` holds the d1->B = B / S videos once and pos_feats per row.  The encoder, v2a(V) and
+    // the initial state are computed once in `enc`, only the initial state is repeated, and every step's attention reads enc's V and
+    // v2a(V) at row / S.  `w` is then the row part of cc_carve: every per-step tensor is ONE block that each step overwrites (slot()
+    // below), the state alternates between two blocks.
+    const bool rows = rows_per_video > 0;
+    const float *Vsrc = rows ? enc->Venc : w.Venc, *vproj_src = rows ? enc->vproj : w.vproj;
+    auto slot = [&](int t) { return rows ? 0 : t; };
+    if (rows) {
+        XG_TRY(encoder_fwd(st, *d1, *p, bn, *x, *run, *enc, &es));
+        XG_TRY(init_and_vproj(es, *d1, *p, x->feat_mask, *enc));
+        CapBeamRepeatArgs ra{};
+        auto rep = [&](float* dst, const float* src) { ra.e[ra.n++] = CapBeamRepeatEntry{dst, src, (int64_t)R}; };
+        rep(w.H1, enc->H1); rep(w.C1, enc->C1); rep(w.H2, enc->H2); rep(w.C2, enc->C2);
+        XG_TRY(xgk_cap_beam_repeat(st, ra, d1->B, rows_per_video));
+    } else if (enc) {
         const size_t B1 = d1->B, N1 = B1 * d->K;
         XG_TRY(encoder_fwd(st, *d1, *p, bn, *x, *run, *enc, &es));
         if (run->train && bn && bn->rgb_mean && bn->rgb_var && bn->opfl_mean && bn->opfl_var) {      // the second sample() call's update
@@ -1694,7 +1718,7 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
     const int wr_rows = mode == XG_ROLLOUT_SAMPLE ? split : ((mode == XG_ROLLOUT_REPLAY || run->save) ? B : 0);
     const bool alt = logits_alt != nullptr && fused_select && mode == XG_ROLLOUT_SAMPLE && split < B;
     if (used_alt) *used_alt = alt;
-    auto logits_of = [&](int t) { return alt ? logits_alt + (size_t)t * split * d->V : w.LOGITS + (size_t)t * B * d->V; };
+    auto logits_of = [&](int t) { return alt ? logits_alt + (size_t)t * split * d->V : w.LOGITS + (size_t)slot(t) * B * d->V; };
     // Steps t >= 1 on the packed fp32 path CHOOSE their tokens themselves: the choice is the prologue of the step's first launch
     // (its POS-gate tiles: xg_step.hip SEL, xg_select.h) instead of a launch of its own between the vocabulary product and the step
     // -- four dependent launches per step instead of five.  The last choice of a rollout (no step follows) keeps its launch.
@@ -1703,7 +1727,7 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
     for (int t = 0; t < T; ++t) {
         int64_t* tok = w.TOK + (size_t)t * B;
         float* unf = w.UNF + (size_t)t * B;
-        float* xt = w.Xe + (size_t)t * B * E;
+        float* xt = w.Xe + (size_t)slot(t) * B * E;
         const float* prev_logits = t >= 1 ? logits_of(t - 1) : nullptr;
         // token choice from the previous step's raw logits + bookkeeping + embedding gather: one launch (:183-215)
         const bool in_step = step_select && t >= 1 && t + 1 < T;
@@ -1715,24 +1739,30 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
         if (in_step) sel = xgk_roll_select_args(ra, w.VPART);
         else if (t >= 1 && fused_select) XG_TRY(xgk_roll_select(st, B, ra, w.VPART));
         else XG_TRY(xgk_rollout_step(st, B, ra));
-        StepIO s = step_io_at(w, *d, t);
-        s.pos = pos_rows; s.gp = w.GP + (size_t)t * B * R; s.mask = unf; s.ldm = 1;
+        StepIO s = step_io_at(w, *d, slot(t));
+        s.pos = pos_rows; s.gp = w.GP + (size_t)slot(t) * B * R; s.mask = unf; s.ldm = 1;
+        if (rows) {                               // state block t & 1 -> the other one; no saved gates
+            const size_t in = (size_t)(t & 1) * B * R, out = (size_t)((t + 1) & 1) * B * R;
+            s.h1 = w.H1 + in; s.c1 = w.C1 + in; s.h2 = w.H2 + in; s.c2 = w.C2 + in;
+            s.h1o = w.H1 + out; s.c1o = w.C1 + out; s.h2o = w.H2 + out; s.c2o = w.C2 + out;
+            s.g1 = nullptr; s.g2 = nullptr; s.t = t; s.rows_per_video = rows_per_video;
+        }
         if (in_step) { s.sel = &sel; s.xt = nullptr; s.tok = tok; }
         // The reference runs the core once more at t = L and discards what it computes (SAModel.py:182,217: the loop ends before
         // those logits are ever read, and no state is returned): that step feeds neither an output nor a gradient and is not run.
         if (t + 1 == T) break;
-        XG_TRY(core_step(st, *d, *p, *run, w, w.Venc, w.vproj, s));
+        XG_TRY(core_step(st, *d, *p, *run, w, Vsrc, vproj_src, s));
         if (t + 1 < T) {
             if (fused_select)
                 XG_TRY(xgk_vocab_part(st, B, R, d->V, s.h2o, R, p->logit_w, p->logit_b, logits_of(t), wr_rows,
                                       w.VPART, temperature > 0.f ? temperature : 1.0f));
             else
-                XG_TRY(xgk_linear(st, w.gm, B, d->V, R, s.h2o, R, p->logit_w, p->logit_b, w.LOGITS + (size_t)t * B * d->V, d->V));
+                XG_TRY(xgk_linear(st, w.gm, B, d->V, R, s.h2o, R, p->logit_w, p->logit_b, logits_of(t), d->V));
         }
     }
     // the steps that chose their own tokens gathered their embedding rows inside the products: the (T, B, E) copy the backward (and a
     // compaction) reads is made here for all of them at once, off the token's path
-    if (step_select && T >= 3)
+    if (step_select && T >= 3 && !rows)
         XG_TRY(xgk_embed_gather(st, p->embed_w, E, w.TOK + B, (T - 2) * B, 1, 0, (T - 2) * B, d->V, w.Xe + (size_t)B * E, E));
     XG_TRY(record_prof(run->prof_event1, st));
     return xgk_rollout_finalize(st, w.alive, n_steps, T - 1, split < B ? 2 : 1);
@@ -1951,6 +1981,71 @@ extern "C" int xgcb_beam_search(void* stream, const XgDims* d, int32_t W, int32_
         XG_TRY(xgk_cap_beam_merge(st, B, ma));
     }
     return xgk_cap_beam_backtrace(st, w.trace, w.r, w.done_score, w.done_at, seq, seq_logp, score, M, W, L);
+}
+
+// ================================================================== the captioner under S templates per video (include/xgate_control.h)
+// rollout_impl over M = B S rows with rows_per_video = S: the per-video part is a whole workspace at T = 1 over the B videos
+// (encoder, Venc, vproj, the initial state), the row part holds what the step loop touches and nothing of size (M,K,.).
+namespace {
+
+struct ControlWs {
+    Ws enc;                        // the B videos
+    Ws step;                       // the M rows: one block per per-step tensor, two per state tensor (every other field stays null)
+    size_t bytes;
+};
+
+ControlWs cc_carve(const XgDims& d, int S, void* base) {
+    ControlWs w{};
+    w.enc = carve(beam_dims(d, d.B), base);
+    w.enc.sh16 = nullptr; w.enc.bytes = w.enc.core_bytes;          // fp32 only: no bf16 mirror region
+    Carver c{static_cast<char*>(base), w.enc.core_bytes};
+    const size_t M = (size_t)d.B * S, K = d.K, R = d.R, A = d.A, E = d.E, V = d.V, T = d.T;
+    Ws& s = w.step;
+    s.H1 = c.take<float>(2 * M * R); s.C1 = c.take<float>(2 * M * R); s.H2 = c.take<float>(2 * M * R); s.C2 = c.take<float>(2 * M * R);
+    s.S = c.take<float>(M * 4 * R); s.S2 = c.take<float>(M * 4 * R);
+    s.Xe = c.take<float>(M * E); s.GP = c.take<float>(M * R); s.POSG = c.take<float>(M * R);
+    s.P = c.take<float>(M * A); s.ALPHA = c.take<float>(M * K); s.AF = c.take<float>(M * R);
+    s.TOK = c.take<int64_t>(T * M); s.TOKLP = c.take<float>(T * M); s.UNF = c.take<float>(T * M); s.LSE = c.take<float>(T * M);
+    s.alive = c.take<int32_t>(4);
+    s.LOGITS = c.take<float>(M * V);                               // one step's raw logits (full-logits choice; the rows a draw re-reads)
+    c.off = (c.off + 15) & ~(size_t)15;
+    s.VPART = c.take<float>(M * ((V + 31) / 32 + 16) * 4);         // per-tile row statistics (row pitch: xg_select.h rs_pitch)
+    s.dsync = c.take<int32_t>(XGK_DSTEP_SYNC_BYTES / sizeof(int32_t));
+    w.bytes = (c.off + 255) & ~(size_t)255;
+    return w;
+}
+
+bool cc_dims_ok(const XgDims* d, int S) {
+    return dims_ok(d) && d->T >= 2 && S >= 1 && (int64_t)d->B * S <= (1 << 20);
+}
+
+}  // namespace
+
+extern "C" int xgcc_version(void) { return XGCC_VERSION; }
+
+extern "C" size_t xgcc_workspace_bytes(const XgDims* d, int32_t S) {
+    if (!cc_dims_ok(d, S)) return 0;
+    return cc_carve(*d, S, nullptr).bytes;
+}
+
+extern "C" int xgcc_rollout(void* stream, const XgDims* d, int32_t S, const XgParams* p, const XgBnState* bn, const XgBatch* x,
+                            const XgRun* run, int mode, const float* uniforms, float temperature, int64_t* seq, float* seq_logp,
+                            int32_t* n_steps, void* ws, size_t ws_bytes) {
+    if (!cc_dims_ok(d, S) || !p || !x || !run || !seq || !seq_logp || !n_steps || !ws) return XG_EINVAL;
+    if (!bn || !bn->rgb_mean || !bn->rgb_var || !bn->opfl_mean || !bn->opfl_var) return XG_EINVAL;
+    if (!x->feats_rgb || !x->feats_opfl || !x->feat_mask || !x->pos_feats) return XG_EINVAL;
+    if (run->train || run->save || run->gemm_mode != 0 || (uintptr_t)ws % 256 != 0) return XG_EINVAL;
+    if (mode != XG_ROLLOUT_GREEDY && mode != XG_ROLLOUT_SAMPLE) return XG_EINVAL;
+    if (mode == XG_ROLLOUT_SAMPLE && (!uniforms || !(temperature > 0.f))) return XG_EINVAL;
+    ControlWs w = cc_carve(*d, S, ws);
+    if (ws_bytes < w.bytes) return XG_EWORKSPACE;
+    const int M = d->B * S;
+    const XgDims de = beam_dims(*d, d->B);
+    XgDims dm = *d; dm.B = M;
+    attach_packed(w.enc, de, run);
+    attach_packed(w.step, dm, run);
+    return rollout_impl((hipStream_t)stream, &dm, p, bn, x, run, mode, uniforms, nullptr, temperature, w.step, seq, seq_logp, n_steps,
+                        M, nullptr, nullptr, &de, &w.enc, S);
 }
 
 extern "C" int xg_rollout_bwd(void* stream, const XgDims* d, const XgParams* p, const XgParams* g, const XgBatch* x,

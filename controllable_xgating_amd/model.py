@@ -589,6 +589,68 @@ class SAModel(nn.Module):
         from .beam import sample_beam
         return sample_beam(self, feats, feat_masks, pos_feats, opt)
 
+    def sample_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, opt={}):
+        """``sample`` for S `pos_feats` rows per video on ONE encoder pass (include/xgate_control.h): the B videos are handed over
+        once, `pos_feats` is (B,S,R), and the result is what ``sample`` gives on the batch with every video repeated S times, row by
+        row: seq (B,S,n) int64 and seqLogprobs (B,S,n).  The encoder, init_hidden and v2a(V) run once per video and every step's
+        attention reads a video's v2a(V) and V once per group of its rows; one enqueue, no host work per step.
+
+        `opt` as in ``sample``: `sample_max` (1: greedy), `temperature`, `uniforms` (L + 1, B*S), `async` (no host sync: full-width
+        (B,S,L) tensors and the device-side n).  Eval mode, fp32 and device tensors only; `beam_size` > 1 and `forced_tokens` are not
+        served.  Nothing returned carries an autograd graph."""
+        from . import _native_control as ncc
+        if self.training:
+            raise NotImplementedError("sample_per_video runs in eval mode only: call model.eval() first")
+        if self.precision != "fp32":
+            raise NotImplementedError("sample_per_video is fp32 only (precision = %r)" % (self.precision,))
+        if opt.get("beam_size", 1) > 1:
+            raise NotImplementedError("sample_per_video has no beam search: beam_size must be 1")
+        if opt.get("forced_tokens", None) is not None:
+            raise NotImplementedError("sample_per_video has no replay mode: forced_tokens must be None")
+        B, K = feats_rgb.shape[0], feats_rgb.shape[1]
+        if pos_feats.dim() != 3 or pos_feats.shape[0] != B or pos_feats.shape[1] < 1 or pos_feats.shape[2] != self.rnn_size:
+            raise ValueError("pos_feats (B = %d, S, R = %d) expected, got %s" % (B, self.rnn_size, tuple(pos_feats.shape)))
+        for t in (feats_rgb, feats_opfl, feat_mask, pos_feats):
+            if not t.is_cuda:
+                raise NotImplementedError("sample_per_video needs device tensors: there is no CPU path")
+        S, L = int(pos_feats.shape[1]), self.seq_length
+        M = B * S
+        dev = feats_rgb.device
+        mode = nv.XG_ROLLOUT_GREEDY if opt.get("sample_max", 1) else nv.XG_ROLLOUT_SAMPLE
+        temperature = float(opt.get("temperature", 1.0))
+        uniforms = opt.get("uniforms", None)
+        if mode == nv.XG_ROLLOUT_SAMPLE:
+            if uniforms is None:
+                uniforms = torch.rand(L + 1, M, device=dev, dtype=torch.float32)
+            uniforms = uniforms.detach().contiguous().float()
+            if tuple(uniforms.shape) != (L + 1, M) or not uniforms.is_cuda:
+                raise ValueError("uniforms (L + 1 = %d, B*S = %d) on the device expected, got %s" % (L + 1, M, tuple(uniforms.shape)))
+        else:
+            uniforms = None
+        lib = ncc.lib()
+        d = self._dims(B, K, L + 1)
+        key = (B, K, L, S, str(dev))
+        ws = getattr(self, "_control_ws", {}).get(key)
+        if ws is None:
+            n = lib.xgcc_workspace_bytes(C.byref(d), S)
+            if n == 0:
+                raise nv.XgError("xgcc_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S))
+            ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+            self._control_ws = {key: ws}                # (one shape at a time, as beam_captions keeps its workspace)
+        wp, wn = _ws_ptr(ws)
+        with torch.no_grad():
+            b, keep = self._batch(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(M, self.rnn_size))
+            ps, bn, run = self._params_struct(), self._bn_struct(), self._run(False)
+            seq = torch.empty(B, S, L, dtype=torch.int64, device=dev)
+            slp = torch.empty(B, S, L, dtype=torch.float32, device=dev)
+            n = torch.empty(1, dtype=torch.int32, device=dev)
+            nv.check(lib.xgcc_rollout(_stream(), C.byref(d), S, C.byref(ps), C.byref(bn), C.byref(b), C.byref(run), mode,
+                                      nv.ptr(uniforms), temperature, nv.ptr(seq), nv.ptr(slp), nv.ptr(n), wp, wn), "xgcc_rollout")
+        if opt.get("async", False):
+            return seq, slp, n
+        n = int(n.item())
+        return seq[:, :, :n], slp[:, :, :n]
+
     def beam_captions(self, feats_rgb, feats_opfl, feat_mask, pos_feats, beam_size=5, suppress_token=1, return_trace=False):
         """The W = beam_size captions the model finds most likely for each of the B videos (include/xgate_beam.h: the search of
         beam.py / the reference's sample_beam, SAModel.py:129-161, as ONE enqueue with no host work per step).  Returns (seq
