@@ -5,15 +5,13 @@
 //                          log-softmax is never written.  The row is read from memory ONCE and staged in LDS (80 KB at V = 20000);
 //                          a row beyond 150 KiB is read three times instead.  Ranking is on lp = logit - lse itself, so two
 //                          logits that round to one lp are ordered by word index like the host search's torch.topk over lp.
-//   cap_beam_merge_kernel  one workgroup per video: wave 0 ranks the rows * W candidates by counting (stable), thread 0 writes the
-//                          step's (token, parent, r), the sums, the next tokens and the video's best-W done list, and every thread
-//                          gathers h1, c1, h2, c2 of slot v from its parent out of the step's OUTPUT buffer into its INPUT buffer.
-// After the loop cap_beam_backtrace_kernel follows each done entry's parents back.  cap_beam_repeat_kernel row-repeats what was
-// computed once per video (xgk_compact copies contiguous blocks: rows b W + slot of video b are not one).
-// Plain stores, no atomics, one fixed order for every sum.
+//   cap_beam_merge_kernel  one workgroup per video: fills the candidate tables from topv / topi, runs steps 3-5 of the rule
+//                          (beam_merge, xg_beam_core.h), and every thread gathers h1, c1, h2, c2 of slot v from its parent out of
+//                          the step's OUTPUT buffer into its INPUT buffer.
+// After the loop cap_beam_backtrace_kernel follows each done entry's parents back (beam_backtrace_row).  cap_beam_repeat_kernel
+// row-repeats what was computed once per video (xgk_compact copies contiguous blocks: rows b W + slot of video b are not one).
 #include "xg_common.h"
 #include "xg_kernels.h"
-#include "../../include/xgate_beam.h"
 
 namespace {
 
@@ -21,15 +19,10 @@ constexpr int CB_TPB = 256;
 // the top-W kernel's workgroup: a row of V = 20000 is 20 elements a thread (38 -> 31 us over 320 rows against 256 threads;
 // docs/CAPTION_BEAM.md has what else was measured)
 constexpr int TW_TPB = 1024, TW_WAVES = TW_TPB / 64;
-constexpr int CB_MAX = XGCB_MAX_BEAM;
+constexpr int CB_MAX = XG_BEAM_MAX;
 constexpr int CB_EMPTY = 0x7fffffff;                      // word index of a list entry that holds nothing
 constexpr int CB_STAGE_BYTES = 150 * 1024;                // the most dynamic LDS a row may take (as xgk_rollout_step)
-static_assert(CB_MAX * CB_MAX <= 64, "one wave ranks a video's candidates");
 static_assert(TW_WAVES * CB_MAX <= TW_TPB, "one thread per entry of the last ranking");
-
-// the order of the search: larger value first, lower word index first on exact ties.  Total on non-NaN values; a NaN is
-// better than nothing and nothing is better than it, so it is never kept.
-__device__ __forceinline__ bool cb_better(float v, int i, float ov, int oi) { return v > ov || (v == ov && i < oi); }
 
 template <int W, bool STAGE>
 __global__ void __launch_bounds__(TW_TPB) cap_beam_topw_kernel(const float* __restrict__ logits, int64_t ld, int V, int suppress,
@@ -98,10 +91,10 @@ __global__ void __launch_bounds__(TW_TPB) cap_beam_topw_kernel(const float* __re
         float v = x - lse;
         if (i == suppress) v -= 1000.0f;
         int ix = i;
-        if (cb_better(v, ix, bv[W - 1], bi[W - 1])) {
+        if (beam_before(v, ix, bv[W - 1], bi[W - 1])) {
 #pragma unroll
             for (int k = 0; k < W; ++k) {
-                if (cb_better(v, ix, bv[k], bi[k])) {           // from here on v is what the list pushes down
+                if (beam_before(v, ix, bv[k], bi[k])) {         // from here on v is what the list pushes down
                     const float tv = bv[k]; const int ti = bi[k];
                     bv[k] = v; bi[k] = ix; v = tv; ix = ti;
                 }
@@ -117,7 +110,7 @@ __global__ void __launch_bounds__(TW_TPB) cap_beam_topw_kernel(const float* __re
         for (int off = 32; off > 0; off >>= 1) {
             const float ov = __shfl_xor(v, off);
             const int oi = __shfl_xor(ix, off);
-            if (cb_better(ov, oi, v, ix)) { v = ov; ix = oi; }
+            if (beam_before(ov, oi, v, ix)) { v = ov; ix = oi; }
         }
         if (lane == 0) { cv[wave * W + r] = v; ci[wave * W + r] = ix; }
         if (bi[0] == ix) {
@@ -136,7 +129,7 @@ __global__ void __launch_bounds__(TW_TPB) cap_beam_topw_kernel(const float* __re
         for (int j = 0; j < TW_WAVES * W; ++j) {
             const float ov = cv[j];
             const int oi = ci[j];
-            rank += (cb_better(ov, oi, v, ix) || (ov == v && oi == ix && j < tid)) ? 1 : 0;
+            rank += (beam_before(ov, oi, v, ix) || (ov == v && oi == ix && j < tid)) ? 1 : 0;
         }
         if (rank < W) {
             topv[(size_t)blockIdx.x * W + rank] = v;
@@ -162,14 +155,12 @@ int launch_topw(hipStream_t st, const float* logits, int64_t ld, int M, int V, i
 }
 
 __global__ void __launch_bounds__(CB_TPB) cap_beam_merge_kernel(CapBeamMergeArgs a) {
-    __shared__ float c_lp[CB_MAX * CB_MAX], c_p[CB_MAX * CB_MAX], s_lp[CB_MAX], s_p[CB_MAX];
-    __shared__ int c_tok[CB_MAX * CB_MAX], s_q[CB_MAX], s_tok[CB_MAX];
+    __shared__ BeamTables T;
     const int tid = threadIdx.x;
-    const int R = a.R, W = a.W, t = a.t, L = a.L;
+    const int R = a.R, W = a.book.W;
     const size_t b = blockIdx.x, row0 = b * W;
-    const int rows = t == 0 ? 1 : W;          // (every slot holds the video's initial state at t = 0)
-    // (a NaN ranks nowhere: whatever stays unwritten below is slot 0 / word 0, never an index out of range)
-    if (tid < CB_MAX * CB_MAX) {
+    const int rows = a.book.t == 0 ? 1 : W;   // (every slot holds the video's initial state at t = 0)
+    if (tid < CB_MAX * CB_MAX) {              // (whatever topw left unwritten is word 0, never an index out of range)
         const int q = tid / CB_MAX, k = tid - q * CB_MAX;
         float lp = 0.f;
         int tk = 0;
@@ -178,100 +169,31 @@ __global__ void __launch_bounds__(CB_TPB) cap_beam_merge_kernel(CapBeamMergeArgs
             tk = a.topi[(row0 + q) * W + k];
             tk = tk < 0 ? 0 : (tk >= a.V ? a.V - 1 : tk);
         }
-        c_lp[tid] = lp; c_tok[tid] = tk; c_p[tid] = 0.f;
+        T.c_lp[tid] = lp; T.c_tok[tid] = tk;
     }
-    if (tid < CB_MAX) { s_lp[tid] = 0.f; s_p[tid] = 0.f; s_q[tid] = 0; s_tok[tid] = 0; }
-    __syncthreads();
-    const int ncand = W * rows;               // candidate i = c_rank * rows + q
-    int cq = 0, cr = 0;
-    float p = 0.f;
-    if (tid < ncand) {
-        cr = tid / rows;
-        cq = tid - cr * rows;
-        p = (t == 0 ? 0.f : a.sum[row0 + cq]) + c_lp[cq * CB_MAX + cr];
-        c_p[tid] = p;
-    }
-    __syncthreads();
-    if (tid < ncand) {                        // stable descending rank; the first W are the new slots
-        int rank = 0;
-        for (int i = 0; i < ncand; ++i) {
-            const float o = c_p[i];
-            rank += (o > p || (o == p && i < tid)) ? 1 : 0;
-        }
-        if (rank < W) {
-            s_q[rank] = cq;
-            s_tok[rank] = c_tok[cq * CB_MAX + cr];
-            s_lp[rank] = c_lp[cq * CB_MAX + cr];
-            s_p[rank] = p;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float* ds = a.done_score + row0;
-        int32_t* da = a.done_at + row0 * 2;
-        int n = t == 0 ? 0 : a.done_n[b];
-        n = n < 0 ? 0 : (n > W ? W : n);
-        for (int v = 0; v < W; ++v) {
-            const size_t e = (b * L + t) * W + v;
-            a.trace[2 * e] = s_tok[v];
-            a.trace[2 * e + 1] = s_q[v];
-            if (a.trace_out) { a.trace_out[2 * e] = s_tok[v]; a.trace_out[2 * e + 1] = s_q[v]; }
-            a.r[e] = s_lp[v];
-            a.tok[row0 + v] = s_tok[v];
-            float sm = s_p[v];
-            if (s_tok[v] == 0 || t == L - 1) {
-                int pos = n;
-                while (pos > 0 && ds[pos - 1] < sm) --pos;         // after entries of equal score
-                if (pos < W) {
-                    const int last = n < W ? n : W - 1;
-                    for (int i = last; i > pos; --i) { ds[i] = ds[i - 1]; da[2 * i] = da[2 * i - 2]; da[2 * i + 1] = da[2 * i - 1]; }
-                    ds[pos] = sm; da[2 * pos] = t; da[2 * pos + 1] = v;
-                    if (n < W) ++n;
-                }
-                sm = -1000.0f;
-            }
-            a.sum[row0 + v] = sm;
-        }
-        a.done_n[b] = n;
-    }
+    beam_merge(T, a.book, b, rows);
     // slot v takes h1, c1, h2, c2 of its parent: out of the buffer the step wrote, into the buffer the next step reads
     if (a.vec) {
         const int R4 = R >> 2;
         for (int i = tid; i < 4 * W * R4; i += CB_TPB) {
             const int k = i / (W * R4), rem = i - k * (W * R4);
             const int v = rem / R4, j = rem - v * R4;
-            reinterpret_cast<float4*>(a.dst[k] + (row0 + v) * R)[j] = reinterpret_cast<const float4*>(a.src[k] + (row0 + s_q[v]) * R)[j];
+            reinterpret_cast<float4*>(a.dst[k] + (row0 + v) * R)[j] = reinterpret_cast<const float4*>(a.src[k] + (row0 + T.s_q[v]) * R)[j];
         }
     } else {
         for (int i = tid; i < 4 * W * R; i += CB_TPB) {
             const int k = i / (W * R), rem = i - k * (W * R);
             const int v = rem / R, j = rem - v * R;
-            a.dst[k][(row0 + v) * R + j] = a.src[k][(row0 + s_q[v]) * R + j];
+            a.dst[k][(row0 + v) * R + j] = a.src[k][(row0 + T.s_q[v]) * R + j];
         }
     }
 }
 
 // one thread per (video, rank): the done entry's beam, read back along its parents
-__global__ void __launch_bounds__(CB_TPB) cap_beam_backtrace_kernel(const int32_t* __restrict__ trace, const float* __restrict__ r,
-                                                                    const float* __restrict__ done_score,
-                                                                    const int32_t* __restrict__ done_at, int64_t* seq,
-                                                                    float* seq_logp, float* score, int M, int W, int L) {
+__global__ void __launch_bounds__(CB_TPB) cap_beam_backtrace_kernel(BeamBook<int64_t> k, int64_t* seq, float* seq_logp, float* score,
+                                                                    int M) {
     const int i = blockIdx.x * CB_TPB + threadIdx.x;
-    if (i >= M) return;
-    const size_t b = i / W;
-    int tf = done_at[2 * (size_t)i], s = done_at[2 * (size_t)i + 1];
-    tf = tf < 0 ? 0 : (tf >= L ? L - 1 : tf);
-    int64_t* sq = seq + (size_t)i * L;
-    float* lp = seq_logp + (size_t)i * L;
-    score[i] = done_score[i];
-    for (int t = L - 1; t > tf; --t) { sq[t] = 0; lp[t] = 0.f; }
-    for (int t = tf; t >= 0; --t) {
-        s = s < 0 ? 0 : (s >= W ? W - 1 : s);
-        const size_t e = (b * L + t) * W + s;
-        sq[t] = trace[2 * e];
-        lp[t] = r[e];
-        s = trace[2 * e + 1];
-    }
+    if (i < M) beam_backtrace_row(k, i, seq, seq_logp, score);
 }
 
 // dst row b W + slot = src row b, for every entry in one launch (blockIdx.y: the entry)
@@ -324,7 +246,8 @@ int xgk_cap_beam_topw(hipStream_t st, const float* logits, int64_t ld, int M, in
 }
 
 int xgk_cap_beam_merge(hipStream_t st, int B, CapBeamMergeArgs a) {
-    if (B <= 0 || a.W < 1 || a.W > CB_MAX || a.R <= 0 || a.L <= 0 || a.t < 0 || a.t >= a.L) return XG_EINVAL;
+    const BeamBook<int64_t>& k = a.book;
+    if (B <= 0 || k.W < 1 || k.W > CB_MAX || a.R <= 0 || k.L <= 0 || k.t < 0 || k.t >= k.L) return XG_EINVAL;
     uintptr_t bits = 0;
     for (int k = 0; k < 4; ++k) bits |= reinterpret_cast<uintptr_t>(a.src[k]) | reinterpret_cast<uintptr_t>(a.dst[k]);
     a.vec = (a.R % 4 == 0 && bits % 16 == 0) ? 1 : 0;
@@ -333,10 +256,9 @@ int xgk_cap_beam_merge(hipStream_t st, int B, CapBeamMergeArgs a) {
     return XG_OK;
 }
 
-int xgk_cap_beam_backtrace(hipStream_t st, const int32_t* trace, const float* r, const float* done_score, const int32_t* done_at,
-                           int64_t* seq, float* seq_logp, float* score, int M, int W, int L) {
-    hipLaunchKernelGGL(cap_beam_backtrace_kernel, dim3(xg_cdiv(M, CB_TPB)), dim3(CB_TPB), 0, st, trace, r, done_score, done_at, seq,
-                       seq_logp, score, M, W, L);
+int xgk_cap_beam_backtrace(hipStream_t st, int B, const BeamBook<int64_t>& book, int64_t* seq, float* seq_logp, float* score) {
+    const int M = B * book.W;
+    hipLaunchKernelGGL(cap_beam_backtrace_kernel, dim3(xg_cdiv(M, CB_TPB)), dim3(CB_TPB), 0, st, book, seq, seq_logp, score, M);
     XG_CHECK_LAUNCH();
     return XG_OK;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include "xg_common.h"
 #include "xg_select.h"
+#include "xg_beam_core.h"
 #include <cstddef>
 
 // ---- xg_gemm.hip
@@ -373,20 +374,12 @@ int xgk_cap_beam_repeat(hipStream_t st, const CapBeamRepeatArgs& a, int B, int W
 int xgk_cap_beam_topw(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, float* topv, int32_t* topi);
 struct CapBeamMergeArgs {
     const float* topv; const int32_t* topi;   // (M,W) of this step
-    float* sum;                   // (M) running sums (not read at t = 0)
-    int64_t* tok;                 // (M) the step's tokens, fed by the next step
-    int32_t* trace;               // (B,L,W,2) (token, parent) of every slot and step
-    float* r;                     // (B,L,W) the log-probability of that token
-    int32_t* trace_out;           // the caller's copy of trace, or null
-    float* done_score;            // (B,W) the best completions so far, descending
-    int32_t* done_at;             // (B,W,2) their (step, slot)
-    int32_t* done_n;              // (B) how many (not read at t = 0)
+    BeamBook<int64_t> book;
     const float* src[4]; float* dst[4];       // h1, c1, h2, c2 (M,R): what the step wrote -> what the next step reads
-    int R, V, L, W, t, vec;       // (vec: set by the launcher)
+    int R, V, vec;                // (vec: set by the launcher)
 };
 int xgk_cap_beam_merge(hipStream_t st, int B, CapBeamMergeArgs a);
-int xgk_cap_beam_backtrace(hipStream_t st, const int32_t* trace, const float* r, const float* done_score, const int32_t* done_at,
-                           int64_t* seq, float* seq_logp, float* score, int M, int W, int L);
+int xgk_cap_beam_backtrace(hipStream_t st, int B, const BeamBook<int64_t>& book, int64_t* seq, float* seq_logp, float* score);
 
 // ---- xg_optim.hip
 int xgk_clip_adam(hipStream_t st, int64_t n, float* p, float* g, float* m, float* v, float lr, float b1, float b2,

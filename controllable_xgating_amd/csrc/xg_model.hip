@@ -1884,9 +1884,8 @@ struct BeamWs {
     Ws step;                       // what core_step touches, over M rows (every other field stays null)
     float *Venc, *vproj, *pos;     // row-repeated (M,K,R), (M,K,A), (M,R)
     float* st[2][4];               // h1, c1, h2, c2 (M,R): [0] read by the step, [1] written by it
-    float *topv, *sum, *r, *done_score;
-    int32_t *topi, *trace, *done_at, *done_n;
-    int64_t* tok;
+    float* topv; int32_t* topi;    // (M,W) every row's W best of the step
+    BeamBook<int64_t> book;
     size_t bytes;
 };
 
@@ -1908,9 +1907,7 @@ BeamWs beam_carve(const XgDims& d, int W, void* base) {
     w.Venc = c.take<float>(M * K * R); w.vproj = c.take<float>(M * K * A); w.pos = c.take<float>(M * R);
     for (int i = 0; i < 2; ++i) for (int k = 0; k < 4; ++k) w.st[i][k] = c.take<float>(M * R);
     w.topv = c.take<float>(M * W); w.topi = c.take<int32_t>(M * W);
-    w.sum = c.take<float>(M); w.tok = c.take<int64_t>(M);
-    w.trace = c.take<int32_t>(B * L * W * 2); w.r = c.take<float>(B * L * W);
-    w.done_score = c.take<float>(M); w.done_at = c.take<int32_t>(M * 2); w.done_n = c.take<int32_t>(B);
+    w.book = beam_book_carve<int64_t>(c, B, W, L);
     w.bytes = (c.off + 255) & ~(size_t)255;
     return w;
 }
@@ -1956,18 +1953,17 @@ extern "C" int xgcb_beam_search(void* stream, const XgDims* d, int32_t W, int32_
         XG_TRY(xgk_cap_beam_repeat(st, ra, B, W));
     }
     XG_TRY(zero_dsync(st, w.step));
-    if (hipMemsetAsync(w.tok, 0, sizeof(int64_t) * (size_t)M, st) != hipSuccess) return XG_EHIP;        // BOS
+    if (hipMemsetAsync(w.book.tok, 0, sizeof(int64_t) * (size_t)M, st) != hipSuccess) return XG_EHIP;   // BOS
     CapBeamMergeArgs ma{};
-    ma.topv = w.topv; ma.topi = w.topi; ma.sum = w.sum; ma.tok = w.tok; ma.trace = w.trace; ma.r = w.r; ma.trace_out = trace;
-    ma.done_score = w.done_score; ma.done_at = w.done_at; ma.done_n = w.done_n;
+    ma.topv = w.topv; ma.topi = w.topi; ma.book = w.book; ma.book.trace_out = trace;
     for (int k = 0; k < 4; ++k) { ma.src[k] = w.st[1][k]; ma.dst[k] = w.st[0][k]; }
-    ma.R = R; ma.V = V; ma.L = L; ma.W = W;
+    ma.R = R; ma.V = V;
     const bool pk = step_packed(w.step, dm);
     for (int t = 0; t < L; ++t) {
         StepIO s{};
-        if (pk) s.tok = w.tok;                    // token rows gathered by index inside the products
+        if (pk) s.tok = w.book.tok;               // token rows gathered by index inside the products
         else {
-            XG_TRY(xgk_embed_gather(st, p->embed_w, E, w.tok, M, 1, 0, M, V, w.step.Xe, E));
+            XG_TRY(xgk_embed_gather(st, p->embed_w, E, w.book.tok, M, 1, 0, M, V, w.step.Xe, E));
             s.xt = w.step.Xe;
         }
         s.pos = w.pos; s.gp = w.step.GP; s.posg = w.step.POSG; s.pre1 = nullptr; s.mask = nullptr; s.ldm = 1;
@@ -1977,10 +1973,10 @@ extern "C" int xgcb_beam_search(void* stream, const XgDims* d, int32_t W, int32_
         XG_TRY(core_step(st, dm, *p, *run, w.step, w.Venc, w.vproj, s));
         XG_TRY(xgk_linear(st, 0, M, V, R, s.h2o, R, p->logit_w, p->logit_b, w.step.LOGITS, V));
         XG_TRY(xgk_cap_beam_topw(st, w.step.LOGITS, V, M, V, W, suppress_token, w.topv, w.topi));
-        ma.t = t;
+        ma.book.t = t;
         XG_TRY(xgk_cap_beam_merge(st, B, ma));
     }
-    return xgk_cap_beam_backtrace(st, w.trace, w.r, w.done_score, w.done_at, seq, seq_logp, score, M, W, L);
+    return xgk_cap_beam_backtrace(st, B, w.book, seq, seq_logp, score);
 }
 
 // ================================================================== the captioner under S templates per video (include/xgate_control.h)

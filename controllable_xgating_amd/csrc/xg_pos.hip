@@ -371,6 +371,7 @@ struct Carve {
     float* base;
     size_t off;
     float* take(size_t n) { float* r = base ? base + off : nullptr; off += (n + 63) / 64 * 64; return r; }
+    template <typename T> T* take(size_t n) { static_assert(sizeof(T) == sizeof(float), "counted in floats"); return (T*)take(n); }
 };
 
 struct Ws {
@@ -1556,21 +1557,18 @@ extern "C" int xgps_sample_templates(void* stream, const XgpDims* d, int32_t S, 
 //   1. pos_cell of all W rows into LDS (mask 1: dead slots keep running, as the reference's get_logprobs_state does); every c and h
 //      of the step before is read here, before anything is written.
 //   2. pos_head_logits per row, pos_lse_* per row (wave q serves row q), the -1000 on `suppress_tag`.
-//   3. per row the W largest log-probabilities in descending order, lower category first on ties: C <= 64 by counting (one lane per
-//      category), beyond by lane 0 of the row's wave serially.  Candidate c_rank * rows + q carries p = sum[q] + lp (one fp32 add);
-//      wave 0 ranks the <= 64 candidates by counting with the stable tie rule (lower index first) and the first W are the new slots.
-//   4. thread 0: the step's (token, parent, r), the sums, and the video's best-W done list (an insertion goes after entries of
-//      equal score, so the list is the first W of a stable descending sort of every completion).
+//   3. per row the W largest log-probabilities in descending order, lower category first on ties, into the candidate tables:
+//      C <= 64 by counting (one lane per category), beyond by lane 0 of the row's wave serially.
+//   4. beam_merge (xg_beam_core.h): the rest of step 3 and steps 4-5 of the rule, shared with the captioner's search.
 //   5. every thread: h and c of slot v from parent q out of LDS.  The rows are this workgroup's alone: barrier, then write.
-// pos_beam_backtrace_kernel then follows each done entry's parents back through the stored (token, parent) and writes the outputs,
-// and pos_first_zero_col_kernel n_out.  Plain stores from one lane, no atomics, one fixed order for every sum.
+// pos_beam_backtrace_kernel then follows each done entry's parents back (beam_backtrace_row) and appends the masks, and
+// pos_first_zero_col_kernel writes n_out.
 // ==================================================================================================================================
 #include "../../include/xgate_pos_beam.h"
 
 namespace {
 
-constexpr int BEAM_MAX = XGPB_MAX_BEAM;
-static_assert(BEAM_MAX * BEAM_MAX <= 64, "one wave ranks a video's candidates");
+constexpr int BEAM_MAX = XG_BEAM_MAX;
 static_assert(BEAM_MAX <= STEP_WAVES, "one wave per row of the video");
 
 struct BeamArgs {
@@ -1579,41 +1577,30 @@ struct BeamArgs {
     const float *logit_w, *logit_b;
     float* X;                    // (M,2R): h read from and h' written to columns R..2R
     float* c;                    // (M,R) cell state, in place
-    float* sum;                  // (M) running sums (not read at t = 0)
-    int32_t* tok;                // (M) the step's tokens, fed by the next step
-    int32_t* trace;              // (B,L,W,2) (token, parent) of every slot and step
-    float* r;                    // (B,L,W) the log-probability of that token
-    int32_t* trace_out;          // the caller's copy of trace, or null
-    float* done_score;           // (B,W) the best completions so far, descending
-    int32_t* done_at;            // (B,W,2) their (step, slot)
-    int32_t* done_n;             // (B) how many (not read at t = 0)
-    int R, C, L, W, t, suppress;
+    BeamBook<int32_t> book;
+    int R, C, suppress;
 };
 
 __global__ void __launch_bounds__(STEP_TPB) pos_beam_merge_kernel(BeamArgs a) {
     extern __shared__ float lds[];
-    // (896 bytes: the fixed part of XGPB_LDS_BYTES is 1024)
-    __shared__ float c_lp[BEAM_MAX * BEAM_MAX], c_p[BEAM_MAX * BEAM_MAX], s_lp[BEAM_MAX], s_p[BEAM_MAX];
-    __shared__ int c_tok[BEAM_MAX * BEAM_MAX], s_q[BEAM_MAX], s_tok[BEAM_MAX];
+    __shared__ BeamTables T;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int R = a.R, C = a.C, W = a.W, t = a.t, L = a.L;
+    const int R = a.R, C = a.C, W = a.book.W, t = a.book.t;
     const size_t b = blockIdx.x, row0 = b * W;
     float* hs = lds;                          // W x R
     float* cs = hs + (size_t)W * R;           // W x R
     float* lg = cs + (size_t)W * R;           // W x C: the logits, then the log-probabilities
-    // (a NaN ranks nowhere: whatever stays unwritten below is slot 0 / category 0, never an index out of range)
-    if (tid < BEAM_MAX * BEAM_MAX) { c_lp[tid] = 0.f; c_p[tid] = 0.f; c_tok[tid] = 0; }
-    if (tid < BEAM_MAX) { s_lp[tid] = 0.f; s_p[tid] = 0.f; s_q[tid] = 0; s_tok[tid] = 0; }
+    // (a NaN ranks nowhere: whatever stays unwritten below is category 0, never an index out of range)
+    if (tid < BEAM_MAX * BEAM_MAX) { T.c_lp[tid] = 0.f; T.c_tok[tid] = 0; }
     for (int i = tid; i < W * R; i += STEP_TPB) {
         const int q = i / R, j = i - q * R;
         const size_t row = row0 + q;
-        const int64_t tk = t == 0 ? 0 : pos_clamp_tag(a.tok[row], C);
+        const int64_t tk = t == 0 ? 0 : pos_clamp_tag(a.book.tok[row], C);
         const PosCell o = pos_cell(a.S + row * 4 * R, a.tab + (size_t)tk * 4 * R, R, j, a.c[row * R + j], a.X[row * 2 * R + R + j], 1.0f);
         hs[i] = o.hn;
         cs[i] = o.cn;
     }
     const int rows = t == 0 ? 1 : W;          // (every slot holds the video's initial state at t = 0)
-    const int cols = W < C ? W : C;
     for (int q = 0; q < rows; ++q) pos_head_logits(a.logit_w, a.logit_b, hs + (size_t)q * R, lg + (size_t)q * C, R, C);
     if (wave < rows) {                        // wave q: the log-probabilities of row q, in place
         float* lr = lg + (size_t)wave * C;
@@ -1631,118 +1618,51 @@ __global__ void __launch_bounds__(STEP_TPB) pos_beam_merge_kernel(BeamArgs a) {
         }
     }
     __syncthreads();
-    if (wave < rows) {                        // the `cols` largest of row q, descending, lower category first on ties
+    if (wave < rows) {                        // the W largest of row q, descending, lower category first on ties (the gate: W <= C)
         const float* lr = lg + (size_t)wave * C;
         if (C <= 64) {
             if (lane < C) {
                 const float me = lr[lane];
                 int rank = 0;
-                for (int cc = 0; cc < C; ++cc) {
-                    const float o = lr[cc];
-                    rank += (o > me || (o == me && cc < lane)) ? 1 : 0;
-                }
-                if (rank < cols) { c_lp[wave * BEAM_MAX + rank] = me; c_tok[wave * BEAM_MAX + rank] = lane; }
+                for (int cc = 0; cc < C; ++cc) rank += beam_before(lr[cc], cc, me, lane) ? 1 : 0;
+                if (rank < W) { T.c_lp[wave * BEAM_MAX + rank] = me; T.c_tok[wave * BEAM_MAX + rank] = lane; }
             }
         } else if (lane == 0) {
             float pv = INFINITY;
             int pc = -1;
-            for (int k = 0; k < cols; ++k) {  // the largest of what comes after the pick before in that order
+            for (int k = 0; k < W; ++k) {     // the largest of what comes after the pick before in that order
                 float bv = 0.f;
                 int bc = -1;
                 for (int cc = 0; cc < C; ++cc) {
                     const float o = lr[cc];
-                    if ((o < pv || (o == pv && cc > pc)) && (bc < 0 || o > bv)) { bv = o; bc = cc; }
+                    if (beam_before(pv, pc, o, cc) && (bc < 0 || o > bv)) { bv = o; bc = cc; }
                 }
                 if (bc < 0) break;
-                c_lp[wave * BEAM_MAX + k] = bv;
-                c_tok[wave * BEAM_MAX + k] = bc;
+                T.c_lp[wave * BEAM_MAX + k] = bv;
+                T.c_tok[wave * BEAM_MAX + k] = bc;
                 pv = bv;
                 pc = bc;
             }
         }
     }
-    __syncthreads();
-    const int ncand = cols * rows;            // candidate i = c_rank * rows + q
-    int cq = 0, cr = 0;
-    float p = 0.f;
-    if (wave == 0 && lane < ncand) {
-        cr = lane / rows;
-        cq = lane - cr * rows;
-        p = (t == 0 ? 0.f : a.sum[row0 + cq]) + c_lp[cq * BEAM_MAX + cr];
-        c_p[lane] = p;
-    }
-    __syncthreads();
-    if (wave == 0 && lane < ncand) {          // stable descending rank; the first W are the new slots
-        int rank = 0;
-        for (int i = 0; i < ncand; ++i) {
-            const float o = c_p[i];
-            rank += (o > p || (o == p && i < lane)) ? 1 : 0;
-        }
-        if (rank < W) {
-            s_q[rank] = cq;
-            s_tok[rank] = c_tok[cq * BEAM_MAX + cr];
-            s_lp[rank] = c_lp[cq * BEAM_MAX + cr];
-            s_p[rank] = p;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float* ds = a.done_score + row0;
-        int32_t* da = a.done_at + row0 * 2;
-        int n = t == 0 ? 0 : a.done_n[b];
-        for (int v = 0; v < W; ++v) {
-            const size_t e = (b * L + t) * W + v;
-            a.trace[2 * e] = s_tok[v];
-            a.trace[2 * e + 1] = s_q[v];
-            if (a.trace_out) { a.trace_out[2 * e] = s_tok[v]; a.trace_out[2 * e + 1] = s_q[v]; }
-            a.r[e] = s_lp[v];
-            a.tok[row0 + v] = s_tok[v];
-            float sm = s_p[v];
-            if (s_tok[v] == 0 || t == L - 1) {
-                int pos = n;
-                while (pos > 0 && ds[pos - 1] < sm) --pos;         // after entries of equal score
-                if (pos < W) {
-                    const int last = n < W ? n : W - 1;
-                    for (int i = last; i > pos; --i) { ds[i] = ds[i - 1]; da[2 * i] = da[2 * i - 2]; da[2 * i + 1] = da[2 * i - 1]; }
-                    ds[pos] = sm; da[2 * pos] = t; da[2 * pos + 1] = v;
-                    if (n < W) ++n;
-                }
-                sm = -1000.0f;
-            }
-            a.sum[row0 + v] = sm;
-        }
-        a.done_n[b] = n;
-    }
+    beam_merge(T, a.book, b, rows);
     for (int i = tid; i < W * R; i += STEP_TPB) {
         const int v = i / R, j = i - v * R;
-        const int q = s_q[v];
+        const int q = T.s_q[v];
         a.X[(row0 + v) * 2 * R + R + j] = hs[(size_t)q * R + j];
         a.c[(row0 + v) * R + j] = cs[(size_t)q * R + j];
     }
 }
 
 // one thread per (video, rank): the done entry's beam, read back along its parents
-__global__ void __launch_bounds__(POS_TPB) pos_beam_backtrace_kernel(const int32_t* __restrict__ trace, const float* __restrict__ r,
-                                                                     const float* __restrict__ done_score,
-                                                                     const int32_t* __restrict__ done_at, int64_t* templates,
-                                                                     float* tag_logp, float* score, float* masks, int M, int W, int L) {
+__global__ void __launch_bounds__(POS_TPB) pos_beam_backtrace_kernel(BeamBook<int32_t> k, int64_t* templates, float* tag_logp,
+                                                                     float* score, float* masks, int M) {
     const int i = blockIdx.x * POS_TPB + threadIdx.x;
     if (i >= M) return;
-    const size_t b = i / W;
-    int tf = done_at[2 * (size_t)i], s = done_at[2 * (size_t)i + 1];
-    tf = tf < 0 ? 0 : (tf >= L ? L - 1 : tf);
-    int64_t* tm = templates + (size_t)i * L;
-    float* lp = tag_logp + (size_t)i * L;
+    const int L = k.L;
+    beam_backtrace_row(k, i, templates, tag_logp, score);
+    const int64_t* tm = templates + (size_t)i * L;
     float* mk = masks + (size_t)i * (L + 1);
-    score[i] = done_score[i];
-    for (int t = L - 1; t > tf; --t) { tm[t] = 0; lp[t] = 0.f; }
-    for (int t = tf; t >= 0; --t) {
-        s = s < 0 ? 0 : (s >= W ? W - 1 : s);
-        const size_t e = (b * L + t) * W + s;
-        tm[t] = trace[2 * e];
-        lp[t] = r[e];
-        s = trace[2 * e + 1];
-    }
     float m = 1.0f;
     mk[0] = m;
     for (int t = 1; t <= L; ++t) {
@@ -1754,23 +1674,15 @@ __global__ void __launch_bounds__(POS_TPB) pos_beam_backtrace_kernel(const int32
 // the workspace: the forced call's at S = W, then the search's own regions
 struct BWs {
     CWs c;
-    float *sum, *r, *done_score;
-    int32_t *tok, *trace, *done_at, *done_n;
+    BeamBook<int32_t> book;
     size_t floats;
 };
 
 BWs bws_layout(const XgpDims* d, int W, void* base) {
     BWs w;
     w.c = cws_layout(d, W, base);
-    const size_t B = d->B, M = B * W, L = d->T - 1;
     Carve cv{(float*)base, w.c.floats};
-    w.sum = cv.take(M);
-    w.tok = (int32_t*)cv.take(M);
-    w.trace = (int32_t*)cv.take(B * L * W * 2);
-    w.r = cv.take(B * L * W);
-    w.done_score = cv.take(M);
-    w.done_at = (int32_t*)cv.take(M * 2);
-    w.done_n = (int32_t*)cv.take(B);
+    w.book = beam_book_carve<int32_t>(cv, d->B, W, d->T - 1);
     w.floats = cv.off;
     return w;
 }
@@ -1802,19 +1714,18 @@ extern "C" int xgpb_beam_templates(void* stream, const XgpDims* d, int32_t W, in
     XG_TRY(rows_prologue(st, d, W, p, bn, feats_rgb, feats_opfl, feat_mask, w.c));
     BeamArgs a{};
     a.S = w.c.S; a.tab = w.c.v.tab; a.logit_w = p->logit_w; a.logit_b = p->logit_b; a.X = w.c.X; a.c = w.c.c;
-    a.sum = w.sum; a.tok = w.tok; a.trace = w.trace; a.r = w.r; a.trace_out = trace;
-    a.done_score = w.done_score; a.done_at = w.done_at; a.done_n = w.done_n;
-    a.R = R; a.C = C; a.L = L; a.W = W; a.suppress = suppress_tag < 0 ? -1 : suppress_tag;
+    a.book = w.book; a.book.trace_out = trace;
+    a.R = R; a.C = C; a.suppress = suppress_tag < 0 ? -1 : suppress_tag;
     const size_t lds_merge = XGPB_LDS_BYTES(W, R, C) - 1024;
     const StepPlan pl = step_plan(d, W);         // (a video's W beams are one attention group)
     for (int t = 0; t < L; ++t) {
         XG_TRY(step_front(st, d, p, pl, w.c.v, w.c.X, w.c.P, w.c.S));
-        a.t = t;
+        a.book.t = t;
         hipLaunchKernelGGL(pos_beam_merge_kernel, dim3(B), dim3(STEP_TPB), lds_merge, st, a);
         XG_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(pos_beam_backtrace_kernel, dim3(xg_cdiv(M, POS_TPB)), dim3(POS_TPB), 0, st, w.trace, w.r, w.done_score, w.done_at,
-                       templates, tag_logp, score, masks, M, W, L);
+    hipLaunchKernelGGL(pos_beam_backtrace_kernel, dim3(xg_cdiv(M, POS_TPB)), dim3(POS_TPB), 0, st, w.book, templates, tag_logp,
+                       score, masks, M);
     XG_CHECK_LAUNCH();
     hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, nullptr, masks, M, L + 1, 1, n_out);
     XG_CHECK_LAUNCH();

@@ -10,7 +10,6 @@ from __future__ import annotations
 
 import contextlib
 import os
-from unittest import mock
 
 import numpy as np
 import torch
@@ -160,9 +159,5 @@ def check_admissible(trace, r, score, seq, Pn, xn, L, W, suppress_token=1):
     """The kernel's own search, judged in float64 by tests/pos_beam_oracle.check_admissible (see there for every rule) over the
     captioner's log-probabilities along that trace.  trace (B,L,W,2), r = the returned seq_logp (B,W,L), score (B,W), seq (B,W,L)
     as numpy.  Returns the number of (video, step) pairs checked."""
-    P64 = {"logit.bias": torch.from_numpy(np.ascontiguousarray(Pn["logit.bias"])).double()}
-    fr = torch.from_numpy(np.ascontiguousarray(xn["feats_rgb"])).double()
-    along = lambda P, run, fr_, fo, fm, tr: logps_along_trace(Pn, xn, tr, torch.float64)      # noqa: E731
-    with mock.patch.object(pbo, "logps_along_trace", along):
-        return pbo.check_admissible(trace, r, score, dict(P=P64, run=None, feats=(fr, None, None), L=L, W=W,
-                                                          suppress_tag=suppress_token, templates=seq))
+    return pbo.check_admissible(trace, r, score, seq, lambda tr: logps_along_trace(Pn, xn, tr, torch.float64),
+                                C=Pn["logit.bias"].shape[0], L=L, W=W, suppress_tag=suppress_token)

@@ -164,28 +164,26 @@ def logps_along_trace(P, run, fr, fo, fm, trace):
     return torch.stack(out, 1).cpu().numpy()
 
 
-@torch.no_grad()
-def check_admissible(trace, r, score, inputs):
-    """The kernel's own search, judged in float64.  trace (B,L,W,2), r = the returned tag_logp (B,W,L), score (B,W) as numpy;
-    inputs: dict(P, run, feats=(fr, fo, fm) -- float64 tensors -- L, W, suppress_tag, templates (B,W,L)).  The states are
-    teacher-forced along the kernel's parents and tokens; at every step at which a video selects at least one candidate with
+def check_admissible(trace, r, score, templates, along, *, C, L, W, suppress_tag):
+    """The kernel's own search, judged in float64.  trace (B,L,W,2), r = the returned tag_logp (B,W,L), score (B,W), templates
+    (B,W,L) as numpy; along: a callable trace -> the float64 log-probabilities (B,L,W,C), before the -1000, of the states
+    teacher-forced along the kernel's parents and tokens (logps_along_trace here, the captioner's in tests/cap_beam_oracle.py),
+    called once the trace's indices are known to be in range.  At every step at which a video selects at least one candidate with
     p > -500, for EVERY selected slot: the token is among its parent row's `cols` largest within 3e-4, its float64 p is at least
     the W-th largest float64 p - eps_t, the selected slots descend within eps_t (eps_t = 2 (t + 1) 3e-4: two sums of t + 1
     log-probabilities, each within the bound), and no (parent, token) pair is taken twice.  Then the returned beams: each is a
     distinct completion of the trace with its tokens verbatim, every r within 3e-4 and its score within eps_t of the float64
     one; scores descend, equal scores in completion order, and no completion left out beats a returned one by more than eps.
     Returns the number of (video, step) pairs checked."""
-    P, run, (fr, fo, fm) = inputs["P"], inputs["run"], inputs["feats"]
-    L, W, sup, templates = inputs["L"], inputs["W"], inputs["suppress_tag"], np.asarray(inputs["templates"])
-    assert fr.dtype == torch.float64
-    trace, r, score = np.asarray(trace), np.asarray(r), np.asarray(score)
-    B = fr.shape[0]
+    sup, Cn = suppress_tag, C
+    trace, r, score, templates = np.asarray(trace), np.asarray(r), np.asarray(score), np.asarray(templates)
+    B = trace.shape[0]
     assert trace.shape == (B, L, W, 2) and r.shape == (B, W, L) and score.shape == (B, W) and templates.shape == (B, W, L)
-    Cn = P["logit.bias"].shape[0]
     cols = min(W, Cn)
     assert trace[..., 0].min() >= 0 and trace[..., 0].max() < Cn and trace[..., 1].min() >= 0 and trace[..., 1].max() < W
     assert (trace[:, 0, :, 1] == 0).all()                         # one row at t = 0
-    lp_all = logps_along_trace(P, run, fr, fo, fm, trace)
+    lp_all = along(trace)
+    assert lp_all.dtype == np.float64 and lp_all.shape == (B, L, W, Cn)
     sums = np.zeros((B, W))
     r64 = np.zeros((B, L, W))
     events = [[] for _ in range(B)]                               # completion order: (t, slot, float64 score)

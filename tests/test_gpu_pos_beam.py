@@ -75,7 +75,8 @@ def _f64(P, run, x):
 
 def _admissible(d, P, run, x, W, suppress, tm, lp, score, trace):
     Pt, rt, f = _f64(P, run, x)
-    return pbo.check_admissible(trace, lp, score, dict(P=Pt, run=rt, feats=f, L=d.L, W=W, suppress_tag=suppress, templates=tm))
+    return pbo.check_admissible(trace, lp, score, tm, lambda tr: pbo.logps_along_trace(Pt, rt, *f, tr),
+                                C=d.C, L=d.L, W=W, suppress_tag=suppress)
 
 
 def _shape_checks(d, W, tm, lp, score, mk, trace):
