@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nv
+from ._plumbing import FlatParams, _Holder, _stream, bn_struct, bump_bn, next_seed  # noqa: F401 (_stream: imported from here by callers)
 
 
 def make_opt(d=None, **kw):
@@ -34,10 +35,6 @@ def make_opt(d=None, **kw):
                     seq_length=d.L, feat_size=d.F1, feat_size2=d.F2, att_size=d.A)
     base.update(kw)
     return argparse.Namespace(**base)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _with_grad_event(model, run):
@@ -60,10 +57,6 @@ def _with_grad_event(model, run):
 # per model, and streams beyond the first handful share the hardware's compute pipes with the earlier ones -- see
 # train.shared_stream for what that costs.
 _AUX_HANDLES = {}
-
-
-class _Holder(nn.Module):
-    """Bare container so parameter names nest like the reference's sub-modules."""
 
 
 class _WorkspacePool:
@@ -105,7 +98,7 @@ def _ws_ptr(ws):
     return C.c_void_p(p), C.c_size_t(ws.numel() - 256)
 
 
-class SAModel(nn.Module):
+class SAModel(FlatParams, nn.Module):
     """Drop-in for reference caption_src/SAModel.py:SAModel (CaptionModel(nn.Module))."""
 
     def __init__(self, opt):
@@ -175,10 +168,6 @@ class SAModel(nn.Module):
         if getattr(opt, "fusion_activity", "ReLU") != "ReLU":
             raise ValueError("only fusion_activity='ReLU' (the shipped recipe) is implemented in HIP")
         self._pool = _WorkspacePool({"fp32": 0, "bf16": 1, "bf16x3": 3}.get(getattr(opt, "precision", "fp32"), 1))
-        self._flat = None
-        self._ps_cache = None
-        self._gs_cache = None
-        self._offsets = []
         self._call = 0
         self.dropout_seed = None        # fixed seed of the dropout hash (tests / bench parity leg: a checker can regenerate the same masks); None = a fresh seed per call
         self._packed = None          # recurrent weights in MFMA-fragment order (xg_pack_weights), refreshed lazily
@@ -198,98 +187,14 @@ class SAModel(nn.Module):
         self.logit.weight.data.uniform_(-initrange, initrange)
 
     # ------------------------------------------------------------------ plumbing
-    def _named(self):
-        return dict(self.named_parameters())
-
-    def _plist(self):
-        """The nn.Parameter objects in the C ABI's order (= state_dict order).  The objects themselves are stable for the
-        life of the module (.cuda()/.to()/load_state_dict replace their DATA), so the walk over named_parameters() is
-        done once."""
-        pl = self.__dict__.get("_plist_cache")
-        if pl is None:
-            named = self._named()
-            pl = [named[n] for n in nv.PARAM_NAMES]
-            self.__dict__["_plist_cache"] = pl
-        return pl
+    def _abi(self):
+        return nv.PARAM_NAMES, nv.XgParams
 
     def _param_list(self):
         return self._plist()
 
-    def _ensure_flat(self):
-        """All parameters live in ONE flat fp32 buffer (one RCCL all-reduce, one Adam launch);
-        the nn.Parameters are views into it.  Rebuilt if .cuda()/.to() replaced the storages."""
-        names = nv.PARAM_NAMES
-        plist = self._plist()
-        first = plist[0]
-        if self._flat is not None and self._flat.device == first.device:
-            base, ok = self._flat.data_ptr(), True
-            for p, off in zip(plist, self._offsets):
-                if p.data_ptr() != base + 4 * off:
-                    ok = False
-                    break
-            if ok:
-                return
-        if not first.is_cuda:
-            raise nv.XgError("SAModel runs on an MI355X only: call model.cuda() first (no CPU path)")
-        total = sum((p.numel() + 63) // 64 * 64 for p in plist)
-        flat = torch.zeros(total, dtype=torch.float32, device=first.device)
-        gflat = torch.zeros(total, dtype=torch.float32, device=first.device)
-        off = 0
-        self._slices = {}
-        self._offsets = []
-        for n, p in zip(names, plist):
-            if p.dtype != torch.float32:
-                raise nv.XgError("fp32 parameters only")
-            k = p.numel()
-            v = flat[off:off + k].view_as(p)
-            v.copy_(p.data)
-            had_grad = p.grad is not None
-            if had_grad:
-                gflat[off:off + k].view_as(p).copy_(p.grad)
-            p.data = v
-            p.grad = gflat[off:off + k].view_as(p) if had_grad else None
-            self._slices[n] = (off, k)
-            self._offsets.append(off)
-            off += (k + 63) // 64 * 64
-        self._flat, self._gflat = flat, gflat
-        self._ps_cache = None
-        self._gs_cache = None
-
-    def flat_parameters(self):
-        self._ensure_flat()
-        return self._flat
-
-    def flat_grads(self):
-        """Flat gradient buffer; binds every p.grad to its slice (zeroing is the caller's zero_grad)."""
-        self._ensure_flat()
-        base = self._gflat.data_ptr()
-        for p, off in zip(self._plist(), self._offsets):
-            if p.grad is None or p.grad.data_ptr() != base + 4 * off:
-                v = self._gflat[off:off + p.numel()].view_as(p)
-                if p.grad is not None:
-                    v.copy_(p.grad)
-                else:
-                    v.zero_()
-                p.grad = v
-        return self._gflat
-
-    def _params_struct(self):
-        """XgParams of the flat buffer's slices (cached until the buffer is rebuilt)."""
-        self._ensure_flat()
-        if self._ps_cache is None:
-            ps = nv.XgParams()
-            base = self._flat.data_ptr()
-            for i, off in enumerate(self._offsets):
-                setattr(ps, "p%d" % i, base + 4 * off)
-            self._ps_cache = ps
-        return self._ps_cache
-
     def _bn_struct(self):
-        e = self.two_spatial_encoder
-        s = nv.XgBnState()
-        s.rgb_mean, s.rgb_var = e.visual_emb_rgb[1].running_mean.data_ptr(), e.visual_emb_rgb[1].running_var.data_ptr()
-        s.opfl_mean, s.opfl_var = e.visual_emb_opfl[1].running_mean.data_ptr(), e.visual_emb_opfl[1].running_var.data_ptr()
-        return s
+        return bn_struct(self.two_spatial_encoder)
 
     def _dims(self, B, K, T):
         d = nv.XgDims()
@@ -409,12 +314,7 @@ class SAModel(nn.Module):
         r = nv.XgRun()
         r.train = 1 if self.training else 0
         r.drop_p = float(self.drop_prob_lm)
-        if seed is None and self.dropout_seed is not None:
-            seed = int(self.dropout_seed) & 0xFFFFFFFF
-        if seed is None:
-            self._call += 1
-            seed = (int(torch.initial_seed()) * 2654435761 + self._call * 40503) & 0xFFFFFFFF
-        r.seed = seed
+        r.seed = next_seed(self, seed)
         r.save = 1 if save else 0
         r.bn_momentum, r.bn_eps = 0.1, 1e-5
         r.gemm_mode = {"fp32": 0, "bf16": 1, "bf16x3": 3}[self.precision]
@@ -443,11 +343,7 @@ class SAModel(nn.Module):
         return b, keep
 
     def _bump_bn(self, n=1):
-        if self.training:
-            ts = [m.num_batches_tracked for m in (self.two_spatial_encoder.visual_emb_rgb[1], self.two_spatial_encoder.visual_emb_opfl[1])
-                  if m.num_batches_tracked is not None]
-            if ts:
-                torch._foreach_add_(ts, n)          # (one launch for both counters)
+        bump_bn(self.two_spatial_encoder, self.training, n)
 
     # ------------------------------------------------------------------ reference surface
     def forward(self, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask):
@@ -589,6 +485,30 @@ class SAModel(nn.Module):
         from .beam import sample_beam
         return sample_beam(self, feats, feat_masks, pos_feats, opt)
 
+    def _search_gate(self, name, *tensors):
+        """What the device searches (sample_per_video, beam_captions) require: eval mode, fp32, and `tensors` on the device.
+        Called at the head of an entry point without tensors, and with them once its own arguments have been checked."""
+        if self.training:
+            raise NotImplementedError("%s runs in eval mode only: call model.eval() first" % name)
+        if self.precision != "fp32":
+            raise NotImplementedError("%s is fp32 only (precision = %r)" % (name, self.precision))
+        for t in tensors:
+            if not t.is_cuda:
+                raise NotImplementedError("%s needs device tensors: there is no CPU path" % name)
+
+    def _search_workspace(self, attr, key, nbytes, dev, invalid):
+        """(pointer, bytes) of a device search's workspace, kept in the dict `attr` as {key: tensor} for ONE shape at a time
+        (an evaluation runs one batch shape).  `nbytes()`: the library's size for this shape; `invalid`: the error text when
+        it refuses the dims."""
+        ws = getattr(self, attr, {}).get(key)
+        if ws is None:
+            n = nbytes()
+            if n == 0:
+                raise nv.XgError(invalid)
+            ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+            setattr(self, attr, {key: ws})
+        return _ws_ptr(ws)
+
     def sample_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, opt={}):
         """``sample`` for S `pos_feats` rows per video on ONE encoder pass (include/xgate_control.h): the B videos are handed over
         once, `pos_feats` is (B,S,R), and the result is what ``sample`` gives on the batch with every video repeated S times, row by
@@ -599,10 +519,7 @@ class SAModel(nn.Module):
         (B,S,L) tensors and the device-side n).  Eval mode, fp32 and device tensors only; `beam_size` > 1 and `forced_tokens` are not
         served.  Nothing returned carries an autograd graph."""
         from . import _native_control as ncc
-        if self.training:
-            raise NotImplementedError("sample_per_video runs in eval mode only: call model.eval() first")
-        if self.precision != "fp32":
-            raise NotImplementedError("sample_per_video is fp32 only (precision = %r)" % (self.precision,))
+        self._search_gate("sample_per_video")
         if opt.get("beam_size", 1) > 1:
             raise NotImplementedError("sample_per_video has no beam search: beam_size must be 1")
         if opt.get("forced_tokens", None) is not None:
@@ -610,9 +527,7 @@ class SAModel(nn.Module):
         B, K = feats_rgb.shape[0], feats_rgb.shape[1]
         if pos_feats.dim() != 3 or pos_feats.shape[0] != B or pos_feats.shape[1] < 1 or pos_feats.shape[2] != self.rnn_size:
             raise ValueError("pos_feats (B = %d, S, R = %d) expected, got %s" % (B, self.rnn_size, tuple(pos_feats.shape)))
-        for t in (feats_rgb, feats_opfl, feat_mask, pos_feats):
-            if not t.is_cuda:
-                raise NotImplementedError("sample_per_video needs device tensors: there is no CPU path")
+        self._search_gate("sample_per_video", feats_rgb, feats_opfl, feat_mask, pos_feats)
         S, L = int(pos_feats.shape[1]), self.seq_length
         M = B * S
         dev = feats_rgb.device
@@ -629,15 +544,8 @@ class SAModel(nn.Module):
             uniforms = None
         lib = ncc.lib()
         d = self._dims(B, K, L + 1)
-        key = (B, K, L, S, str(dev))
-        ws = getattr(self, "_control_ws", {}).get(key)
-        if ws is None:
-            n = lib.xgcc_workspace_bytes(C.byref(d), S)
-            if n == 0:
-                raise nv.XgError("xgcc_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S))
-            ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
-            self._control_ws = {key: ws}                # (one shape at a time, as beam_captions keeps its workspace)
-        wp, wn = _ws_ptr(ws)
+        wp, wn = self._search_workspace("_control_ws", (B, K, L, S, str(dev)), lambda: lib.xgcc_workspace_bytes(C.byref(d), S), dev,
+                                        "xgcc_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S))
         with torch.no_grad():
             b, keep = self._batch(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(M, self.rnn_size))
             ps, bn, run = self._params_struct(), self._bn_struct(), self._run(False)
@@ -661,32 +569,20 @@ class SAModel(nn.Module):
         merge (the reference does this for UNK, index 1); -1 turns it off.  `return_trace`: also the (token, parent slot) of every
         slot and step.  Eval mode, fp32 and device tensors only; beam_size may not exceed vocab_size or 8."""
         from . import _native_beam as nb
-        if self.training:
-            raise NotImplementedError("beam_captions runs in eval mode only: call model.eval() first")
-        if self.precision != "fp32":
-            raise NotImplementedError("beam_captions is fp32 only (precision = %r)" % (self.precision,))
+        self._search_gate("beam_captions")
         W, sup = int(beam_size), int(suppress_token)
         if W < 1 or W > self.vocab_size or W > nb.XGCB_MAX_BEAM:
             raise ValueError("1 <= beam_size <= min(vocab_size = %d, %d) expected, got %d" % (self.vocab_size, nb.XGCB_MAX_BEAM, W))
         if sup >= self.vocab_size:
             raise ValueError("suppress_token must lie below vocab_size = %d (-1: none), got %d" % (self.vocab_size, sup))
-        for t in (feats_rgb, feats_opfl, feat_mask, pos_feats):
-            if not t.is_cuda:
-                raise NotImplementedError("beam_captions needs device tensors: there is no CPU path")
+        self._search_gate("beam_captions", feats_rgb, feats_opfl, feat_mask, pos_feats)
         B, K = feats_rgb.shape[0], feats_rgb.shape[1]
         L = self.seq_length
         dev = feats_rgb.device
         lib = nb.lib()
         d = self._dims(B, K, L + 1)
-        key = (B, K, L, W, str(dev))
-        ws = getattr(self, "_beam_ws", {}).get(key)
-        if ws is None:
-            n = lib.xgcb_workspace_bytes(C.byref(d), W)
-            if n == 0:
-                raise nv.XgError("xgcb_workspace_bytes: invalid dims or too many rows (B %d, W %d)" % (B, W))
-            ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
-            self._beam_ws = {key: ws}                   # (one shape at a time: an evaluation runs one batch shape)
-        wp, wn = _ws_ptr(ws)
+        wp, wn = self._search_workspace("_beam_ws", (B, K, L, W, str(dev)), lambda: lib.xgcb_workspace_bytes(C.byref(d), W), dev,
+                                        "xgcb_workspace_bytes: invalid dims or too many rows (B %d, W %d)" % (B, W))
         b, keep = self._batch(feats_rgb, feats_opfl, feat_mask, pos_feats)
         ps, bn, run = self._params_struct(), self._bn_struct(), self._run(False)
         seq = torch.empty(B, W, L, dtype=torch.int64, device=dev)
@@ -700,40 +596,47 @@ class SAModel(nn.Module):
 
 
 # ====================================================================== autograd glue
-def _grads_bound(model):
-    base = model._gflat.data_ptr()
-    for p, off in zip(model._plist(), model._offsets):
-        g = p.grad
-        if g is None or g.data_ptr() != base + 4 * off:
-            return False
-    return True
+def _grads_struct(model, device=None):
+    """model._grads_struct() under the name callers outside this module import: (g, struct of gradient pointers)."""
+    return model._grads_struct()
 
 
-def _grads_struct(model, device):
-    """XgParams struct of gradient pointers (the C ABI accumulates into them).  If every p.grad is
-    already bound to the model's flat gradient buffer (model.flat_grads()), accumulate there directly
-    and hand autograd nothing; otherwise use a fresh zero buffer and return views for autograd."""
-    model._ensure_flat()
-    model._grad_writes = getattr(model, "_grad_writes", 0) + 1     # a backward is about to add to the gradient buffer
-    if _grads_bound(model):
-        if model._gs_cache is None:
-            s = nv.XgParams()
-            base = model._gflat.data_ptr()
-            for i, off in enumerate(model._offsets):
-                setattr(s, "p%d" % i, base + 4 * off)
-            model._gs_cache = s
-        return None, model._gs_cache
-    g = torch.zeros_like(model._flat)
-    s = nv.XgParams()
-    for i, off in enumerate(model._offsets):
-        setattr(s, "p%d" % i, g.data_ptr() + 4 * off)
-    return g, s
+def _take_workspace(model, d, dev, save):
+    """(ws, pointer, bytes) of a forward's workspace: its own until the backward has run when it saves activations,
+    else the shared scratch."""
+    ws = model._pool.take(d, dev) if save else model._pool.shared(d, dev)
+    return (ws,) + _ws_ptr(ws)
 
 
-def _grad_views(model, g):
-    if g is None:
-        return [None] * len(nv.PARAM_NAMES)
-    return [g[off:off + p.numel()].view_as(p) for p, off in zip(model._plist(), model._offsets)]
+def _open_backward(ctx):
+    """What every backward hands the library, from what its forward left in ctx (model, d, keep, ws, run):
+    (model, d, g, gs, b, keep, wp, wn, ps, run) -- g / gs of _grads_struct, run with the gradient event."""
+    model = ctx.model
+    g, gs = model._grads_struct()
+    b, keep = model._batch(*ctx.keep)
+    wp, wn = _ws_ptr(ctx.ws)
+    return model, ctx.d, g, gs, b, keep, wp, wn, model._params_struct(), _with_grad_event(model, ctx.run)
+
+
+def _close_backward(ctx, g, k):
+    """Give the forward's workspace back and return backward's result: None for the k non-parameter inputs, then the
+    parameters' gradient views (None each when the library added into the bound gradient buffer)."""
+    ctx.model._pool.give(ctx.d, ctx.keep[0].device, ctx.ws)
+    ctx.ws = None
+    return (None,) * k + tuple(ctx.model._grad_views(g))
+
+
+def _rollout_backward(ctx, dslp, k):
+    """xg_rollout_bwd of the sampled rollout whose activations ctx.ws holds: backward of both rollout functions (k: the
+    number of their non-parameter inputs)."""
+    if not ctx.need_grad:
+        raise nv.XgError("rollout ran without saved activations")
+    model, d, g, gs, b, keep, wp, wn, ps, run = _open_backward(ctx)
+    full = torch.zeros(d.B, d.T - 1, dtype=torch.float32, device=keep[0].device)
+    full[:, :dslp.shape[1]] = dslp
+    nv.check(nv.lib().xg_rollout_bwd(_stream(), C.byref(d), C.byref(ps), C.byref(gs), C.byref(b), C.byref(run),
+                                     wp, wn, nv.ptr(full)), "xg_rollout_bwd")
+    return _close_backward(ctx, g, k)
 
 
 class _XEFunction(torch.autograd.Function):
@@ -743,8 +646,7 @@ class _XEFunction(torch.autograd.Function):
         T = seq.shape[1]
         dev = feats_rgb.device
         d = model._dims(B, K, T)
-        ws = model._pool.take(d, dev) if save else model._pool.shared(d, dev)
-        wp, wn = _ws_ptr(ws)
+        ws, wp, wn = _take_workspace(model, d, dev, save)
         b, keep = model._batch(feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask)
         logp = torch.empty(B, T, model.vocab_size, dtype=torch.float32, device=dev)
         cat = torch.empty(B, T, model.category_size, dtype=torch.float32, device=dev)
@@ -762,23 +664,15 @@ class _XEFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogp, dcat):
-        model, d = ctx.model, ctx.d
         if not ctx.saved_ws:
             raise nv.XgError("backward without saved activations")
-        dev = ctx.keep[0].device
-        g, gs = _grads_struct(model, dev)
-        b, keep = model._batch(*ctx.keep)
-        wp, wn = _ws_ptr(ctx.ws)
-        ps = model._params_struct()
+        model, d, g, gs, b, keep, wp, wn, ps, run = _open_backward(ctx)
         dl = None if dlogp is None else dlogp.contiguous().float()
         dc = None if dcat is None else dcat.contiguous().float()
         fn = nv.lib().xg_backward_ss if ctx.ss else nv.lib().xg_backward_xe
-        run = _with_grad_event(model, ctx.run)
         nv.check(fn(_stream(), C.byref(d), C.byref(ps), C.byref(gs), C.byref(b), C.byref(run),
                     wp, wn, nv.ptr(dl), nv.ptr(dc)), "xg_backward_ss" if ctx.ss else "xg_backward_xe")
-        model._pool.give(d, dev, ctx.ws)
-        ctx.ws = None
-        return (None,) * 9 + tuple(_grad_views(model, g))
+        return _close_backward(ctx, g, 9)
 
 
 class _XELossFunction(torch.autograd.Function):
@@ -789,8 +683,7 @@ class _XELossFunction(torch.autograd.Function):
         T = seq.shape[1]
         dev = feats_rgb.device
         d = model._dims(B, K, T)
-        ws = model._pool.take(d, dev) if save else model._pool.shared(d, dev)
-        wp, wn = _ws_ptr(ws)
+        ws, wp, wn = _take_workspace(model, d, dev, save)
         b, keep = model._batch(feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask)
         cc = None if cap_classes is None else cap_classes.detach().contiguous().long()
         cm = None if class_mask is None else class_mask.detach().contiguous().float()
@@ -812,19 +705,11 @@ class _XELossFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss):
-        model, d = ctx.model, ctx.d
-        dev = ctx.keep[0].device
-        g, gs = _grads_struct(model, dev)
-        b, keep = model._batch(*ctx.keep)
-        wp, wn = _ws_ptr(ctx.ws)
-        ps = model._params_struct()
-        dl = dloss.detach().contiguous().float().to(dev)
-        run = _with_grad_event(model, ctx.run)
+        model, d, g, gs, b, keep, wp, wn, ps, run = _open_backward(ctx)
+        dl = dloss.detach().contiguous().float().to(keep[0].device)
         nv.check(nv.lib().xg_xe_loss_bwd(_stream(), C.byref(d), C.byref(ps), C.byref(gs), C.byref(b), nv.ptr(ctx.cc),
                                          nv.ptr(ctx.cm), ctx.wc, nv.ptr(dl), C.byref(run), wp, wn), "xg_xe_loss_bwd")
-        model._pool.give(d, dev, ctx.ws)
-        ctx.ws = None
-        return (None,) * 11 + tuple(_grad_views(model, g))
+        return _close_backward(ctx, g, 11)
 
 
 class _RolloutFunction(torch.autograd.Function):
@@ -835,8 +720,7 @@ class _RolloutFunction(torch.autograd.Function):
         T = model.seq_length + 1
         dev = feats_rgb.device
         d = model._dims(B, K, T)
-        ws = model._pool.take(d, dev) if need_grad else model._pool.shared(d, dev)
-        wp, wn = _ws_ptr(ws)
+        ws, wp, wn = _take_workspace(model, d, dev, need_grad)
         b, keep = model._batch(feats_rgb, feats_opfl, feat_mask, pos_feats)
         seq = torch.zeros(B, T - 1, dtype=torch.int64, device=dev)
         slp = torch.zeros(B, T - 1, dtype=torch.float32, device=dev)
@@ -865,23 +749,7 @@ class _RolloutFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dseq, dslp, dn):
-        model, d = ctx.model, ctx.d
-        if not ctx.need_grad:
-            raise nv.XgError("rollout ran without saved activations")
-        dev = ctx.keep[0].device
-        g, gs = _grads_struct(model, dev)
-        b, keep = model._batch(*ctx.keep)
-        wp, wn = _ws_ptr(ctx.ws)
-        ps = model._params_struct()
-        T = d.T
-        full = torch.zeros(d.B, T - 1, dtype=torch.float32, device=dev)
-        full[:, :dslp.shape[1]] = dslp
-        run = _with_grad_event(model, ctx.run)
-        nv.check(nv.lib().xg_rollout_bwd(_stream(), C.byref(d), C.byref(ps), C.byref(gs), C.byref(b), C.byref(run),
-                                         wp, wn, nv.ptr(full)), "xg_rollout_bwd")
-        model._pool.give(d, dev, ctx.ws)
-        ctx.ws = None
-        return (None,) * 11 + tuple(_grad_views(model, g))
+        return _rollout_backward(ctx, dslp, 11)
 
 
 class _RolloutPairFunction(torch.autograd.Function):
@@ -911,8 +779,7 @@ class _RolloutPairFunction(torch.autograd.Function):
         ps, bn, run = model._params_struct(), model._bn_struct(), model._run(need_grad)
         # rollout + compaction of the sampled half into the m-row workspace (what the backward reads) as one call: the encoder
         # runs there in the first place, and the sampled rows' logits are written there by the rollout itself
-        ws1 = model._pool.take(d1, dev) if need_grad else model._pool.shared(d1, dev)
-        wp1, wn1 = _ws_ptr(ws1)
+        ws1, wp1, wn1 = _take_workspace(model, d1, dev, need_grad)
         nv.check(nv.lib().xg_rollout_pair_videos(_stream(), C.byref(d2), C.byref(ps), C.byref(bn), C.byref(b1), C.byref(run),
                                                  nv.ptr(uniforms), temperature, wp2, wn2, C.byref(d1), wp1, wn1, 1 if need_grad else 0,
                                                  nv.ptr(seq), nv.ptr(slp), nv.ptr(n)), "xg_rollout_pair_videos")
@@ -930,22 +797,7 @@ class _RolloutPairFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dgen, dslp, dgreedy, dn):
-        model, d = ctx.model, ctx.d
-        if not ctx.need_grad:
-            raise nv.XgError("rollout ran without saved activations")
-        dev = ctx.keep[0].device
-        g, gs = _grads_struct(model, dev)
-        b, keep = model._batch(*ctx.keep)
-        wp, wn = _ws_ptr(ctx.ws)
-        ps = model._params_struct()
-        full = torch.zeros(d.B, d.T - 1, dtype=torch.float32, device=dev)
-        full[:, :dslp.shape[1]] = dslp
-        run = _with_grad_event(model, ctx.run)
-        nv.check(nv.lib().xg_rollout_bwd(_stream(), C.byref(d), C.byref(ps), C.byref(gs), C.byref(b), C.byref(run),
-                                         wp, wn, nv.ptr(full)), "xg_rollout_bwd")
-        model._pool.give(d, dev, ctx.ws)
-        ctx.ws = None
-        return (None,) * 8 + tuple(_grad_views(model, g))
+        return _rollout_backward(ctx, dslp, 8)
 
 
 # ====================================================================== criteria

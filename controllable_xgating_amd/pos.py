@@ -23,17 +23,10 @@ import torch.nn as nn
 from . import _native as nv
 from . import _native_pos as npos
 from . import _native_pos_train as npt
+from ._plumbing import FlatParams, _Holder, _stream, bn_struct, bump_bn, next_seed
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class _Holder(nn.Module):
-    """Bare container so parameter names nest like the reference's sub-modules."""
-
-
-class PosModel(nn.Module):
+class PosModel(FlatParams, nn.Module):
     """reference pos_src/SAModel.py:13-184 (eval-mode inference)."""
 
     def __init__(self, opt):
@@ -76,8 +69,6 @@ class PosModel(nn.Module):
         self._cws = None                # workspace of sample_forced / sample_templates / beam_templates (grows to the largest call)
         self._tws = None                # training workspace: the saved activations of the last train-mode forward
         self._train_gen = 0             # bumped by every train-mode forward: a backward of an older one must not read them
-        self._flat = self._gflat = None
-        self._offsets = None
         self._call = 0
         self.dropout_seed = None        # fixed seed of the dropout hash (tests: a checker regenerates the masks); None = fresh per call
         self.ss_prob = 0.0              # accepted and ignored: both branches of SAModel.py:76-79 feed the ground truth
@@ -97,98 +88,28 @@ class PosModel(nn.Module):
             if not p.is_cuda or p.dtype != torch.float32:
                 raise nv.XgError("PosModel parameters must be fp32 on the GPU (model.cuda())")
 
-    def _plist(self):
-        named = dict(self.named_parameters())
+    def _abi(self):
         npos.lib()
-        return [named[n] for n in npos.PARAM_NAMES]
+        return npos.PARAM_NAMES, npos.XgpParams
 
-    def _ensure_flat(self):
-        """All parameters live in ONE flat fp32 buffer (one Adam launch); the nn.Parameters are views into it.  Rebuilt when
-        .cuda() / .to() replaced the storages."""
-        plist = self._plist()
-        if self._flat is not None and self._flat.device == plist[0].device:
-            base = self._flat.data_ptr()
-            if all(p.data_ptr() == base + 4 * off for p, off in zip(plist, self._offsets)):
-                return
-        if not plist[0].is_cuda:
+    def _refuse_host_params(self, first):
+        if not first.is_cuda:
             raise nv.XgError("PosModel trains on the GPU only: call model.cuda() first (no CPU path)")
-        total = sum((p.numel() + 63) // 64 * 64 for p in plist)
-        flat = torch.zeros(total, dtype=torch.float32, device=plist[0].device)
-        gflat = torch.zeros_like(flat)
-        off, offsets = 0, []
-        for p in plist:
-            if p.dtype != torch.float32:
-                raise nv.XgError("fp32 parameters only")
-            k = p.numel()
-            v = flat[off:off + k].view_as(p)
-            v.copy_(p.data)
-            had_grad = p.grad is not None
-            if had_grad:
-                gflat[off:off + k].view_as(p).copy_(p.grad)
-            p.data = v
-            p.grad = gflat[off:off + k].view_as(p) if had_grad else None
-            offsets.append(off)
-            off += (k + 63) // 64 * 64
-        self._flat, self._gflat, self._offsets = flat, gflat, offsets
-
-    def flat_parameters(self):
-        self._ensure_flat()
-        return self._flat
-
-    def flat_grads(self):
-        """Flat gradient buffer; binds every p.grad to its slice (zeroing is the caller's zero_grad)."""
-        self._ensure_flat()
-        base = self._gflat.data_ptr()
-        for p, off in zip(self._plist(), self._offsets):
-            if p.grad is None or p.grad.data_ptr() != base + 4 * off:
-                v = self._gflat[off:off + p.numel()].view_as(p)
-                if p.grad is not None:
-                    v.copy_(p.grad)
-                else:
-                    v.zero_()
-                p.grad = v
-        return self._gflat
 
     def mark_params_changed(self, **kw):
         """train.ClipAdam's notice that a kernel rewrote the flat buffer.  Nothing to do: every call reads the parameters afresh
         (the decoder's packed tiles are rebuilt per call)."""
 
-    def _grads_struct(self):
-        """XgpParams of gradient pointers (the library ADDS into them): the flat gradient buffer when every p.grad is bound to
-        it (flat_grads()), else a fresh zero buffer whose views autograd then accumulates."""
-        self._ensure_flat()
-        self._grad_writes = getattr(self, "_grad_writes", 0) + 1
-        plist = self._plist()
-        base = self._gflat.data_ptr()
-        if all(p.grad is not None and p.grad.data_ptr() == base + 4 * off for p, off in zip(plist, self._offsets)):
-            g = None
-            base_g = base
-        else:
-            g = torch.zeros_like(self._flat)
-            base_g = g.data_ptr()
-        s = npos.XgpParams(*[base_g + 4 * off for off in self._offsets])
-        views = [None] * len(plist) if g is None else [g[off:off + p.numel()].view_as(p) for p, off in zip(plist, self._offsets)]
-        return s, views
-
     def _run(self):
         r = npt.XgptRun()
         r.train = 1 if self.training else 0
         r.drop_p = float(self.drop_prob_lm or 0.0)
-        if self.dropout_seed is not None:
-            seed = int(self.dropout_seed)
-        else:
-            self._call += 1
-            seed = int(torch.initial_seed()) * 2654435761 + self._call * 40503
-        r.seed = seed & 0xFFFFFFFF
+        r.seed = next_seed(self)
         r.bn_momentum = 0.1
         return r
 
     def _bump_bn(self, n=1):
-        if self.training:
-            e = self.two_fc_encoder
-            ts = [m.num_batches_tracked for m in (e.visual_emb_rgb[1], e.visual_emb_opfl[1]) if m.num_batches_tracked is not None]
-            if ts:
-                torch._foreach_add_(ts, n)
+        bump_bn(self.two_fc_encoder, self.training, n)
 
     def _train_workspace(self, dims, device):
         n = npt.lib().xgpt_workspace_bytes(C.byref(dims))
@@ -206,9 +127,7 @@ class PosModel(nn.Module):
         return npos.XgpParams(*[p.data_ptr() for p in plist])
 
     def _bn(self):
-        e = self.two_fc_encoder
-        return nv.XgBnState(e.visual_emb_rgb[1].running_mean.data_ptr(), e.visual_emb_rgb[1].running_var.data_ptr(),
-                            e.visual_emb_opfl[1].running_mean.data_ptr(), e.visual_emb_opfl[1].running_var.data_ptr())
+        return bn_struct(self.two_fc_encoder)
 
     def _dims(self, B, K, T):
         return npos.XgpDims(B, K, self.rnn_size, self.att_size, self.input_encoding_size, self.category_size, self.feat_size,
@@ -489,13 +408,13 @@ class _PosTrainFunction(torch.autograd.Function):
                              "(call backward before the next forward)")
         fr, fo, fm = ctx.keep
         ws = model._tws
-        gs, views = model._grads_struct()
+        g, gs = model._grads_struct()
         dl = dlogp.detach().float().contiguous()
         run = ctx.run
         nv.check(npt.lib().xgpt_backward(_stream(), C.byref(ctx.dims), C.byref(model._params()), C.byref(gs), C.byref(run),
                                          fr.data_ptr(), fo.data_ptr(), fm.data_ptr(), ctx.Tp, dl.data_ptr(), ws.data_ptr(),
                                          ws.numel()), "xgpt_backward")
-        return (None,) * 6 + tuple(views)
+        return (None,) * 6 + tuple(model._grad_views(g))
 
 
 class ClassiferCriterion(nn.Module):

@@ -123,6 +123,21 @@ def test_two_identical_calls_are_bit_identical():
     assert a["loss"] == b["loss"]
 
 
+def test_inference_only_model_is_never_flattened():
+    """An eval-mode PosModel reads every parameter through its own pointer: forward, sample and sample_forced allocate no flat
+    or gradient buffer and rebind no parameter."""
+    d = po.make_dims(**po.POS_CFG["tiny"])
+    P, run, x = po.make_params(d), po.make_running(d), po.make_inputs(d, seed=3, ragged=True)
+    m = pos_model(d, P, run)
+    ptrs = [p.data_ptr() for p in m.parameters()]
+    h = run_model(m, x)                                          # forward and sample
+    tag_logp, _, _, pos_feats = m.sample_forced(*cuda_inputs(x), [[[2, 4, 1], [3]]] * d.B)
+    torch.cuda.synchronize()
+    assert np.isfinite(h["tf_logp"]).all() and torch.isfinite(tag_logp).all() and torch.isfinite(pos_feats).all()
+    assert [p.data_ptr() for p in m.parameters()] == ptrs
+    assert m._flat is None and m._gflat is None and all(p.grad is None for p in m.parameters())
+
+
 def test_extraction_feeds_the_captioner_end_to_end():
     """extract_pos_features over two batches into a dict -> data.make_video_item picks each video's last state row -> the
     captioner's greedy SAModel.sample on those vectors, against the oracle chain (pos_oracle -> oracle.xgate_oracle)."""
