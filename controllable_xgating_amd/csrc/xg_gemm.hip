@@ -864,7 +864,6 @@ int launch_pk(hipStream_t st, const GemmArgs& a, long min_units_default) {
     // (vocabulary head: logits, dW_logit, dH) and loses 10-15 % to 64x64 tiles + split-K on the mid-size products
     static const long min_units_env = xg_diag_env("XG_PK_MIN") ? atol(xg_diag_env("XG_PK_MIN")) : -1;
     const long min_units = min_units_env >= 0 ? min_units_env : min_units_default;      // (XG_PK_MIN: tests force the kernel onto small shapes)
-    if (units < 512L * min_units) return 1;
     // 2 workgroups per CU (73.7 KB of LDS each) -- or, for a background product, ONE per CU (LDS padded past half a CU so
     // that the dispatcher cannot pair them): 512 persistent workgroups own every register file and LDS for the whole
     // product (0.7 ms for dW_logit), and a recurrent chain on another stream then waits for leftovers -- its step took
@@ -874,6 +873,12 @@ int launch_pk(hipStream_t st, const GemmArgs& a, long min_units_default) {
     static const int bg_all = xg_diag_env("XG_GEMM_FORCE_BG") ? 1 : 0;     // tests: every product takes the background form
     const bool bg = (a.bg + bg_all > 0) && !bg_off;
     const int GMAX = bg ? 256 : 512;
+    // A background product is here for the chain beside it, not for its own speed: every other kernel of this file fills whole
+    // CUs and stops that chain.  Its floor is what the one-workgroup-per-CU grid needs -- one share of 4 slabs for each of the 256
+    // workgroups -- so that a chunk of two or three decoder steps' logits (256 x 20000 x 512: 314 tiles, one round + 58) still
+    // runs in this form, and so does a product of fewer than 256 tiles (rounds == 0: stream-K shares only).  Everything else
+    // keeps the measured floor above.
+    if (units < (bg && min_units_env < 0 ? 256L * 4 : 512L * min_units)) return 1;
     int G;
     const bool split = !a.relu && g.nslab >= 2;
     if (!split) {

@@ -836,9 +836,10 @@ int decoder_tokens_xe(hipStream_t sx, const XgDims& d, const XgParams& p, const 
     return XG_OK;
 }
 
-// teacher-forced decoder, states into w.H1/C1/H2/C2 (SAModel.py:85-112).  The vocabulary product of the first half of
-// the steps is issued on the auxiliary stream as soon as those steps are done; *logit_rows_done receives the number of
-// (t,b) rows whose logits are already under way there.
+// teacher-forced decoder, states into w.H1/C1/H2/C2 (SAModel.py:85-112).  The vocabulary product of the earlier steps
+// is issued on the auxiliary stream as soon as those steps are done (fp32: in chunks of a few steps, see below; bf16 modes:
+// the first half of the steps as one product); *logit_rows_done receives the number of (t,b) rows whose logits are
+// already under way there.
 // early_loss (fused loss path): the cross-entropy rows of those steps follow their logits on the auxiliary stream, under
 // the remaining steps (w.sums must have been zeroed on the main stream before).
 int decoder_fwd_xe(Streams& ss, const XgDims& d, const XgParams& p, const XgBatch& x, const XgRun& run, Ws& w,
@@ -853,20 +854,42 @@ int decoder_fwd_xe(Streams& ss, const XgDims& d, const XgParams& p, const XgBatc
     // ... as a background product, with the stand-alone attention in its half-CU form beside it: the 128-VGPR attention
     // needs an EMPTY CU and waited for the whole persistent product (255 us: the chain simply stopped).  6.16 -> 6.10 ms.
     const bool fwd_bg = th > 0 && w.gm == 0;
+    // The background form follows the loop in chunks: behind every `chunk`-th step the rows of the steps finished since the last
+    // chunk go to the auxiliary stream (one fork, behind the step's last launch), so that only the last `tail` steps' rows are
+    // left for the section behind the loop, where nothing runs beside them.  The last chunk ends `tail` steps before the loop
+    // does and is at least two steps long (T = 21: steps 3, 6, 9, 12, 15 and 19).  The bf16 modes keep the single split at T / 2
+    // (their rounding rule is per product: DESIGN.md 4.2), and so does a run without side streams (th == 0: no split at all).
+    // A step beside the background product takes about twice its time alone (64 against 31-35 us), so the loop pays for most of
+    // what the section behind it saves: 5.29 -> 5.23 ms for the schedule (docs/EXPERIMENTS.md, round 7: 3,2 and 2,2 level,
+    // 4,2 / 6,2 / 9,2 / 3,1 / 3,3 behind them).
+    static const char* chunk_env = xg_diag_env("XG_LOGIT_CHUNK");      // diagnosis: "<steps per chunk>,<tail steps>"; "0,0" = one split at T / 2
+    int chunk = 3, tail = 2;
+    if (chunk_env) sscanf(chunk_env, "%d,%d", &chunk, &tail);
+    const bool chunked = fwd_bg && chunk > 0 && tail > 0;
+    const int last_cut = chunked ? T - tail : th;                      // no rows go to the auxiliary stream behind this step count
+    int done = 0;                                                      // steps whose rows are under way on the auxiliary stream
     *logit_rows_done = 0;
     XG_TRY(record_prof(run.prof_event0, st));
     for (int t = 0; t < T; ++t) {
         StepIO s = step_io_at(w, d, t);
         s.pre1 = w.PRE1 + (size_t)t * B * 4 * R; s.mask = x.seq_mask + t; s.ldm = T; s.half_attn = fwd_bg;
         XG_TRY(core_step(st, d, p, run, w, w.Venc, w.vproj, s));
-        if (th > 0 && t == th - 1) {
+        const int n = t + 1;                                           // steps finished
+        bool cut;
+        if (!chunked) cut = th > 0 && n == th;
+        else if (n < last_cut) cut = n % chunk == 0 && last_cut - n >= 2;      // (a chunk that would leave the last one a single step joins it)
+        else cut = n == last_cut && n - done >= 2;
+        if (cut) {
+            const int rows = (n - done) * B, row0 = done * B;
+            const float* Hc = w.H2 + BR + (size_t)row0 * R;
             XG_TRY(ss.fork());
-            XG_TRY(cvt16(ss.aux, w, w.H2 + BR, (size_t)th * B * R));
-            XG_TRY(lin16(ss.aux, w.gm | (fwd_bg ? XGK_GEMM_BG : 0), th * B, d.V, R, w.H2 + BR, m16(w, w.H2 + BR), R, p.logit_w,
-                         w16(w, W16_LOGIT), p.logit_b, w.LOGITS, d.V));
-            *logit_rows_done = th * B;
+            XG_TRY(cvt16(ss.aux, w, Hc, (size_t)rows * R));
+            XG_TRY(lin16(ss.aux, w.gm | (fwd_bg ? XGK_GEMM_BG : 0), rows, d.V, R, Hc, m16(w, Hc), R, p.logit_w,
+                         w16(w, W16_LOGIT), p.logit_b, w.LOGITS + (size_t)row0 * d.V, d.V));
             if (early_loss)
-                XG_TRY(xgk_xent_fwd(ss.aux, w.LOGITS, d.V, x.seq, x.seq_mask, nullptr, B, T, d.V, 1, w.LSE, w.sums, 0, th * B, false));
+                XG_TRY(xgk_xent_fwd(ss.aux, w.LOGITS, d.V, x.seq, x.seq_mask, nullptr, B, T, d.V, 1, w.LSE, w.sums, row0, rows, false));
+            done = n;
+            *logit_rows_done = done * B;
         }
     }
     return record_prof(run.prof_event1, st);
@@ -881,15 +904,16 @@ int classifier_fwd(hipStream_t st, const XgDims& d, const XgParams& p, const XgR
 }
 
 // classifier hidden + logits for the stacked outputs H2[1..T] (SAModel.py:109-110)
-int heads_fwd_logits(Streams& ss, const XgDims& d, const XgParams& p, const XgRun& run, Ws& w, int rows, int rows_done) {
+// cls == false: nobody reads the classifier head in this call (fused loss path without class targets; its backward skips the head too)
+int heads_fwd_logits(Streams& ss, const XgDims& d, const XgParams& p, const XgRun& run, Ws& w, int rows, int rows_done, bool cls = true) {
     hipStream_t st = ss.main;
     const int R = d.R;
     const float* Hlate = w.H2 + (size_t)d.B * R + (size_t)rows_done * R;       // the rows whose logits are not under way yet
     XG_TRY(cvt16(st, w, Hlate, (size_t)(rows - rows_done) * R));
     XG_TRY(lin16(st, w.gm, rows - rows_done, d.V, R, Hlate, m16(w, Hlate), R, p.logit_w, w16(w, W16_LOGIT), p.logit_b,
                  w.LOGITS + (size_t)rows_done * d.V, d.V));
-    XG_TRY(classifier_fwd(st, d, p, run, w, rows));
-    return ss.join();                         // first-half logits from the auxiliary stream
+    if (cls) XG_TRY(classifier_fwd(st, d, p, run, w, rows));
+    return ss.join();                         // the earlier steps' logits from the auxiliary stream
 }
 
 // Shared reverse-time pass.  On entry: DH2OUT (TB,R) holds d(loss)/d(h2'_t) from the heads.
@@ -1215,12 +1239,12 @@ int open_ws(const XgDims* d, void* ws, size_t ws_bytes, const XgRun* run, Ws* w)
 // teacher-forced forward up to the logits (time-major, w.LOGITS) and the classifier head (w.CL); *rows_done: the (t,b) rows whose
 // logits (early_loss: and cross-entropy) ran on the auxiliary stream under the remaining steps
 int forward_xe_front(Streams& ss, const XgDims& d, const XgParams& p, const XgBnState* bn, const XgBatch& x, const XgRun& run, Ws& w,
-                     bool early_loss, int* rows_done) {
+                     bool early_loss, int* rows_done, bool cls = true) {
     XG_TRY(ss.fork());
     XG_TRY(decoder_tokens_xe(ss.aux, d, p, x, run, w));
     XG_TRY(encoder_fwd(ss.main, d, p, bn, x, run, w, &ss));
     XG_TRY(decoder_fwd_xe(ss, d, p, x, run, w, rows_done, early_loss));
-    return heads_fwd_logits(ss, d, p, run, w, d.T * d.B, *rows_done);       // (joins the auxiliary stream)
+    return heads_fwd_logits(ss, d, p, run, w, d.T * d.B, *rows_done, cls);  // (joins the auxiliary stream)
 }
 
 // dlogits (in place, w.LOGITS) and dcl (w.DCL) from the gradients of the two log-prob outputs.  have_logp: LOGITS already holds
@@ -1624,7 +1648,10 @@ extern "C" int xg_xe_loss_fwd(void* stream, const XgDims* d, const XgParams* p, 
     Streams ss(st, run);
     int rows_done = 0;
     ZERO(st, w.sums, 2);                       // both halves of the cross-entropy add into it
-    XG_TRY(forward_xe_front(ss, *d, *p, bn, *x, *run, w, true, &rows_done));
+    // without class targets the classifier head (two products and a gate pass between the late logits and the loss) is read by
+    // nobody: xg_xe_loss_bwd skips its backward as well
+    static const bool keep_cls = xg_diag_env("XG_KEEP_CLS") != nullptr;      // diagnosis: run it regardless
+    XG_TRY(forward_xe_front(ss, *d, *p, bn, *x, *run, w, true, &rows_done, cap_classes != nullptr || keep_cls));
     XG_TRY(xgk_xent_fwd(st, w.LOGITS, d->V, x->seq, x->seq_mask, nullptr, d->B, d->T, d->V, 1, w.LSE, w.sums, rows_done, -1, false));
     if (cap_classes) {
         XG_TRY(xgk_xent_fwd(st, w.CL, d->C, cap_classes, x->seq_mask, class_mask, d->B, d->T, d->C, 0, w.LSEC, w.sums + 2));

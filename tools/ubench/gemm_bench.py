@@ -17,6 +17,11 @@ SHAPES = [  # name, ta, tb, M, N, K, acc
     ("dH NN 1920x512 K=20000", 0, 0, 1920, 512, 20000, 0),
     ("dH half NN 1408x512 K=20000", 0, 0, 1408, 512, 20000, 0),
     ("dH half NN 1280x512 K=20000", 0, 0, 1280, 512, 20000, 0),
+    # the teacher-forced forward's vocabulary product in step-sized chunks (with XG_GEMM_FORCE_BG=1: the background form they run in)
+    ("logits chunk NT 256x20000 K=512", 0, 1, 256, 20000, 512, 0),
+    ("logits chunk NT 384x20000 K=512", 0, 1, 384, 20000, 512, 0),
+    ("logits chunk NT 512x20000 K=512", 0, 1, 512, 20000, 512, 0),
+    ("logits chunk NT 1280x20000 K=512", 0, 1, 1280, 20000, 512, 0),
 ]
 if os.environ.get("XG_GEMM_SHAPES"):
     SHAPES = [s for s in SHAPES if any(k in s[0] for k in os.environ["XG_GEMM_SHAPES"].split(","))]
