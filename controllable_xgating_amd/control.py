@@ -9,6 +9,8 @@ itself, ``caption_sampled`` captions under them and ``first_occurrences`` marks 
 captions under them.  Eval mode, fp32, one GPU.  By default the captioner runs over the B*S rows with the video inputs repeated per
 template; ``share_encoder=True`` hands the videos over once (``SAModel.sample_per_video``, include/xgate_control.h): the captioner's
 encoder, init_hidden and v2a(V) then run once per video and a step's attention reads them once per group of a video's templates.
+``beam_captions_with_templates`` is the captioner's BEAM SEARCH under the templates on one encoder pass
+(``SAModel.beam_captions_per_video``, include/xgate_beam_control.h).
 """
 from __future__ import annotations
 
@@ -83,13 +85,31 @@ def caption_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mas
     ``share_encoder=True``: the captioner takes the B videos once (``cap_model.sample_per_video``; greedy or sampled, no beam search:
     beam_size > 1 raises NotImplementedError) instead of the repeated inputs; the two paths agree up to the last bits of fp32."""
     if share_encoder and opt.get("beam_size", 1) > 1:
-        raise NotImplementedError("share_encoder=True has no beam search: beam_size must be 1")
+        raise NotImplementedError("share_encoder=True has no beam search: beam_size must be 1 (beam_captions_with_templates "
+                                  "is the beam search on one encoder pass)")
     with torch.no_grad():
         tag_logp, _, _, pos_feats = pos_model.sample_forced(feats_rgb, feats_opfl, feat_mask, templates, collect_states=False,
                                                             trim=False)
         B, S = tag_logp.shape[:2]
         seq, slp = _caption_rows(cap_model, feats_rgb, feats_opfl, feat_mask, pos_feats, B, S, opt, share_encoder)
     return seq, slp, tag_logp.sum(2)
+
+
+def beam_captions_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, beam_size=5, suppress_token=1):
+    """The W = beam_size most likely captions of each of the B videos under each of its S POS templates, on one captioner encoder
+    pass: (seq (B,S,W,L) int64, seq_logp (B,S,W,L), score (B,S,W), template_score (B,S)).  The forced POS rollout
+    (``pos_model.sample_forced``) leaves `pos_feats` (B*S,R) on the device and ``cap_model.beam_captions_per_video``
+    (include/xgate_beam_control.h; `beam_size`, `suppress_token` and the order of a pair's beams as there) takes the B videos once;
+    nothing is read back between the two or after them.  `templates` as in ``caption_with_templates``: those of
+    ``pos_model.sample_templates`` or ``beam_templates`` are valid inputs.  Inference only: both models run under
+    ``torch.no_grad()``."""
+    with torch.no_grad():
+        tag_logp, _, _, pos_feats = pos_model.sample_forced(feats_rgb, feats_opfl, feat_mask, templates, collect_states=False,
+                                                            trim=False)
+        B, S = tag_logp.shape[:2]
+        seq, seq_logp, score = cap_model.beam_captions_per_video(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(B, S, -1),
+                                                                 beam_size=beam_size, suppress_token=suppress_token)
+    return seq, seq_logp, score, tag_logp.sum(2)
 
 
 def first_occurrences(templates):
@@ -115,7 +135,8 @@ def caption_sampled(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, S, t
     marks each video's distinct templates (``first_occurrences``).  Inference only: both models run under ``torch.no_grad()``.
     `share_encoder` as in ``caption_with_templates``."""
     if share_encoder and opt.get("beam_size", 1) > 1:
-        raise NotImplementedError("share_encoder=True has no beam search: beam_size must be 1")
+        raise NotImplementedError("share_encoder=True has no beam search: beam_size must be 1 (beam_captions_with_templates "
+                                  "is the beam search on one encoder pass)")
     with torch.no_grad():
         templates, tag_logp, _, _, pos_feats = pos_model.sample_templates(feats_rgb, feats_opfl, feat_mask, S, temperature=temperature,
                                                                           uniforms=uniforms, generator=generator,
@@ -136,7 +157,8 @@ def caption_beam(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, beam_si
     Inference only: both models run under ``torch.no_grad()``.  `share_encoder` as in ``caption_with_templates`` (it is the
     CAPTIONER's beam search, opt["beam_size"] > 1, that it does not serve; `beam_size` here is the POS generator's)."""
     if share_encoder and opt.get("beam_size", 1) > 1:
-        raise NotImplementedError("share_encoder=True has no beam search: beam_size must be 1")
+        raise NotImplementedError("share_encoder=True has no beam search: beam_size must be 1 (beam_captions_with_templates "
+                                  "is the beam search on one encoder pass)")
     with torch.no_grad():
         templates, _, score, _ = pos_model.beam_templates(feats_rgb, feats_opfl, feat_mask, beam_size=beam_size,
                                                           suppress_tag=suppress_tag, trim=False)

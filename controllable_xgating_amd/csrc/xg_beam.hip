@@ -5,6 +5,8 @@
 //                          log-softmax is never written.  The row is read from memory ONCE and staged in LDS (80 KB at V = 20000);
 //                          a row beyond 150 KiB is read three times instead.  Ranking is on lp = logit - lse itself, so two
 //                          logits that round to one lp are ordered by word index like the host search's torch.topk over lp.
+//   cap_beam_topw_thr_kernel  the same outputs, the insertion replaced by a threshold from the threads' maxima and a short candidate
+//                          list (the search over S templates per video, include/xgate_beam_control.h, has S times the rows).
 //   cap_beam_merge_kernel  one workgroup per video: fills the candidate tables from topv / topi, runs steps 3-5 of the rule
 //                          (beam_merge, xg_beam_core.h), and every thread gathers h1, c1, h2, c2 of slot v from its parent out of
 //                          the step's OUTPUT buffer into its INPUT buffer.
@@ -22,24 +24,28 @@ constexpr int TW_TPB = 1024, TW_WAVES = TW_TPB / 64;
 constexpr int CB_MAX = XG_BEAM_MAX;
 constexpr int CB_EMPTY = 0x7fffffff;                      // word index of a list entry that holds nothing
 constexpr int CB_STAGE_BYTES = 150 * 1024;                // the most dynamic LDS a row may take (as xgk_rollout_step)
+constexpr int TW_CAND = 32;                               // the threshold form's candidate list (cap_beam_topw_thr_kernel): 4 W at the widest
 static_assert(TW_WAVES * CB_MAX <= TW_TPB, "one thread per entry of the last ranking");
+static_assert(TW_CAND <= TW_TPB && TW_CAND >= CB_MAX, "one thread per candidate; room for W of them");
 
-template <int W, bool STAGE>
-__global__ void __launch_bounds__(TW_TPB) cap_beam_topw_kernel(const float* __restrict__ logits, int64_t ld, int V, int suppress,
-                                                               float* __restrict__ topv, int32_t* __restrict__ topi) {
-    extern __shared__ float4 cb_lds4[];
-    __shared__ float red[TW_WAVES], cv[TW_WAVES * W];
-    __shared__ int ci[TW_WAVES * W];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* g = logits + (size_t)blockIdx.x * ld;
-    // rows of a V that is no multiple of 4 start off the 16-byte grid: `head` scalars, `nvec` float4, the rest scalars
-    const int mis = (int)((reinterpret_cast<uintptr_t>(g) >> 2) & 3);
-    const int head = min(V, (4 - mis) & 3);
-    const int nvec = (V - head) >> 2;
-    const int tail0 = head + 4 * nvec;
-    const float4* g4 = reinterpret_cast<const float4*>(g + head);
-    float* row = reinterpret_cast<float*>(cb_lds4) + mis;         // (row + head is on the 16-byte grid like g + head)
-    auto each_global = [&](auto&& f) {
+// One row of logits as the top-W kernels see it: staged in LDS after its one trip from memory, or (a row beyond CB_STAGE_BYTES)
+// read from memory by every pass.
+template <bool STAGE>
+struct TopwRow {
+    const float* g; const float4* g4; float* row;
+    int V, tid, head, nvec, tail0;
+    __device__ __forceinline__ TopwRow(const float* logits, int64_t ld, int V_, float4* lds4) : V(V_), tid(threadIdx.x) {
+        g = logits + (size_t)blockIdx.x * ld;
+        // rows of a V that is no multiple of 4 start off the 16-byte grid: `head` scalars, `nvec` float4, the rest scalars
+        const int mis = (int)((reinterpret_cast<uintptr_t>(g) >> 2) & 3);
+        head = min(V, (4 - mis) & 3);
+        nvec = (V - head) >> 2;
+        tail0 = head + 4 * nvec;
+        g4 = reinterpret_cast<const float4*>(g + head);
+        row = reinterpret_cast<float*>(lds4) + mis;               // (row + head is on the 16-byte grid like g + head)
+    }
+    template <typename F>
+    __device__ __forceinline__ void each_global(F&& f) const {
         if (tid < head) f(g[tid], tid);
         for (int j = tid; j < nvec; j += TW_TPB) {
             const float4 x = g4[j];
@@ -47,47 +53,59 @@ __global__ void __launch_bounds__(TW_TPB) cap_beam_topw_kernel(const float* __re
             f(x.x, i); f(x.y, i + 1); f(x.z, i + 2); f(x.w, i + 3);
         }
         if (tail0 + tid < V) f(g[tail0 + tid], tail0 + tid);
-    };
-    auto each = [&](auto&& f) {
+    }
+    template <typename F>
+    __device__ __forceinline__ void each(F&& f) const {
         if constexpr (STAGE) { for (int i = tid; i < V; i += TW_TPB) f(row[i], i); }
         else each_global(f);
-    };
-    // ---- the row's maximum (and, staged, its one trip from memory)
-    float mx = -INFINITY;
-    if constexpr (STAGE) {
-        if (tid < head) { const float x = g[tid]; row[tid] = x; mx = fmaxf(mx, x); }
-        for (int j = tid; j < nvec; j += TW_TPB) {
-            const float4 x = g4[j];
-            *reinterpret_cast<float4*>(row + head + 4 * j) = x;
-            mx = fmaxf(fmaxf(mx, fmaxf(x.x, x.y)), fmaxf(x.z, x.w));
-        }
-        if (tail0 + tid < V) { const float x = g[tail0 + tid]; row[tail0 + tid] = x; mx = fmaxf(mx, x); }
-    } else {
-        each_global([&](float x, int) { mx = fmaxf(mx, x); });
     }
-    mx = wave_max(mx);
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = red[0];
+    // the row's maximum (and, staged, its one trip from memory), then its log-sum-exp; red: TW_WAVES floats of LDS
+    __device__ __forceinline__ float stage_lse(float* red) const {
+        const int lane = tid & 63, wave = tid >> 6;
+        float mx = -INFINITY;
+        if constexpr (STAGE) {
+            if (tid < head) { const float x = g[tid]; row[tid] = x; mx = fmaxf(mx, x); }
+            for (int j = tid; j < nvec; j += TW_TPB) {
+                const float4 x = g4[j];
+                *reinterpret_cast<float4*>(row + head + 4 * j) = x;
+                mx = fmaxf(fmaxf(mx, fmaxf(x.x, x.y)), fmaxf(x.z, x.w));
+            }
+            if (tail0 + tid < V) { const float x = g[tail0 + tid]; row[tail0 + tid] = x; mx = fmaxf(mx, x); }
+        } else {
+            each_global([&](float x, int) { mx = fmaxf(mx, x); });
+        }
+        mx = wave_max(mx);
+        if (lane == 0) red[wave] = mx;
+        __syncthreads();
+        mx = red[0];
 #pragma unroll
-    for (int k = 1; k < TW_WAVES; ++k) mx = fmaxf(mx, red[k]);
-    __syncthreads();
-    // ---- log-sum-exp: thread, wave (DPP), then the waves in one fixed order
-    float s = 0.f;
-    each([&](float x, int) { s += __expf(x - mx); });
-    s = wave_sum(s);
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    float tot = 0.f;
+        for (int k = 1; k < TW_WAVES; ++k) mx = fmaxf(mx, red[k]);
+        __syncthreads();
+        // log-sum-exp: thread, wave (DPP), then the waves in one fixed order
+        float s = 0.f;
+        each([&](float x, int) { s += __expf(x - mx); });
+        s = wave_sum(s);
+        if (lane == 0) red[wave] = s;
+        __syncthreads();
+        float tot = 0.f;
 #pragma unroll
-    for (int k = 0; k < TW_WAVES; ++k) tot += red[k];
-    const float lse = mx + logf(tot);
+        for (int k = 0; k < TW_WAVES; ++k) tot += red[k];
+        return mx + logf(tot);
+    }
+};
+
+// The selection by insertion, called by ALL threads of the workgroup: each thread's W best of its elements in registers, a wave's W
+// best by W rounds of a shuffle arg-max, the last waves * W entries by counting.  cv / ci: TW_WAVES * W entries of LDS.
+template <int W, bool STAGE>
+__device__ __forceinline__ void topw_by_insertion(const TopwRow<STAGE>& r, float lse, int suppress, float* cv, int* ci,
+                                                  float* __restrict__ topv, int32_t* __restrict__ topi) {
+    const int tid = r.tid, lane = tid & 63, wave = tid >> 6, V = r.V;
     // ---- each thread's W best in registers (a descending list; unrolled insertion, no indexing by a variable)
     float bv[W];
     int bi[W];
 #pragma unroll
     for (int k = 0; k < W; ++k) { bv[k] = -INFINITY; bi[k] = CB_EMPTY; }
-    each([&](float x, int i) {
+    r.each([&](float x, int i) {
         float v = x - lse;
         if (i == suppress) v -= 1000.0f;
         int ix = i;
@@ -103,7 +121,7 @@ __global__ void __launch_bounds__(TW_TPB) cap_beam_topw_kernel(const float* __re
     });
     // ---- the wave's W best: W rounds of (best head of any lane, that lane pops)
 #pragma unroll
-    for (int r = 0; r < W; ++r) {
+    for (int rd = 0; rd < W; ++rd) {
         float v = bv[0];
         int ix = bi[0];
 #pragma unroll
@@ -112,7 +130,7 @@ __global__ void __launch_bounds__(TW_TPB) cap_beam_topw_kernel(const float* __re
             const int oi = __shfl_xor(ix, off);
             if (beam_before(ov, oi, v, ix)) { v = ov; ix = oi; }
         }
-        if (lane == 0) { cv[wave * W + r] = v; ci[wave * W + r] = ix; }
+        if (lane == 0) { cv[wave * W + rd] = v; ci[wave * W + rd] = ix; }
         if (bi[0] == ix) {
 #pragma unroll
             for (int k = 0; k + 1 < W; ++k) { bv[k] = bv[k + 1]; bi[k] = bi[k + 1]; }
@@ -138,20 +156,122 @@ __global__ void __launch_bounds__(TW_TPB) cap_beam_topw_kernel(const float* __re
     }
 }
 
-template <int W>
+template <int W, bool STAGE>
+__global__ void __launch_bounds__(TW_TPB) cap_beam_topw_kernel(const float* __restrict__ logits, int64_t ld, int V, int suppress,
+                                                               float* __restrict__ topv, int32_t* __restrict__ topi) {
+    extern __shared__ float4 cb_lds4[];
+    __shared__ float red[TW_WAVES], cv[TW_WAVES * W];
+    __shared__ int ci[TW_WAVES * W];
+    const TopwRow<STAGE> r(logits, ld, V, cb_lds4);
+    const float lse = r.stage_lse(red);
+    topw_by_insertion<W, STAGE>(r, lse, suppress, cv, ci, topv, topi);
+}
+
+// The same contract and outputs with the selection behind a THRESHOLD (include/xgate_beam_control.h; only xgbc_beam_search
+// launches it).  tau = the W-th largest of the threads' maxima of v = lp (less 1000 at `suppress`): every thread's maximum is
+// another element of the row and min(V, TW_TPB) >= W threads hold one, so at least W elements have v >= tau and every member of the
+// top W has.  A second pass collects the elements with v >= tau in LDS (the list's order never reaches the output: an LDS atomic
+// counts them) and the list is ranked by counting on beam_before, ties at tau included.  A list outside [W, TW_CAND] -- many
+// exact ties at tau; none at all in a row with NaNs, where no comparison holds -- sends the WHOLE workgroup to the insertion path.
+template <int W, bool STAGE>
+__global__ void __launch_bounds__(TW_TPB) cap_beam_topw_thr_kernel(const float* __restrict__ logits, int64_t ld, int V, int suppress,
+                                                                   float* __restrict__ topv, int32_t* __restrict__ topi) {
+    extern __shared__ float4 cb_lds4[];
+    __shared__ float red[TW_WAVES], cv[TW_WAVES * W], lv[TW_CAND], tau_s;
+    __shared__ int ci[TW_WAVES * W], li[TW_CAND], cnt_s;
+    const TopwRow<STAGE> r(logits, ld, V, cb_lds4);
+    const int tid = r.tid, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) cnt_s = 0;                                      // (two barriers in stage_lse come before its first use)
+    const float lse = r.stage_lse(red);
+    // ---- each thread's maximum, a wave's W largest of those (W rounds: the wave's maximum, its first holder gives it up)
+    float tm = -INFINITY;
+    r.each([&](float x, int i) {
+        float v = x - lse;
+        if (i == suppress) v -= 1000.0f;
+        tm = fmaxf(tm, v);
+    });
+#pragma unroll
+    for (int rd = 0; rd < W; ++rd) {
+        const float m = wave_max(tm);
+        const unsigned long long holders = __ballot(tm == m);
+        if (lane == 0) cv[wave * W + rd] = m;
+        if (holders != 0 && lane == __ffsll(holders) - 1) tm = -INFINITY;
+    }
+    __syncthreads();
+    // ---- tau: the W-th largest of the waves * W values, with multiplicity (the position breaks ties: one entry has rank W - 1)
+    if (tid < TW_WAVES * W) {
+        const float v = cv[tid];
+        int rank = 0;
+        for (int j = 0; j < TW_WAVES * W; ++j) {
+            const float ov = cv[j];
+            rank += (ov > v || (ov == v && j < tid)) ? 1 : 0;
+        }
+        if (rank == W - 1) tau_s = v;
+    }
+    __syncthreads();
+    const float tau = tau_s;
+    // ---- the candidates
+    r.each([&](float x, int i) {
+        float v = x - lse;
+        if (i == suppress) v -= 1000.0f;
+        if (v >= tau) {
+            const int at = atomicAdd(&cnt_s, 1);
+            if (at < TW_CAND) { lv[at] = v; li[at] = i; }
+        }
+    });
+    __syncthreads();
+    const int n = cnt_s;
+    if (n < W || n > TW_CAND) {                                   // uniform over the workgroup
+        topw_by_insertion<W, STAGE>(r, lse, suppress, cv, ci, topv, topi);
+        return;
+    }
+    // ---- n >= W distinct words under a total order: every rank below W is taken exactly once, so every output is written
+    if (tid < n) {
+        const float v = lv[tid];
+        const int ix = li[tid];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += beam_before(lv[j], li[j], v, ix) ? 1 : 0;
+        if (rank < W) {
+            topv[(size_t)blockIdx.x * W + rank] = v;
+            topi[(size_t)blockIdx.x * W + rank] = ix;             // (an index of `each`: inside [0, V))
+        }
+    }
+}
+
+template <int W, bool THR>
 int launch_topw(hipStream_t st, const float* logits, int64_t ld, int M, int V, int suppress, float* topv, int32_t* topi) {
+    using Kernel = void (*)(const float*, int64_t, int, int, float*, int32_t*);
+    Kernel staged, unstaged;
+    if constexpr (THR) { staged = cap_beam_topw_thr_kernel<W, true>; unstaged = cap_beam_topw_thr_kernel<W, false>; }
+    else { staged = cap_beam_topw_kernel<W, true>; unstaged = cap_beam_topw_kernel<W, false>; }
     const size_t lds = ((size_t)V + 8) * sizeof(float);
     if (lds <= (size_t)CB_STAGE_BYTES) {
         if (lds > 64 * 1024) {                                 // > 64 KiB of dynamic LDS is opted into once per kernel and device
             static std::atomic<unsigned> optin{0};
-            XG_TRY(xg_lds_optin(optin, reinterpret_cast<const void*>(&cap_beam_topw_kernel<W, true>), CB_STAGE_BYTES));
+            XG_TRY(xg_lds_optin(optin, reinterpret_cast<const void*>(staged), CB_STAGE_BYTES));
         }
-        hipLaunchKernelGGL((cap_beam_topw_kernel<W, true>), dim3(M), dim3(TW_TPB), lds, st, logits, ld, V, suppress, topv, topi);
+        hipLaunchKernelGGL(staged, dim3(M), dim3(TW_TPB), lds, st, logits, ld, V, suppress, topv, topi);
     } else {
-        hipLaunchKernelGGL((cap_beam_topw_kernel<W, false>), dim3(M), dim3(TW_TPB), 0, st, logits, ld, V, suppress, topv, topi);
+        hipLaunchKernelGGL(unstaged, dim3(M), dim3(TW_TPB), 0, st, logits, ld, V, suppress, topv, topi);
     }
     XG_CHECK_LAUNCH();
     return XG_OK;
+}
+
+template <bool THR>
+int topw_any(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, float* topv, int32_t* topi) {
+    if (M <= 0 || V <= 0 || W < 1 || W > CB_MAX || W > V || ld < V || suppress >= V) return XG_EINVAL;
+    if (suppress < 0) suppress = -1;
+    switch (W) {
+        case 1: return launch_topw<1, THR>(st, logits, ld, M, V, suppress, topv, topi);
+        case 2: return launch_topw<2, THR>(st, logits, ld, M, V, suppress, topv, topi);
+        case 3: return launch_topw<3, THR>(st, logits, ld, M, V, suppress, topv, topi);
+        case 4: return launch_topw<4, THR>(st, logits, ld, M, V, suppress, topv, topi);
+        case 5: return launch_topw<5, THR>(st, logits, ld, M, V, suppress, topv, topi);
+        case 6: return launch_topw<6, THR>(st, logits, ld, M, V, suppress, topv, topi);
+        case 7: return launch_topw<7, THR>(st, logits, ld, M, V, suppress, topv, topi);
+        default: return launch_topw<8, THR>(st, logits, ld, M, V, suppress, topv, topi);
+    }
 }
 
 __global__ void __launch_bounds__(CB_TPB) cap_beam_merge_kernel(CapBeamMergeArgs a) {
@@ -231,18 +351,11 @@ int xgk_cap_beam_repeat(hipStream_t st, const CapBeamRepeatArgs& a, int B, int W
 }
 
 int xgk_cap_beam_topw(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, float* topv, int32_t* topi) {
-    if (M <= 0 || V <= 0 || W < 1 || W > CB_MAX || W > V || ld < V || suppress >= V) return XG_EINVAL;
-    if (suppress < 0) suppress = -1;
-    switch (W) {
-        case 1: return launch_topw<1>(st, logits, ld, M, V, suppress, topv, topi);
-        case 2: return launch_topw<2>(st, logits, ld, M, V, suppress, topv, topi);
-        case 3: return launch_topw<3>(st, logits, ld, M, V, suppress, topv, topi);
-        case 4: return launch_topw<4>(st, logits, ld, M, V, suppress, topv, topi);
-        case 5: return launch_topw<5>(st, logits, ld, M, V, suppress, topv, topi);
-        case 6: return launch_topw<6>(st, logits, ld, M, V, suppress, topv, topi);
-        case 7: return launch_topw<7>(st, logits, ld, M, V, suppress, topv, topi);
-        default: return launch_topw<8>(st, logits, ld, M, V, suppress, topv, topi);
-    }
+    return topw_any<false>(st, logits, ld, M, V, W, suppress, topv, topi);
+}
+
+int xgk_cap_beam_topw_thr(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, float* topv, int32_t* topi) {
+    return topw_any<true>(st, logits, ld, M, V, W, suppress, topv, topi);
 }
 
 int xgk_cap_beam_merge(hipStream_t st, int B, CapBeamMergeArgs a) {

@@ -372,6 +372,8 @@ int xgk_cap_beam_repeat(hipStream_t st, const CapBeamRepeatArgs& a, int B, int W
 // per row of (M,V) raw logits: the W largest log_softmax values (the one at `suppress` >= 0 less 1000) in descending order, lower
 // word first on exact ties, into topv / topi (M,W)
 int xgk_cap_beam_topw(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, float* topv, int32_t* topi);
+// the same contract and outputs, the selection behind a threshold from the threads' maxima (xgbc_beam_search's form)
+int xgk_cap_beam_topw_thr(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, float* topv, int32_t* topi);
 struct CapBeamMergeArgs {
     const float* topv; const int32_t* topi;   // (M,W) of this step
     BeamBook<int64_t> book;

@@ -14,6 +14,7 @@
 #include "xg_kernels.h"
 #include "../../include/xgate_beam.h"
 #include "../../include/xgate_control.h"
+#include "../../include/xgate_beam_control.h"
 
 #include <new>
 #include <cstdlib>
@@ -1909,7 +1910,7 @@ namespace {
 struct BeamWs {
     Ws enc;                        // the B videos: encoder, initial state, v2a(V)   (a whole workspace at T = 1)
     Ws step;                       // what core_step touches, over M rows (every other field stays null)
-    float *Venc, *vproj, *pos;     // row-repeated (M,K,R), (M,K,A), (M,R)
+    float *Venc, *vproj, *pos;     // row-repeated (M,K,R), (M,K,A), (M,R); the first two only when S == 0
     float* st[2][4];               // h1, c1, h2, c2 (M,R): [0] read by the step, [1] written by it
     float* topv; int32_t* topi;    // (M,W) every row's W best of the step
     BeamBook<int64_t> book;
@@ -1918,12 +1919,14 @@ struct BeamWs {
 
 inline XgDims beam_dims(const XgDims& d, int B) { XgDims e = d; e.B = B; e.T = 1; return e; }
 
-BeamWs beam_carve(const XgDims& d, int W, void* base) {
+// S == 0: xgcb_beam_search, one group of W rows per video.  S >= 1: xgbc_beam_search (include/xgate_beam_control.h), G = B S groups of
+// W rows, a video's S W rows share its V and v2a(V) in the per-video part: no (M,K,R) or (M,K,A) block.
+BeamWs beam_carve(const XgDims& d, int S, int W, void* base) {
     BeamWs w{};
     w.enc = carve(beam_dims(d, d.B), base);
     w.enc.sh16 = nullptr; w.enc.bytes = w.enc.core_bytes;          // fp32 only: no bf16 mirror region
     Carver c{static_cast<char*>(base), w.enc.core_bytes};
-    const size_t B = d.B, M = B * W, K = d.K, R = d.R, A = d.A, E = d.E, V = d.V, L = d.T - 1;
+    const size_t G = (size_t)d.B * (S > 0 ? S : 1), M = G * W, K = d.K, R = d.R, A = d.A, E = d.E, V = d.V, L = d.T - 1;
     Ws& s = w.step;
     s.S = c.take<float>(M * 4 * R); s.S2 = c.take<float>(M * 4 * R); s.state_tmp = c.take<float>(4 * M * R);
     s.AFU = c.take<float>(M * R + ((M + 3) & ~(size_t)3)); s.ATS = s.AFU + M * R;
@@ -1931,40 +1934,36 @@ BeamWs beam_carve(const XgDims& d, int W, void* base) {
     s.P = c.take<float>(M * A); s.ALPHA = c.take<float>(M * K); s.AF = c.take<float>(M * R);
     s.LOGITS = c.take<float>(M * V);
     s.dsync = c.take<int32_t>(XGK_DSTEP_SYNC_BYTES / sizeof(int32_t));
-    w.Venc = c.take<float>(M * K * R); w.vproj = c.take<float>(M * K * A); w.pos = c.take<float>(M * R);
+    if (S == 0) { w.Venc = c.take<float>(M * K * R); w.vproj = c.take<float>(M * K * A); }
+    w.pos = c.take<float>(M * R);
     for (int i = 0; i < 2; ++i) for (int k = 0; k < 4; ++k) w.st[i][k] = c.take<float>(M * R);
     w.topv = c.take<float>(M * W); w.topi = c.take<int32_t>(M * W);
-    w.book = beam_book_carve<int64_t>(c, B, W, L);
+    w.book = beam_book_carve<int64_t>(c, G, W, L);
     w.bytes = (c.off + 255) & ~(size_t)255;
     return w;
 }
 
-bool beam_dims_ok(const XgDims* d, int W, int suppress) {
-    if (!dims_ok(d) || d->T < 2) return false;
+bool beam_dims_ok(const XgDims* d, int S, int W, int suppress) {
+    if (!dims_ok(d) || d->T < 2 || S < 0) return false;
     if (W < 1 || W > XGCB_MAX_BEAM || W > d->V || suppress >= d->V) return false;
-    return (int64_t)d->B * W <= (1 << 20);                         // (row indices and launch grids stay far inside int)
+    return (int64_t)d->B * (S > 0 ? S : 1) * W <= (1 << 20);       // (row indices and launch grids stay far inside int)
 }
 
-}  // namespace
-
-extern "C" int xgcb_version(void) { return XGCB_VERSION; }
-
-extern "C" size_t xgcb_workspace_bytes(const XgDims* d, int32_t W) {
-    if (!beam_dims_ok(d, W, -1)) return 0;
-    return beam_carve(*d, W, nullptr).bytes;
-}
-
-extern "C" int xgcb_beam_search(void* stream, const XgDims* d, int32_t W, int32_t suppress_token, const XgParams* p,
-                                const XgBnState* bn, const XgBatch* x, const XgRun* run, int64_t* seq, float* seq_logp,
-                                float* score, int32_t* trace, void* ws, size_t ws_bytes) {
-    if (!beam_dims_ok(d, W, suppress_token) || !p || !x || !run || !seq || !seq_logp || !score || !ws) return XG_EINVAL;
+// Both searches (S as in beam_carve).  Once per call on the B videos: encoder, init_hidden, v2a(V); then the initial state goes to
+// each video's rows and pos_feats to each group's W slots; V and v2a(V) are row-repeated for S == 0 only.  With S >= 1 core_step is
+// told the rows per video (the stand-alone group attention over the per-video V / v2a(V)) and the selection is the threshold form.
+int beam_search_impl(void* stream, const XgDims* d, int S, int W, int32_t suppress_token, const XgParams* p, const XgBnState* bn,
+                     const XgBatch* x, const XgRun* run, int64_t* seq, float* seq_logp, float* score, int32_t* trace, void* ws,
+                     size_t ws_bytes) {
+    if (!beam_dims_ok(d, S, W, suppress_token) || !p || !x || !run || !seq || !seq_logp || !score || !ws) return XG_EINVAL;
     if (!bn || !bn->rgb_mean || !bn->rgb_var || !bn->opfl_mean || !bn->opfl_var) return XG_EINVAL;
     if (!x->feats_rgb || !x->feats_opfl || !x->feat_mask || !x->pos_feats) return XG_EINVAL;
     if (run->train || run->save || run->gemm_mode != 0 || (uintptr_t)ws % 256 != 0) return XG_EINVAL;
-    BeamWs w = beam_carve(*d, W, ws);
+    BeamWs w = beam_carve(*d, S, W, ws);
     if (ws_bytes < w.bytes) return XG_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int B = d->B, R = d->R, A = d->A, E = d->E, K = d->K, V = d->V, L = d->T - 1, M = B * W;
+    const bool shared = S > 0;
+    const int B = d->B, R = d->R, A = d->A, E = d->E, K = d->K, V = d->V, L = d->T - 1, G = shared ? B * S : B, M = G * W;
     const XgDims de = beam_dims(*d, B), dm = beam_dims(*d, M);
     attach_packed(w.enc, de, run);
     attach_packed(w.step, dm, run);
@@ -1975,10 +1974,17 @@ extern "C" int xgcb_beam_search(void* stream, const XgDims* d, int32_t W, int32_
     {
         CapBeamRepeatArgs ra{};
         auto rep = [&](float* dst, const float* src, size_t n) { ra.e[ra.n++] = CapBeamRepeatEntry{dst, src, (int64_t)n}; };
-        rep(w.Venc, w.enc.Venc, (size_t)K * R); rep(w.vproj, w.enc.vproj, (size_t)K * A); rep(w.pos, x->pos_feats, R);
+        if (!shared) { rep(w.Venc, w.enc.Venc, (size_t)K * R); rep(w.vproj, w.enc.vproj, (size_t)K * A); rep(w.pos, x->pos_feats, R); }
         rep(w.st[0][0], w.enc.H1, R); rep(w.st[0][1], w.enc.C1, R); rep(w.st[0][2], w.enc.H2, R); rep(w.st[0][3], w.enc.C2, R);
-        XG_TRY(xgk_cap_beam_repeat(st, ra, B, W));
+        XG_TRY(xgk_cap_beam_repeat(st, ra, B, M / B));
+        if (shared) {                                     // pos_feats has a row per GROUP
+            CapBeamRepeatArgs rp{};
+            rp.e[rp.n++] = CapBeamRepeatEntry{w.pos, x->pos_feats, (int64_t)R};
+            XG_TRY(xgk_cap_beam_repeat(st, rp, G, W));
+        }
     }
+    const float* Venc = shared ? w.enc.Venc : w.Venc;
+    const float* vproj = shared ? w.enc.vproj : w.vproj;
     XG_TRY(zero_dsync(st, w.step));
     if (hipMemsetAsync(w.book.tok, 0, sizeof(int64_t) * (size_t)M, st) != hipSuccess) return XG_EHIP;   // BOS
     CapBeamMergeArgs ma{};
@@ -1997,13 +2003,44 @@ extern "C" int xgcb_beam_search(void* stream, const XgDims* d, int32_t W, int32_
         s.h1 = w.st[0][0]; s.c1 = w.st[0][1]; s.h2 = w.st[0][2]; s.c2 = w.st[0][3];
         s.h1o = w.st[1][0]; s.c1o = w.st[1][1]; s.h2o = w.st[1][2]; s.c2o = w.st[1][3];
         s.P = w.step.P; s.alpha = w.step.ALPHA; s.af = w.step.AF; s.g1 = nullptr; s.g2 = nullptr; s.t = t;
-        XG_TRY(core_step(st, dm, *p, *run, w.step, w.Venc, w.vproj, s));
+        s.rows_per_video = shared ? S * W : 0;
+        XG_TRY(core_step(st, dm, *p, *run, w.step, Venc, vproj, s));
         XG_TRY(xgk_linear(st, 0, M, V, R, s.h2o, R, p->logit_w, p->logit_b, w.step.LOGITS, V));
-        XG_TRY(xgk_cap_beam_topw(st, w.step.LOGITS, V, M, V, W, suppress_token, w.topv, w.topi));
+        XG_TRY((shared ? xgk_cap_beam_topw_thr : xgk_cap_beam_topw)(st, w.step.LOGITS, V, M, V, W, suppress_token, w.topv, w.topi));
         ma.book.t = t;
-        XG_TRY(xgk_cap_beam_merge(st, B, ma));
+        XG_TRY(xgk_cap_beam_merge(st, G, ma));
     }
-    return xgk_cap_beam_backtrace(st, B, w.book, seq, seq_logp, score);
+    return xgk_cap_beam_backtrace(st, G, w.book, seq, seq_logp, score);
+}
+
+}  // namespace
+
+extern "C" int xgcb_version(void) { return XGCB_VERSION; }
+
+extern "C" size_t xgcb_workspace_bytes(const XgDims* d, int32_t W) {
+    if (!beam_dims_ok(d, 0, W, -1)) return 0;
+    return beam_carve(*d, 0, W, nullptr).bytes;
+}
+
+extern "C" int xgcb_beam_search(void* stream, const XgDims* d, int32_t W, int32_t suppress_token, const XgParams* p,
+                                const XgBnState* bn, const XgBatch* x, const XgRun* run, int64_t* seq, float* seq_logp,
+                                float* score, int32_t* trace, void* ws, size_t ws_bytes) {
+    return beam_search_impl(stream, d, 0, W, suppress_token, p, bn, x, run, seq, seq_logp, score, trace, ws, ws_bytes);
+}
+
+// ---- the same search under S POS templates per video (include/xgate_beam_control.h): x holds the B videos once, pos_feats (B S,R)
+extern "C" int xgbc_version(void) { return XGBC_VERSION; }
+
+extern "C" size_t xgbc_workspace_bytes(const XgDims* d, int32_t S, int32_t W) {
+    if (S < 1 || !beam_dims_ok(d, S, W, -1)) return 0;
+    return beam_carve(*d, S, W, nullptr).bytes;
+}
+
+extern "C" int xgbc_beam_search(void* stream, const XgDims* d, int32_t S, int32_t W, int32_t suppress_token, const XgParams* p,
+                                const XgBnState* bn, const XgBatch* x, const XgRun* run, int64_t* seq, float* seq_logp,
+                                float* score, int32_t* trace, void* ws, size_t ws_bytes) {
+    if (S < 1) return XG_EINVAL;
+    return beam_search_impl(stream, d, S, W, suppress_token, p, bn, x, run, seq, seq_logp, score, trace, ws, ws_bytes);
 }
 
 // ================================================================== the captioner under S templates per video (include/xgate_control.h)

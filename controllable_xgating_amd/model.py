@@ -594,6 +594,47 @@ class SAModel(FlatParams, nn.Module):
         out = (seq, seq_logp, score)
         return out + (trace,) if return_trace else out
 
+    def beam_captions_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, beam_size=5, suppress_token=1,
+                                return_trace=False):
+        """``beam_captions`` for S `pos_feats` rows per video on ONE encoder pass (include/xgate_beam_control.h): the B videos are
+        handed over once, `pos_feats` is (B,S,R), and the result is what ``beam_captions`` gives on the batch with every video
+        repeated S times, (video, template) pair by pair: (seq (B,S,W,L) int64, seq_logp (B,S,W,L), score (B,S,W)[, trace
+        (B,S,L,W,2) int32]).  The encoder, init_hidden and v2a(V) run once per video, V and v2a(V) are not repeated and every
+        step's attention reads them once per group of a video's S*W rows; one enqueue, nothing here synchronises with the host.
+
+        `beam_size`, `suppress_token`, `return_trace` and the order of a pair's beams as in ``beam_captions``.  Eval mode, fp32 and
+        device tensors only."""
+        from . import _native_beam as nb
+        from . import _native_beam_control as nbc
+        self._search_gate("beam_captions_per_video")
+        W, sup = int(beam_size), int(suppress_token)
+        if W < 1 or W > self.vocab_size or W > nb.XGCB_MAX_BEAM:
+            raise ValueError("1 <= beam_size <= min(vocab_size = %d, %d) expected, got %d" % (self.vocab_size, nb.XGCB_MAX_BEAM, W))
+        if sup >= self.vocab_size:
+            raise ValueError("suppress_token must lie below vocab_size = %d (-1: none), got %d" % (self.vocab_size, sup))
+        B, K = feats_rgb.shape[0], feats_rgb.shape[1]
+        if pos_feats.dim() != 3 or pos_feats.shape[0] != B or pos_feats.shape[1] < 1 or pos_feats.shape[2] != self.rnn_size:
+            raise ValueError("pos_feats (B = %d, S, R = %d) expected, got %s" % (B, self.rnn_size, tuple(pos_feats.shape)))
+        self._search_gate("beam_captions_per_video", feats_rgb, feats_opfl, feat_mask, pos_feats)
+        S, L = int(pos_feats.shape[1]), self.seq_length
+        dev = feats_rgb.device
+        lib = nbc.lib()
+        d = self._dims(B, K, L + 1)
+        wp, wn = self._search_workspace("_beam_control_ws", (B, K, L, S, W, str(dev)),
+                                        lambda: lib.xgbc_workspace_bytes(C.byref(d), S, W), dev,
+                                        "xgbc_workspace_bytes: invalid dims or too many rows (B %d, S %d, W %d)" % (B, S, W))
+        with torch.no_grad():
+            b, keep = self._batch(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(B * S, self.rnn_size))
+            ps, bn, run = self._params_struct(), self._bn_struct(), self._run(False)
+            seq = torch.empty(B, S, W, L, dtype=torch.int64, device=dev)
+            seq_logp = torch.empty(B, S, W, L, dtype=torch.float32, device=dev)
+            score = torch.empty(B, S, W, dtype=torch.float32, device=dev)
+            trace = torch.empty(B, S, L, W, 2, dtype=torch.int32, device=dev) if return_trace else None
+            nv.check(lib.xgbc_beam_search(_stream(), C.byref(d), S, W, sup, C.byref(ps), C.byref(bn), C.byref(b), C.byref(run),
+                                          nv.ptr(seq), nv.ptr(seq_logp), nv.ptr(score), nv.ptr(trace), wp, wn), "xgbc_beam_search")
+        out = (seq, seq_logp, score)
+        return out + (trace,) if return_trace else out
+
 
 # ====================================================================== autograd glue
 def _grads_struct(model, device=None):
