@@ -123,6 +123,17 @@ struct Carver {
     }
 };
 
+// What core_step needs besides its StepIO, over `rows` rows, written here only: the cells' products, the dataflow step's sync words
+// and -- whole -- the scratch of an in-place step (state_tmp) and of the fused attention (AFU, ATS).  whole == false: a form of the step
+// that reaches neither branch (separate state blocks, rows_per_video > 0).  core_step refuses a branch whose scratch is null.
+void carve_step_scratch(Carver& c, Ws& w, size_t rows, size_t R, bool whole) {
+    w.S = c.take<float>(rows * 4 * R); w.S2 = c.take<float>(rows * 4 * R);
+    w.dsync = c.take<int32_t>(XGK_DSTEP_SYNC_BYTES / sizeof(int32_t));
+    if (!whole) return;
+    w.state_tmp = c.take<float>(4 * rows * R);
+    w.AFU = c.take<float>(rows * R + ((rows + 3) & ~(size_t)3)); w.ATS = w.AFU + rows * R;
+}
+
 Ws carve(const XgDims& d, void* base) {
     Ws w{};
     Carver c{static_cast<char*>(base), 0};
@@ -137,7 +148,8 @@ Ws carve(const XgDims& d, void* base) {
         w.dX[m] = c.take<float>(N * R);
         w.dCrec[m][1] = c.take<float>(B * R);
     }
-    w.zeroBR = c.take<float>(B * R); w.S = c.take<float>(B * 4 * R); w.S2 = c.take<float>(B * 4 * R);
+    w.zeroBR = c.take<float>(B * R);
+    carve_step_scratch(c, w, B, R, true);
     w.Y = c.take<float>(N * 2 * R); w.Venc = c.take<float>(N * R);
     w.dVw = c.take<float>(N * R); w.dY = c.take<float>(N * 2 * R);
     w.vbar = c.take<float>(B * R); w.vproj = c.take<float>(N * A);
@@ -155,13 +167,9 @@ Ws carve(const XgDims& d, void* base) {
     for (int j = 0; j < 4; ++j) w.dst[1][j] = c.take<float>(B * R);
     w.DVPROJ = c.take<float>(N * A); w.DV = c.take<float>(N * R); w.DPOSG = c.take<float>(TB * R); w.DH1X = c.take<float>(TB * R);
     w.DGP = c.take<float>(TB * R); w.DXe = c.take<float>(TB * E);
-    w.state_tmp = c.take<float>(4 * B * R);
-    w.AFU = c.take<float>(B * R + ((B + 3) & ~(size_t)3)); w.ATS = w.AFU + B * R;
     w.TOK = c.take<int64_t>(TB); w.TOKLP = c.take<float>(TB); w.UNF = c.take<float>(TB);
     w.alive = c.take<int32_t>(4);
-    c.off = (c.off + 15) & ~(size_t)15;
     w.VPART = c.take<float>(B * ((V + 31) / 32 + 16) * 4);    // per-tile row statistics of a rollout step's vocabulary product (row pitch: xg_select.h rs_pitch)
-    w.dsync = c.take<int32_t>(XGK_DSTEP_SYNC_BYTES / sizeof(int32_t));
     {   // the zero block
         c.off = (c.off + 255) & ~(size_t)255;
         const size_t z0 = c.off;
@@ -544,6 +552,11 @@ int init_and_vproj(Streams& ss, const XgDims& d, const XgParams& p, const float*
     XG_TRY(init_hidden(ss.main, d, p, w.Venc, feat_mask, w, w.H1, w.C1, w.H2, w.C2));
     return ss.join2();
 }
+// the encoder, then the initial decoder state and v2a(V), all in `w`
+int encode_and_init(Streams& es, const XgDims& d, const XgParams& p, const XgBnState* bn, const XgBatch& x, const XgRun& run, Ws& w) {
+    XG_TRY(encoder_fwd(es.main, d, p, bn, x, run, w, &es));
+    return init_and_vproj(es, d, p, x.feat_mask, w);
+}
 
 struct StepIO {
     const float* xt;      // (B,E) embedding rows of the step's tokens, or null: gathered from `tok` inside the products
@@ -564,6 +577,11 @@ struct StepIO {
 
 // the packed-weight form of the step needs 16-byte rows everywhere (R % 8 covers R; E and A are checked here)
 inline bool step_packed(const Ws& w, const XgDims& d) { return w.packed && d.R % 8 == 0 && d.E % 4 == 0 && d.A % 4 == 0; }
+// What whoever runs core_step tests before its first launch (core_step tests its own branch again): the scratch of every branch its
+// form of the step can reach.  in_place: the new state overwrites the old one; group_attn: rows_per_video > 0, never the fused attention
+inline bool step_scratch_ok(const Ws& w, bool in_place, bool group_attn) {
+    return w.S && w.S2 && w.dsync && (!in_place || w.state_tmp) && (group_attn || (w.AFU && w.ATS));
+}
 
 // Step t of a time-major workspace: state t -> t + 1, the step's token rows, gated POS rows and saved tensors.  The caller adds
 // the mask and what its form of the step reads besides (pre1 / pos and gp / sel).
@@ -624,6 +642,7 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
         a2.h1 = s.h1; a2.c1 = s.c1; a2.h2 = s.h2; a2.c2 = s.c2;
         a2.h1o = s.h1o; a2.c1o = s.c1o; a2.h2o = s.h2o; a2.c2o = s.c2o;
         a2.copy_back = (s.h1o == s.h1 || s.h2o == s.h2) ? 1 : 0;             // in-place state: new h rows via scratch
+        if (!w.dsync || (a2.copy_back && !w.state_tmp)) return XG_EINVAL;
         a2.h1w = a2.copy_back ? w.state_tmp : s.h1o;
         a2.h2w = a2.copy_back ? w.state_tmp + (size_t)B * R : s.h2o;
         a2.xt = s.xt; a2.tok = s.tok; a2.embed = p.embed_w;
@@ -692,6 +711,7 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
         // old h1, so its new h1 goes to a scratch row block and rides back into the state with launch 3
         const bool h1_alias = s.h1o == s.h1;
         float* h1_new = h1_alias ? w.state_tmp : s.h1o;
+        if ((!s2_in_cell2 && !w.S2) || (!s.pre1 && h1_alias && !w.state_tmp) || (fused_attn && (!w.AFU || !w.ATS))) return XG_EINVAL;   // (carve_step_scratch)
         // ---- launch 1: what the attention and cell 1 wait for (jobs that gather come first: the index load is one more
         // dependent round trip)
         // Job order is dispatch order, and with two workgroups per CU resident at once a CU ends up with tile c of the first 256
@@ -800,6 +820,7 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
         return XG_OK;
     }
     // generic path (R not a multiple of 8): plain GEMMs + pointwise cell kernels
+    if (!w.S || !w.S2) return XG_EINVAL;
     if (!s.pre1) {
         XG_TRY(xgk_linear(st, w.gm, B, R, E, s.xt, E, p.dgate_w, p.dgate_b, s.gp, R, true));
         XG_TRY(xgk_gate_fwd(st, s.gp, R, s.pos, R, 0, s.posg, R, B, R, xg_make_drop(&run, XG_SITE_DGATE, s.t), B, 1 << 30, 1, B));
@@ -848,6 +869,7 @@ int decoder_fwd_xe(Streams& ss, const XgDims& d, const XgParams& p, const XgBatc
     hipStream_t st = ss.main;
     const int B = d.B, R = d.R, T = d.T;
     const size_t BR = (size_t)B * R;
+    if (!step_scratch_ok(w, false, false)) return XG_EINVAL;
     XG_TRY(init_and_vproj(ss, d, p, x.feat_mask, w));
     XG_TRY(zero_dsync(st, w));
     XG_TRY(ss.join());                                                                              // token-side products
@@ -1467,7 +1489,7 @@ extern "C" int xg_step_fwd(void* stream, const XgDims* d, const XgParams* p, con
     hipStream_t st = (hipStream_t)stream;
     const int B = d->B, R = d->R, E = d->E;
     const size_t BR = (size_t)B * R;
-    if ((uintptr_t)state % 16) return XG_EINVAL;
+    if ((uintptr_t)state % 16 || !step_scratch_ok(w, true, false)) return XG_EINVAL;
     StepIO s{};
     s.pos = pos_feats; s.gp = w.GP; s.posg = w.POSG; s.pre1 = nullptr; s.mask = xt_mask; s.ldm = 1;
     s.h1o = state; s.c1o = state + BR; s.h2o = state + 2 * BR; s.c2o = state + 3 * BR;
@@ -1598,13 +1620,12 @@ extern "C" int xg_forward_ss(void* stream, const XgDims* d, const XgParams* p, c
     Ws w; XG_TRY(open_ws(d, ws, ws_bytes, run, &w));
     if (!p || !x || !logp || !x->seq || !x->seq_mask || !x->pos_feats) return XG_EINVAL;
     const bool ss = run->train && ss_prob > 0.f;
-    if (ss && (!u_sel || !u_tok)) return XG_EINVAL;
+    if ((ss && (!u_sel || !u_tok)) || !step_scratch_ok(w, false, false)) return XG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int B = d->B, R = d->R, E = d->E, T = d->T, TB = T * B;
     const size_t BR = (size_t)B * R;
     Streams es(st, run);
-    XG_TRY(encoder_fwd(st, *d, *p, bn, *x, *run, w, &es));
-    XG_TRY(init_and_vproj(es, *d, *p, x->feat_mask, w));
+    XG_TRY(encode_and_init(es, *d, *p, bn, *x, *run, w));
     XG_TRY(zero_dsync(st, w));
     int64_t* sampled = reinterpret_cast<int64_t*>(w.DXe);       // scratch (free until the backward pass)
     for (int t = 0; t < T; ++t) {
@@ -1681,58 +1702,81 @@ extern "C" int xg_xe_loss_bwd(void* stream, const XgDims* d, const XgParams* p, 
     return backward_tail(ss, *d, *d, *p, *g, *x, *run, w, cls, &xent, x->seq_mask, T, 1, x->seq, T, 1);
 }
 
-// One rollout over d.B rows.  split < d.B (SAMPLE mode only): rows [0, split) sample with uniforms (T, split), rows
-// [split, B) decode greedily -- the SCST pair (starttrain.py:131 + myutils.py:45) as ONE batch; n_steps then has two entries.
-// logits_alt (paired rollout whose sampled half will be compacted for the backward): the raw logits of rows [0, split) go there,
-// (T - 1) blocks of `split` rows, instead of into this workspace -- they are two thirds of what a compaction would copy.  Only the
-// tile-statistics path writes row subsets: *used_alt tells the caller whether it happened.
-// shared (paired rollout over the SAME videos, xg_rollout_pair_videos): `x` holds the d1->B = B / 2 videos once; the encoder,
-// v2a(V) and the initial state are computed ONCE, in the workspace `enc` of the un-repeated batch (where the backward of the
-// sampled half reads them), and row-repeated into this workspace for the 2m-row decoder loop -- half the encoder work of the
-// repeated batch, no repeated inputs, and BatchNorm sees the m-row batch exactly as the reference's two sample() calls do
-// (two running-statistics updates with the same batch statistics, SAModel.py:169 called twice: starttrain.py:131, myutils.py:45).
+// Once per call on the B videos of `x` (dims de), in `enc`: the encoder, the initial state and v2a(V); then the four state tensors go to
+// each video's `rep` rows (state[k]: h1, c1, h2, c2) in ONE repeat launch, behind whatever entries the caller put into `ra`.
+static int videos_once(Streams& es, const XgDims& de, const XgParams& p, const XgBnState* bn, const XgBatch& x, const XgRun& run,
+                       Ws& enc, CapBeamRepeatArgs ra, float* const state[4], int rep) {
+    XG_TRY(encode_and_init(es, de, p, bn, x, run, enc));
+    const float* src[4] = {enc.H1, enc.C1, enc.H2, enc.C2};
+    for (int k = 0; k < 4; ++k) ra.e[ra.n++] = CapBeamRepeatEntry{state[k], src[k], (int64_t)de.R};
+    return xgk_cap_beam_repeat(es.main, ra, de.B, rep);
+}
+
+// One rollout over d.B rows, as its caller describes it.  The form picks the prologue, which leaves the initial state in block 0 of
+// w.H1 / C1 / H2 / C2.  Plain: `x` holds the d.B rows, everything runs in `w` (encode_and_init).  PairVideos: rollout_open_pair_videos.
+// RowsPerVideo (xgcc_rollout; videos_once): `x` holds the d1->B = d.B / rows_per_video videos once and pos_feats per row.  Only the
+// initial state is repeated, every step's attention reads enc's V and v2a(V) at row / S.  `w` is the row part of cc_carve: every
+// per-step tensor is ONE block that each step overwrites (slot() below), the state alternates between two blocks.
+enum class RolloutForm { Plain, PairVideos, RowsPerVideo };
+struct RolloutCall {
+    int mode = XG_ROLLOUT_GREEDY;
+    const float* uniforms = nullptr; const int64_t* forced = nullptr; float temperature = 1.0f;
+    // split < d.B (SAMPLE mode only): rows [0, split) sample with uniforms (T, split), rows [split, B) decode greedily -- the SCST pair
+    // (starttrain.py:131 + myutils.py:45) as ONE batch (pair_call); n_steps then has two entries.
+    int split = 0;
+    // logits_alt (paired rollout whose sampled half will be compacted for the backward): the raw logits of rows [0, split) go there,
+    // (T - 1) blocks of `split` rows, instead of into this workspace -- they are two thirds of what a compaction would copy.  Only the
+    // tile-statistics path writes row subsets: used_alt (set by rollout_impl) tells the caller whether it happened.
+    float* logits_alt = nullptr; bool used_alt = false;
+    RolloutForm form = RolloutForm::Plain;
+    const XgDims* d1 = nullptr; Ws* enc = nullptr;      // PairVideos, RowsPerVideo: the videos' dims and the workspace their encoder runs in
+    int rows_per_video = 0;                             // RowsPerVideo
+};
+static RolloutCall pair_call(const float* uniforms, float temperature, int n_sample, float* logits_alt = nullptr) {
+    RolloutCall c;
+    c.mode = XG_ROLLOUT_SAMPLE; c.uniforms = uniforms; c.temperature = temperature; c.split = n_sample; c.logits_alt = logits_alt;
+    return c;
+}
+
+// `x` holds the d1.B = d.B / 2 videos once.  The encoder, v2a(V) and the initial state are computed ONCE, in `enc` (the workspace of the
+// un-repeated batch, where the backward of the sampled half reads them), and row-repeated into `w` for the 2m-row decoder loop -- half
+// the encoder work of the repeated batch, no repeated inputs, and BatchNorm sees the m-row batch exactly as the reference's two
+// sample() calls do (two running-statistics updates with the same batch statistics, SAModel.py:169 called twice: starttrain.py:131,
+// myutils.py:45).  The loop reads pos_feats from w.DPOSG.
+static int rollout_open_pair_videos(Streams& es, const XgDims& d1, const XgParams& p, const XgBnState* bn, const XgBatch& x,
+                                    const XgRun& run, Ws& w, Ws& enc) {
+    hipStream_t st = es.main;
+    const size_t B1 = d1.B, N1 = B1 * d1.K, R = d1.R;
+    XG_TRY(encoder_fwd(st, d1, p, bn, x, run, enc, &es));
+    if (run.train && bn && bn->rgb_mean && bn->rgb_var && bn->opfl_mean && bn->opfl_var) {      // the second sample() call's update
+        XG_TRY(xgk_bn_running(st, enc.bn_mean[0], enc.bn_var[0], bn->rgb_mean, bn->rgb_var, (int)N1, d1.R, run.bn_momentum));
+        XG_TRY(xgk_bn_running(st, enc.bn_mean[1], enc.bn_var[1], bn->opfl_mean, bn->opfl_var, (int)N1, d1.R, run.bn_momentum));
+    }
+    XG_TRY(init_and_vproj(es, d1, p, x.feat_mask, enc));
+    CompactArgs ca{};
+    auto twice = [&](float* dst, const float* src, size_t n) {
+        for (int h = 0; h < 2; ++h) ca.e[ca.n++] = CompactEntry{dst + h * n, src, (int64_t)n, (int64_t)n, (int64_t)n};
+    };
+    twice(w.Venc, enc.Venc, N1 * R); twice(w.vproj, enc.vproj, N1 * d1.A);
+    twice(w.H1, enc.H1, B1 * R); twice(w.C1, enc.C1, B1 * R); twice(w.H2, enc.H2, B1 * R); twice(w.C2, enc.C2, B1 * R);
+    twice(w.DPOSG, x.pos_feats, B1 * R);          // (a backward-only buffer: this workspace never runs a backward)
+    return xgk_compact(st, ca);
+}
+
 static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, const XgBnState* bn, const XgBatch* x,
-                        const XgRun* run, int mode, const float* uniforms, const int64_t* forced, float temperature, Ws& w,
-                        int64_t* seq, float* seq_logp, int32_t* n_steps, int split, float* logits_alt = nullptr,
-                        bool* used_alt = nullptr, const XgDims* d1 = nullptr, Ws* enc = nullptr, int rows_per_video = 0) {
-    const int B = d->B, R = d->R, E = d->E, A = d->A, T = d->T;
+                        const XgRun* run, Ws& w, int64_t* seq, float* seq_logp, int32_t* n_steps, RolloutCall& c) {
+    const int B = d->B, R = d->R, E = d->E, T = d->T, mode = c.mode, split = c.split;
     Streams es(st, run);
-    const float* pos_rows = x->pos_feats;
-    // rows_per_video = S > 0 (xgcc_rollout): `x` holds the d1->B = B / S videos once and pos_feats per row.  The encoder, v2a(V) and
-    // the initial state are computed once in `enc`, only the initial state is repeated, and every step's attention reads enc's V and
-    // v2a(V) at row / S.  `w` is then the row part of cc_carve: every per-step tensor is ONE block that each step overwrites (slot()
-    // below), the state alternates between two blocks.
-    const bool rows = rows_per_video > 0;
-    const float *Vsrc = rows ? enc->Venc : w.Venc, *vproj_src = rows ? enc->vproj : w.vproj;
+    const bool rows = c.form == RolloutForm::RowsPerVideo;
+    if ((c.form != RolloutForm::Plain && (!c.d1 || !c.enc)) || rows != (c.rows_per_video > 0) || !step_scratch_ok(w, false, rows)) return XG_EINVAL;
+    float* const state0[4] = {w.H1, w.C1, w.H2, w.C2};
+    const float* pos_rows = c.form == RolloutForm::PairVideos ? w.DPOSG : x->pos_feats;
+    const float *Vsrc = rows ? c.enc->Venc : w.Venc, *vproj_src = rows ? c.enc->vproj : w.vproj;
     auto slot = [&](int t) { return rows ? 0 : t; };
-    if (rows) {
-        XG_TRY(encoder_fwd(st, *d1, *p, bn, *x, *run, *enc, &es));
-        XG_TRY(init_and_vproj(es, *d1, *p, x->feat_mask, *enc));
-        CapBeamRepeatArgs ra{};
-        auto rep = [&](float* dst, const float* src) { ra.e[ra.n++] = CapBeamRepeatEntry{dst, src, (int64_t)R}; };
-        rep(w.H1, enc->H1); rep(w.C1, enc->C1); rep(w.H2, enc->H2); rep(w.C2, enc->C2);
-        XG_TRY(xgk_cap_beam_repeat(st, ra, d1->B, rows_per_video));
-    } else if (enc) {
-        const size_t B1 = d1->B, N1 = B1 * d->K;
-        XG_TRY(encoder_fwd(st, *d1, *p, bn, *x, *run, *enc, &es));
-        if (run->train && bn && bn->rgb_mean && bn->rgb_var && bn->opfl_mean && bn->opfl_var) {      // the second sample() call's update
-            XG_TRY(xgk_bn_running(st, enc->bn_mean[0], enc->bn_var[0], bn->rgb_mean, bn->rgb_var, (int)N1, R, run->bn_momentum));
-            XG_TRY(xgk_bn_running(st, enc->bn_mean[1], enc->bn_var[1], bn->opfl_mean, bn->opfl_var, (int)N1, R, run->bn_momentum));
-        }
-        XG_TRY(init_and_vproj(es, *d1, *p, x->feat_mask, *enc));
-        CompactArgs ca{};
-        auto twice = [&](float* dst, const float* src, size_t n) {
-            ca.e[ca.n++] = CompactEntry{dst, src, (int64_t)n, (int64_t)n, (int64_t)n};
-            ca.e[ca.n++] = CompactEntry{dst + n, src, (int64_t)n, (int64_t)n, (int64_t)n};
-        };
-        twice(w.Venc, enc->Venc, N1 * R); twice(w.vproj, enc->vproj, N1 * A);
-        twice(w.H1, enc->H1, B1 * R); twice(w.C1, enc->C1, B1 * R); twice(w.H2, enc->H2, B1 * R); twice(w.C2, enc->C2, B1 * R);
-        twice(w.DPOSG, x->pos_feats, B1 * R);          // (a backward-only buffer: this workspace never runs a backward)
-        XG_TRY(xgk_compact(st, ca));
-        pos_rows = w.DPOSG;
-    } else {
-        XG_TRY(encoder_fwd(st, *d, *p, bn, *x, *run, w, &es));
-        XG_TRY(init_and_vproj(es, *d, *p, x->feat_mask, w));
+    switch (c.form) {
+    case RolloutForm::Plain: XG_TRY(encode_and_init(es, *d, *p, bn, *x, *run, w)); break;
+    case RolloutForm::PairVideos: XG_TRY(rollout_open_pair_videos(es, *c.d1, *p, bn, *x, *run, w, *c.enc)); break;
+    case RolloutForm::RowsPerVideo: XG_TRY(videos_once(es, *c.d1, *p, bn, *x, *run, *c.enc, CapBeamRepeatArgs{}, state0, c.rows_per_video)); break;
     }
     XG_TRY(zero_dsync(st, w));
     if (hipMemsetAsync(w.alive, 0, sizeof(int32_t) * 4, st) != hipSuccess) return XG_EHIP;   // alive[i] = running max finishing step
@@ -1744,9 +1788,8 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
     static const bool no_fused_select = xg_diag_env("XG_NO_FUSED_SELECT") != nullptr;
     const bool fused_select = !no_fused_select && w.gm == 0 && xgk_vocab_select_ok(B, R, d->V, w.H2, R, p->logit_w);
     const int wr_rows = mode == XG_ROLLOUT_SAMPLE ? split : ((mode == XG_ROLLOUT_REPLAY || run->save) ? B : 0);
-    const bool alt = logits_alt != nullptr && fused_select && mode == XG_ROLLOUT_SAMPLE && split < B;
-    if (used_alt) *used_alt = alt;
-    auto logits_of = [&](int t) { return alt ? logits_alt + (size_t)t * split * d->V : w.LOGITS + (size_t)slot(t) * B * d->V; };
+    const bool alt = c.used_alt = c.logits_alt != nullptr && fused_select && mode == XG_ROLLOUT_SAMPLE && split < B;
+    auto logits_of = [&](int t) { return alt ? c.logits_alt + (size_t)t * split * d->V : w.LOGITS + (size_t)slot(t) * B * d->V; };
     // Steps t >= 1 on the packed fp32 path CHOOSE their tokens themselves: the choice is the prologue of the step's first launch
     // (its POS-gate tiles: xg_step.hip SEL, xg_select.h) instead of a launch of its own between the vocabulary product and the step
     // -- four dependent launches per step instead of five.  The last choice of a rollout (no step follows) keeps its launch.
@@ -1760,9 +1803,9 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
         // token choice from the previous step's raw logits + bookkeeping + embedding gather: one launch (:183-215)
         const bool in_step = step_select && t >= 1 && t + 1 < T;
         // (nothing was chosen before t = 1: no forced token, no log-sum-exp row; no `unfinished` row before t = 2)
-        const RollStepArgs ra{prev_logits, uniforms ? uniforms + (size_t)t * split : nullptr, (forced && t >= 1) ? forced + (t - 1) : nullptr,
+        const RollStepArgs ra{prev_logits, c.uniforms ? c.uniforms + (size_t)t * split : nullptr, (c.forced && t >= 1) ? c.forced + (t - 1) : nullptr,
                               T - 1, t >= 2 ? unf - B : nullptr, p->embed_w, tok, w.TOKLP + (size_t)t * B, unf,
-                              t >= 1 ? w.LSE + (size_t)(t - 1) * B : nullptr, seq, seq_logp, w.alive, xt, temperature, d->V, E, t, T, mode, split};
+                              t >= 1 ? w.LSE + (size_t)(t - 1) * B : nullptr, seq, seq_logp, w.alive, xt, c.temperature, d->V, E, t, T, mode, split};
         RollSelectArgs sel{};
         if (in_step) sel = xgk_roll_select_args(ra, w.VPART);
         else if (t >= 1 && fused_select) XG_TRY(xgk_roll_select(st, B, ra, w.VPART));
@@ -1773,7 +1816,7 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
             const size_t in = (size_t)(t & 1) * B * R, out = (size_t)((t + 1) & 1) * B * R;
             s.h1 = w.H1 + in; s.c1 = w.C1 + in; s.h2 = w.H2 + in; s.c2 = w.C2 + in;
             s.h1o = w.H1 + out; s.c1o = w.C1 + out; s.h2o = w.H2 + out; s.c2o = w.C2 + out;
-            s.g1 = nullptr; s.g2 = nullptr; s.t = t; s.rows_per_video = rows_per_video;
+            s.g1 = nullptr; s.g2 = nullptr; s.t = t; s.rows_per_video = c.rows_per_video;
         }
         if (in_step) { s.sel = &sel; s.xt = nullptr; s.tok = tok; }
         // The reference runs the core once more at t = L and discards what it computes (SAModel.py:182,217: the loop ends before
@@ -1783,7 +1826,7 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
         if (t + 1 < T) {
             if (fused_select)
                 XG_TRY(xgk_vocab_part(st, B, R, d->V, s.h2o, R, p->logit_w, p->logit_b, logits_of(t), wr_rows,
-                                      w.VPART, temperature > 0.f ? temperature : 1.0f));
+                                      w.VPART, c.temperature > 0.f ? c.temperature : 1.0f));
             else
                 XG_TRY(xgk_linear(st, w.gm, B, d->V, R, s.h2o, R, p->logit_w, p->logit_b, logits_of(t), d->V));
         }
@@ -1803,7 +1846,9 @@ extern "C" int xg_rollout(void* stream, const XgDims* d, const XgParams* p, cons
     if (!p || !x || !seq || !seq_logp || !n_steps || !x->pos_feats || d->T < 2) return XG_EINVAL;
     if (mode == XG_ROLLOUT_SAMPLE && (!uniforms || !(temperature > 0.f))) return XG_EINVAL;
     if (mode == XG_ROLLOUT_REPLAY && !forced) return XG_EINVAL;
-    return rollout_impl((hipStream_t)stream, d, p, bn, x, run, mode, uniforms, forced, temperature, w, seq, seq_logp, n_steps, d->B);
+    RolloutCall c;
+    c.mode = mode; c.uniforms = uniforms; c.forced = forced; c.temperature = temperature; c.split = d->B;
+    return rollout_impl((hipStream_t)stream, d, p, bn, x, run, w, seq, seq_logp, n_steps, c);
 }
 
 extern "C" int xg_rollout_pair(void* stream, const XgDims* d2, const XgParams* p, const XgBnState* bn, const XgBatch* x2,
@@ -1811,8 +1856,8 @@ extern "C" int xg_rollout_pair(void* stream, const XgDims* d2, const XgParams* p
                                size_t ws2_bytes, int64_t* seq, float* seq_logp, int32_t* n_steps) {
     Ws w; XG_TRY(open_ws(d2, ws2, ws2_bytes, run, &w));
     if (!pair_args_ok(d2, p, x2, run, n_sample, uniforms, temperature, seq, seq_logp, n_steps)) return XG_EINVAL;
-    return rollout_impl((hipStream_t)stream, d2, p, bn, x2, run, XG_ROLLOUT_SAMPLE, uniforms, nullptr, temperature, w, seq,
-                        seq_logp, n_steps, n_sample);
+    RolloutCall c = pair_call(uniforms, temperature, n_sample);
+    return rollout_impl((hipStream_t)stream, d2, p, bn, x2, run, w, seq, seq_logp, n_steps, c);
 }
 
 // Everything xg_rollout_bwd reads, for the FIRST d1->B rows of a rollout that ran over d2->B >= d1->B rows: encoder-side
@@ -1876,10 +1921,9 @@ extern "C" int xg_rollout_pair_compact(void* stream, const XgDims* d2, const XgP
     XG_TRY(check(d1, ws1, ws1_bytes, &b));
     if (!pair_args_ok(d2, p, x2, run, n_sample, uniforms, temperature, seq, seq_logp, n_steps) || n_sample != d1->B) return XG_EINVAL;
     attach_packed(w, *d2, run);
-    bool used_alt = false;
-    XG_TRY(rollout_impl((hipStream_t)stream, d2, p, bn, x2, run, XG_ROLLOUT_SAMPLE, uniforms, nullptr, temperature, w, seq, seq_logp,
-                        n_steps, n_sample, b.LOGITS, &used_alt));
-    return compact_impl((hipStream_t)stream, d2, w, d1, b, used_alt);
+    RolloutCall c = pair_call(uniforms, temperature, n_sample, b.LOGITS);
+    XG_TRY(rollout_impl((hipStream_t)stream, d2, p, bn, x2, run, w, seq, seq_logp, n_steps, c));
+    return compact_impl((hipStream_t)stream, d2, w, d1, b, c.used_alt);
 }
 
 extern "C" int xg_rollout_pair_videos(void* stream, const XgDims* d2, const XgParams* p, const XgBnState* bn, const XgBatch* x1,
@@ -1893,47 +1937,55 @@ extern "C" int xg_rollout_pair_videos(void* stream, const XgDims* d2, const XgPa
     if (!x1->feats_rgb || !x1->feats_opfl || !x1->feat_mask || d2->B != 2 * d1->B || ws1 == ws2 || !same_model_dims(d1, d2)) return XG_EINVAL;
     attach_packed(w, *d2, run);
     attach_packed(b, *d1, run);
-    bool used_alt = false;
-    XG_TRY(rollout_impl((hipStream_t)stream, d2, p, bn, x1, run, XG_ROLLOUT_SAMPLE, uniforms, nullptr, temperature, w, seq, seq_logp,
-                        n_steps, d1->B, compact ? b.LOGITS : nullptr, &used_alt, d1, &b));
-    if (!compact) return XG_OK;
-    return compact_impl((hipStream_t)stream, d2, w, d1, b, used_alt, true);
+    RolloutCall c = pair_call(uniforms, temperature, d1->B, compact ? b.LOGITS : nullptr);
+    c.form = RolloutForm::PairVideos; c.d1 = d1; c.enc = &b;
+    XG_TRY(rollout_impl((hipStream_t)stream, d2, p, bn, x1, run, w, seq, seq_logp, n_steps, c));
+    return compact ? compact_impl((hipStream_t)stream, d2, w, d1, b, c.used_alt, true) : XG_OK;
 }
 
-// ================================================================== the captioner's beam search (include/xgate_beam.h)
-// The W most likely captions of each of d->B videos, rows b W + slot.  The encoder, init_hidden and v2a(V) run ONCE on the B videos
-// (in the `enc` part of the workspace) and are row-repeated for the M = B W rows of the decoder loop.  A step is core_step from one
-// state buffer into the other, the vocabulary product, cap_beam_topw_kernel (log-sum-exp and the W best of every row; no (M,V)
-// log-softmax) and cap_beam_merge_kernel, which also permutes the state back into the first buffer: six launches, no host step.
+// ================================================================== the captioner's device searches
+// Beam search (include/xgate_beam.h): the W most likely captions of each of d->B videos, rows b W + slot.  The encoder, init_hidden and
+// v2a(V) run ONCE on the B videos (in the `enc` part of the workspace) and are row-repeated for the M = B W rows of the decoder loop.
+// A step is core_step from one state buffer into the other, the vocabulary product, cap_beam_topw_kernel (log-sum-exp and the W best
+// of every row; no (M,V) log-softmax) and cap_beam_merge_kernel, which also permutes the state back into the first buffer: six
+// launches, no host step.  The rollout under S templates per video (include/xgate_control.h) is rollout_impl in its rows form.
 namespace {
 
-struct BeamWs {
-    Ws enc;                        // the B videos: encoder, initial state, v2a(V)   (a whole workspace at T = 1)
-    Ws step;                       // what core_step touches, over M rows (every other field stays null)
+// What both searches' workspaces begin with (search_carve); each appends its own.
+struct SearchWs {
+    Ws enc;                        // the B videos: encoder, initial state, v2a(V)   (a whole workspace at T = 1, fp32 only)
+    Ws step;                       // the M rows: the step scratch, ONE block per per-step tensor, and what the search appends
+    size_t bytes;
+};
+struct BeamWs : SearchWs {
     float *Venc, *vproj, *pos;     // row-repeated (M,K,R), (M,K,A), (M,R); the first two only when S == 0
     float* st[2][4];               // h1, c1, h2, c2 (M,R): [0] read by the step, [1] written by it
     float* topv; int32_t* topi;    // (M,W) every row's W best of the step
     BeamBook<int64_t> book;
-    size_t bytes;
 };
 
 inline XgDims beam_dims(const XgDims& d, int B) { XgDims e = d; e.B = B; e.T = 1; return e; }
+
+// The shared head over M step rows; the returned carver stands behind it.  whole_scratch: carve_step_scratch
+Carver search_carve(const XgDims& d, size_t M, bool whole_scratch, void* base, SearchWs& w) {
+    w.enc = carve(beam_dims(d, d.B), base);
+    w.enc.sh16 = nullptr; w.enc.bytes = w.enc.core_bytes;          // fp32 only: no bf16 mirror region
+    Carver c{static_cast<char*>(base), w.enc.core_bytes};
+    const size_t K = d.K, R = d.R, A = d.A, E = d.E, V = d.V;
+    Ws& s = w.step;
+    carve_step_scratch(c, s, M, R, whole_scratch);
+    s.Xe = c.take<float>(M * E); s.GP = c.take<float>(M * R); s.POSG = c.take<float>(M * R);
+    s.P = c.take<float>(M * A); s.ALPHA = c.take<float>(M * K); s.AF = c.take<float>(M * R);
+    s.LOGITS = c.take<float>(M * V);                               // one step's raw logits
+    return c;
+}
 
 // S == 0: xgcb_beam_search, one group of W rows per video.  S >= 1: xgbc_beam_search (include/xgate_beam_control.h), G = B S groups of
 // W rows, a video's S W rows share its V and v2a(V) in the per-video part: no (M,K,R) or (M,K,A) block.
 BeamWs beam_carve(const XgDims& d, int S, int W, void* base) {
     BeamWs w{};
-    w.enc = carve(beam_dims(d, d.B), base);
-    w.enc.sh16 = nullptr; w.enc.bytes = w.enc.core_bytes;          // fp32 only: no bf16 mirror region
-    Carver c{static_cast<char*>(base), w.enc.core_bytes};
-    const size_t G = (size_t)d.B * (S > 0 ? S : 1), M = G * W, K = d.K, R = d.R, A = d.A, E = d.E, V = d.V, L = d.T - 1;
-    Ws& s = w.step;
-    s.S = c.take<float>(M * 4 * R); s.S2 = c.take<float>(M * 4 * R); s.state_tmp = c.take<float>(4 * M * R);
-    s.AFU = c.take<float>(M * R + ((M + 3) & ~(size_t)3)); s.ATS = s.AFU + M * R;
-    s.Xe = c.take<float>(M * E); s.GP = c.take<float>(M * R); s.POSG = c.take<float>(M * R);
-    s.P = c.take<float>(M * A); s.ALPHA = c.take<float>(M * K); s.AF = c.take<float>(M * R);
-    s.LOGITS = c.take<float>(M * V);
-    s.dsync = c.take<int32_t>(XGK_DSTEP_SYNC_BYTES / sizeof(int32_t));
+    const size_t G = (size_t)d.B * (S > 0 ? S : 1), M = G * W, K = d.K, R = d.R, A = d.A, L = d.T - 1;
+    Carver c = search_carve(d, M, true, base, w);      // (S == 0 may take the fused attention; both forms carve alike)
     if (S == 0) { w.Venc = c.take<float>(M * K * R); w.vproj = c.take<float>(M * K * A); }
     w.pos = c.take<float>(M * R);
     for (int i = 0; i < 2; ++i) for (int k = 0; k < 4; ++k) w.st[i][k] = c.take<float>(M * R);
@@ -1943,22 +1995,45 @@ BeamWs beam_carve(const XgDims& d, int S, int W, void* base) {
     return w;
 }
 
+// The row part holds what the step loop touches and nothing of size (M,K,.).  The step never updates the state in place (two blocks
+// per state tensor) and rows_per_video = S > 0 keeps it off the fused attention: the smaller scratch.
+SearchWs cc_carve(const XgDims& d, int S, void* base) {
+    SearchWs w{};
+    const size_t M = (size_t)d.B * S, R = d.R, V = d.V, T = d.T;
+    Carver c = search_carve(d, M, false, base, w);
+    Ws& s = w.step;
+    s.H1 = c.take<float>(2 * M * R); s.C1 = c.take<float>(2 * M * R); s.H2 = c.take<float>(2 * M * R); s.C2 = c.take<float>(2 * M * R);
+    s.TOK = c.take<int64_t>(T * M); s.TOKLP = c.take<float>(T * M); s.UNF = c.take<float>(T * M); s.LSE = c.take<float>(T * M);
+    s.alive = c.take<int32_t>(4);
+    s.VPART = c.take<float>(M * ((V + 31) / 32 + 16) * 4);         // per-tile row statistics (row pitch: xg_select.h rs_pitch)
+    w.bytes = (c.off + 255) & ~(size_t)255;
+    return w;
+}
+
 bool beam_dims_ok(const XgDims* d, int S, int W, int suppress) {
     if (!dims_ok(d) || d->T < 2 || S < 0) return false;
     if (W < 1 || W > XGCB_MAX_BEAM || W > d->V || suppress >= d->V) return false;
     return (int64_t)d->B * (S > 0 ? S : 1) * W <= (1 << 20);       // (row indices and launch grids stay far inside int)
 }
+bool cc_dims_ok(const XgDims* d, int S) { return S >= 1 && beam_dims_ok(d, S, 1, -1); }       // (B S rows: one beam per template)
 
-// Both searches (S as in beam_carve).  Once per call on the B videos: encoder, init_hidden, v2a(V); then the initial state goes to
-// each video's rows and pos_feats to each group's W slots; V and v2a(V) are row-repeated for S == 0 only.  With S >= 1 core_step is
-// told the rows per video (the stand-alone group attention over the per-video V / v2a(V)) and the selection is the threshold form.
-int beam_search_impl(void* stream, const XgDims* d, int S, int W, int32_t suppress_token, const XgParams* p, const XgBnState* bn,
-                     const XgBatch* x, const XgRun* run, int64_t* seq, float* seq_logp, float* score, int32_t* trace, void* ws,
-                     size_t ws_bytes) {
-    if (!beam_dims_ok(d, S, W, suppress_token) || !p || !x || !run || !seq || !seq_logp || !score || !ws) return XG_EINVAL;
+// What the device searches refuse alike, before they carve (dims: the search's own test of its dims; out3: its third output)
+int search_args(bool dims, const XgParams* p, const XgBnState* bn, const XgBatch* x, const XgRun* run, const void* seq,
+                const void* seq_logp, const void* out3, const void* ws) {
+    if (!dims || !p || !x || !run || !seq || !seq_logp || !out3 || !ws) return XG_EINVAL;
     if (!bn || !bn->rgb_mean || !bn->rgb_var || !bn->opfl_mean || !bn->opfl_var) return XG_EINVAL;
     if (!x->feats_rgb || !x->feats_opfl || !x->feat_mask || !x->pos_feats) return XG_EINVAL;
     if (run->train || run->save || run->gemm_mode != 0 || (uintptr_t)ws % 256 != 0) return XG_EINVAL;
+    return XG_OK;
+}
+
+// Both beam searches (S as in beam_carve).  videos_once, which also takes the initial state to each video's rows; pos_feats goes to
+// each group's W slots; V and v2a(V) are row-repeated for S == 0 only.  With S >= 1 core_step is told the rows per video (the
+// stand-alone group attention over the per-video V / v2a(V)) and the selection is the threshold form.
+int beam_search_impl(void* stream, const XgDims* d, int S, int W, int32_t suppress_token, const XgParams* p, const XgBnState* bn,
+                     const XgBatch* x, const XgRun* run, int64_t* seq, float* seq_logp, float* score, int32_t* trace, void* ws,
+                     size_t ws_bytes) {
+    XG_TRY(search_args(beam_dims_ok(d, S, W, suppress_token), p, bn, x, run, seq, seq_logp, score, ws));
     BeamWs w = beam_carve(*d, S, W, ws);
     if (ws_bytes < w.bytes) return XG_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -1967,24 +2042,17 @@ int beam_search_impl(void* stream, const XgDims* d, int S, int W, int32_t suppre
     const XgDims de = beam_dims(*d, B), dm = beam_dims(*d, M);
     attach_packed(w.enc, de, run);
     attach_packed(w.step, dm, run);
-    // ---- once per call, on the B videos
+    if (!step_scratch_ok(w.step, false, shared)) return XG_EINVAL;
     Streams es(st, run);
-    XG_TRY(encoder_fwd(st, de, *p, bn, *x, *run, w.enc, &es));
-    XG_TRY(init_and_vproj(es, de, *p, x->feat_mask, w.enc));
-    {
-        CapBeamRepeatArgs ra{};
-        auto rep = [&](float* dst, const float* src, size_t n) { ra.e[ra.n++] = CapBeamRepeatEntry{dst, src, (int64_t)n}; };
-        if (!shared) { rep(w.Venc, w.enc.Venc, (size_t)K * R); rep(w.vproj, w.enc.vproj, (size_t)K * A); rep(w.pos, x->pos_feats, R); }
-        rep(w.st[0][0], w.enc.H1, R); rep(w.st[0][1], w.enc.C1, R); rep(w.st[0][2], w.enc.H2, R); rep(w.st[0][3], w.enc.C2, R);
-        XG_TRY(xgk_cap_beam_repeat(st, ra, B, M / B));
-        if (shared) {                                     // pos_feats has a row per GROUP
-            CapBeamRepeatArgs rp{};
-            rp.e[rp.n++] = CapBeamRepeatEntry{w.pos, x->pos_feats, (int64_t)R};
-            XG_TRY(xgk_cap_beam_repeat(st, rp, G, W));
-        }
+    CapBeamRepeatArgs ra{}, rp{};
+    auto rep = [&](CapBeamRepeatArgs& r, float* dst, const float* src, size_t n) { r.e[r.n++] = CapBeamRepeatEntry{dst, src, (int64_t)n}; };
+    if (!shared) { rep(ra, w.Venc, w.enc.Venc, (size_t)K * R); rep(ra, w.vproj, w.enc.vproj, (size_t)K * A); rep(ra, w.pos, x->pos_feats, R); }
+    XG_TRY(videos_once(es, de, *p, bn, *x, *run, w.enc, ra, w.st[0], M / B));
+    if (shared) {                                         // pos_feats has a row per GROUP
+        rep(rp, w.pos, x->pos_feats, R);
+        XG_TRY(xgk_cap_beam_repeat(st, rp, G, W));
     }
-    const float* Venc = shared ? w.enc.Venc : w.Venc;
-    const float* vproj = shared ? w.enc.vproj : w.vproj;
+    const float *Venc = shared ? w.enc.Venc : w.Venc, *vproj = shared ? w.enc.vproj : w.vproj;
     XG_TRY(zero_dsync(st, w.step));
     if (hipMemsetAsync(w.book.tok, 0, sizeof(int64_t) * (size_t)M, st) != hipSuccess) return XG_EHIP;   // BOS
     CapBeamMergeArgs ma{};
@@ -2018,8 +2086,7 @@ int beam_search_impl(void* stream, const XgDims* d, int S, int W, int32_t suppre
 extern "C" int xgcb_version(void) { return XGCB_VERSION; }
 
 extern "C" size_t xgcb_workspace_bytes(const XgDims* d, int32_t W) {
-    if (!beam_dims_ok(d, 0, W, -1)) return 0;
-    return beam_carve(*d, 0, W, nullptr).bytes;
+    return beam_dims_ok(d, 0, W, -1) ? beam_carve(*d, 0, W, nullptr).bytes : 0;
 }
 
 extern "C" int xgcb_beam_search(void* stream, const XgDims* d, int32_t W, int32_t suppress_token, const XgParams* p,
@@ -2032,8 +2099,7 @@ extern "C" int xgcb_beam_search(void* stream, const XgDims* d, int32_t W, int32_
 extern "C" int xgbc_version(void) { return XGBC_VERSION; }
 
 extern "C" size_t xgbc_workspace_bytes(const XgDims* d, int32_t S, int32_t W) {
-    if (S < 1 || !beam_dims_ok(d, S, W, -1)) return 0;
-    return beam_carve(*d, S, W, nullptr).bytes;
+    return S >= 1 && beam_dims_ok(d, S, W, -1) ? beam_carve(*d, S, W, nullptr).bytes : 0;
 }
 
 extern "C" int xgbc_beam_search(void* stream, const XgDims* d, int32_t S, int32_t W, int32_t suppress_token, const XgParams* p,
@@ -2043,69 +2109,30 @@ extern "C" int xgbc_beam_search(void* stream, const XgDims* d, int32_t S, int32_
     return beam_search_impl(stream, d, S, W, suppress_token, p, bn, x, run, seq, seq_logp, score, trace, ws, ws_bytes);
 }
 
-// ================================================================== the captioner under S templates per video (include/xgate_control.h)
-// rollout_impl over M = B S rows with rows_per_video = S: the per-video part is a whole workspace at T = 1 over the B videos
-// (encoder, Venc, vproj, the initial state), the row part holds what the step loop touches and nothing of size (M,K,.).
-namespace {
-
-struct ControlWs {
-    Ws enc;                        // the B videos
-    Ws step;                       // the M rows: one block per per-step tensor, two per state tensor (every other field stays null)
-    size_t bytes;
-};
-
-ControlWs cc_carve(const XgDims& d, int S, void* base) {
-    ControlWs w{};
-    w.enc = carve(beam_dims(d, d.B), base);
-    w.enc.sh16 = nullptr; w.enc.bytes = w.enc.core_bytes;          // fp32 only: no bf16 mirror region
-    Carver c{static_cast<char*>(base), w.enc.core_bytes};
-    const size_t M = (size_t)d.B * S, K = d.K, R = d.R, A = d.A, E = d.E, V = d.V, T = d.T;
-    Ws& s = w.step;
-    s.H1 = c.take<float>(2 * M * R); s.C1 = c.take<float>(2 * M * R); s.H2 = c.take<float>(2 * M * R); s.C2 = c.take<float>(2 * M * R);
-    s.S = c.take<float>(M * 4 * R); s.S2 = c.take<float>(M * 4 * R);
-    s.Xe = c.take<float>(M * E); s.GP = c.take<float>(M * R); s.POSG = c.take<float>(M * R);
-    s.P = c.take<float>(M * A); s.ALPHA = c.take<float>(M * K); s.AF = c.take<float>(M * R);
-    s.TOK = c.take<int64_t>(T * M); s.TOKLP = c.take<float>(T * M); s.UNF = c.take<float>(T * M); s.LSE = c.take<float>(T * M);
-    s.alive = c.take<int32_t>(4);
-    s.LOGITS = c.take<float>(M * V);                               // one step's raw logits (full-logits choice; the rows a draw re-reads)
-    c.off = (c.off + 15) & ~(size_t)15;
-    s.VPART = c.take<float>(M * ((V + 31) / 32 + 16) * 4);         // per-tile row statistics (row pitch: xg_select.h rs_pitch)
-    s.dsync = c.take<int32_t>(XGK_DSTEP_SYNC_BYTES / sizeof(int32_t));
-    w.bytes = (c.off + 255) & ~(size_t)255;
-    return w;
-}
-
-bool cc_dims_ok(const XgDims* d, int S) {
-    return dims_ok(d) && d->T >= 2 && S >= 1 && (int64_t)d->B * S <= (1 << 20);
-}
-
-}  // namespace
-
+// ---- the captioner under S templates per video (include/xgate_control.h): rollout_impl over M = B S rows in its rows-per-video form
 extern "C" int xgcc_version(void) { return XGCC_VERSION; }
 
 extern "C" size_t xgcc_workspace_bytes(const XgDims* d, int32_t S) {
-    if (!cc_dims_ok(d, S)) return 0;
-    return cc_carve(*d, S, nullptr).bytes;
+    return cc_dims_ok(d, S) ? cc_carve(*d, S, nullptr).bytes : 0;
 }
 
 extern "C" int xgcc_rollout(void* stream, const XgDims* d, int32_t S, const XgParams* p, const XgBnState* bn, const XgBatch* x,
                             const XgRun* run, int mode, const float* uniforms, float temperature, int64_t* seq, float* seq_logp,
                             int32_t* n_steps, void* ws, size_t ws_bytes) {
-    if (!cc_dims_ok(d, S) || !p || !x || !run || !seq || !seq_logp || !n_steps || !ws) return XG_EINVAL;
-    if (!bn || !bn->rgb_mean || !bn->rgb_var || !bn->opfl_mean || !bn->opfl_var) return XG_EINVAL;
-    if (!x->feats_rgb || !x->feats_opfl || !x->feat_mask || !x->pos_feats) return XG_EINVAL;
-    if (run->train || run->save || run->gemm_mode != 0 || (uintptr_t)ws % 256 != 0) return XG_EINVAL;
+    XG_TRY(search_args(cc_dims_ok(d, S), p, bn, x, run, seq, seq_logp, n_steps, ws));
     if (mode != XG_ROLLOUT_GREEDY && mode != XG_ROLLOUT_SAMPLE) return XG_EINVAL;
     if (mode == XG_ROLLOUT_SAMPLE && (!uniforms || !(temperature > 0.f))) return XG_EINVAL;
-    ControlWs w = cc_carve(*d, S, ws);
+    SearchWs w = cc_carve(*d, S, ws);
     if (ws_bytes < w.bytes) return XG_EWORKSPACE;
     const int M = d->B * S;
     const XgDims de = beam_dims(*d, d->B);
     XgDims dm = *d; dm.B = M;
     attach_packed(w.enc, de, run);
     attach_packed(w.step, dm, run);
-    return rollout_impl((hipStream_t)stream, &dm, p, bn, x, run, mode, uniforms, nullptr, temperature, w.step, seq, seq_logp, n_steps,
-                        M, nullptr, nullptr, &de, &w.enc, S);
+    RolloutCall c;
+    c.mode = mode; c.uniforms = uniforms; c.temperature = temperature; c.split = M;
+    c.form = RolloutForm::RowsPerVideo; c.d1 = &de; c.enc = &w.enc; c.rows_per_video = S;
+    return rollout_impl((hipStream_t)stream, &dm, p, bn, x, run, w.step, seq, seq_logp, n_steps, c);
 }
 
 extern "C" int xg_rollout_bwd(void* stream, const XgDims* d, const XgParams* p, const XgParams* g, const XgBatch* x,

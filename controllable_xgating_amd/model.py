@@ -509,6 +509,38 @@ class SAModel(FlatParams, nn.Module):
             setattr(self, attr, {key: ws})
         return _ws_ptr(ws)
 
+    def _search_open(self, name, inputs, per_video, beam=None, refuse=()):
+        """The checks the device searches share, in one order: the gate; `refuse`, the entry point's own (condition, text) pairs;
+        the beam arguments `beam` = (W, suppress_token); the (B,S,R) shape of pos_feats (`per_video`); the gate on the tensors
+        `inputs` = (feats_rgb, feats_opfl, feat_mask, pos_feats).  Returns (B, K, S or None, L, device, dims at T = L + 1)."""
+        from ._native_beam import XGCB_MAX_BEAM
+        self._search_gate(name)
+        for cond, text in refuse:
+            if cond:
+                raise NotImplementedError(text)
+        if beam is not None:
+            W, sup = beam
+            if W < 1 or W > self.vocab_size or W > XGCB_MAX_BEAM:
+                raise ValueError("1 <= beam_size <= min(vocab_size = %d, %d) expected, got %d" % (self.vocab_size, XGCB_MAX_BEAM, W))
+            if sup >= self.vocab_size:
+                raise ValueError("suppress_token must lie below vocab_size = %d (-1: none), got %d" % (self.vocab_size, sup))
+        (B, K), pos = inputs[0].shape[:2], inputs[3]
+        if per_video and (pos.dim() != 3 or pos.shape[0] != B or pos.shape[1] < 1 or pos.shape[2] != self.rnn_size):
+            raise ValueError("pos_feats (B = %d, S, R = %d) expected, got %s" % (B, self.rnn_size, tuple(pos.shape)))
+        self._search_gate(name, *inputs)
+        L = self.seq_length
+        return B, K, int(pos.shape[1]) if per_video else None, L, inputs[0].device, self._dims(B, K, L + 1)
+
+    def _search_call(self, attr, key, nbytes, invalid, inputs):
+        """What a device search hands the library besides its own arguments and outputs: the cached workspace and the parameter,
+        BatchNorm, batch ((B,S,R) pos_feats as its B S rows) and run structs -> (those four by reference in the ABI's order,
+        workspace pointer, bytes, what has to outlive the call)."""
+        wp, wn = self._search_workspace(attr, key, nbytes, inputs[0].device, invalid)
+        with torch.no_grad():
+            b, keep = self._batch(*inputs[:3], inputs[3].reshape(-1, self.rnn_size) if inputs[3].dim() == 3 else inputs[3])
+            own = (self._params_struct(), self._bn_struct(), b, self._run(False))
+        return [C.byref(o) for o in own], wp, wn, (keep, own)
+
     def sample_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, opt={}):
         """``sample`` for S `pos_feats` rows per video on ONE encoder pass (include/xgate_control.h): the B videos are handed over
         once, `pos_feats` is (B,S,R), and the result is what ``sample`` gives on the batch with every video repeated S times, row by
@@ -519,18 +551,11 @@ class SAModel(FlatParams, nn.Module):
         (B,S,L) tensors and the device-side n).  Eval mode, fp32 and device tensors only; `beam_size` > 1 and `forced_tokens` are not
         served.  Nothing returned carries an autograd graph."""
         from . import _native_control as ncc
-        self._search_gate("sample_per_video")
-        if opt.get("beam_size", 1) > 1:
-            raise NotImplementedError("sample_per_video has no beam search: beam_size must be 1")
-        if opt.get("forced_tokens", None) is not None:
-            raise NotImplementedError("sample_per_video has no replay mode: forced_tokens must be None")
-        B, K = feats_rgb.shape[0], feats_rgb.shape[1]
-        if pos_feats.dim() != 3 or pos_feats.shape[0] != B or pos_feats.shape[1] < 1 or pos_feats.shape[2] != self.rnn_size:
-            raise ValueError("pos_feats (B = %d, S, R = %d) expected, got %s" % (B, self.rnn_size, tuple(pos_feats.shape)))
-        self._search_gate("sample_per_video", feats_rgb, feats_opfl, feat_mask, pos_feats)
-        S, L = int(pos_feats.shape[1]), self.seq_length
+        inputs = (feats_rgb, feats_opfl, feat_mask, pos_feats)
+        B, K, S, L, dev, d = self._search_open("sample_per_video", inputs, True, refuse=(
+            (opt.get("beam_size", 1) > 1, "sample_per_video has no beam search: beam_size must be 1"),
+            (opt.get("forced_tokens", None) is not None, "sample_per_video has no replay mode: forced_tokens must be None")))
         M = B * S
-        dev = feats_rgb.device
         mode = nv.XG_ROLLOUT_GREEDY if opt.get("sample_max", 1) else nv.XG_ROLLOUT_SAMPLE
         temperature = float(opt.get("temperature", 1.0))
         uniforms = opt.get("uniforms", None)
@@ -543,17 +568,13 @@ class SAModel(FlatParams, nn.Module):
         else:
             uniforms = None
         lib = ncc.lib()
-        d = self._dims(B, K, L + 1)
-        wp, wn = self._search_workspace("_control_ws", (B, K, L, S, str(dev)), lambda: lib.xgcc_workspace_bytes(C.byref(d), S), dev,
-                                        "xgcc_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S))
-        with torch.no_grad():
-            b, keep = self._batch(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(M, self.rnn_size))
-            ps, bn, run = self._params_struct(), self._bn_struct(), self._run(False)
-            seq = torch.empty(B, S, L, dtype=torch.int64, device=dev)
-            slp = torch.empty(B, S, L, dtype=torch.float32, device=dev)
-            n = torch.empty(1, dtype=torch.int32, device=dev)
-            nv.check(lib.xgcc_rollout(_stream(), C.byref(d), S, C.byref(ps), C.byref(bn), C.byref(b), C.byref(run), mode,
-                                      nv.ptr(uniforms), temperature, nv.ptr(seq), nv.ptr(slp), nv.ptr(n), wp, wn), "xgcc_rollout")
+        args, wp, wn, keep = self._search_call("_control_ws", (B, K, L, S, str(dev)), lambda: lib.xgcc_workspace_bytes(C.byref(d), S),
+                                               "xgcc_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S), inputs)
+        seq = torch.empty(B, S, L, dtype=torch.int64, device=dev)
+        slp = torch.empty(B, S, L, dtype=torch.float32, device=dev)
+        n = torch.empty(1, dtype=torch.int32, device=dev)
+        nv.check(lib.xgcc_rollout(_stream(), C.byref(d), S, *args, mode, nv.ptr(uniforms), temperature, nv.ptr(seq), nv.ptr(slp),
+                                  nv.ptr(n), wp, wn), "xgcc_rollout")
         if opt.get("async", False):
             return seq, slp, n
         n = int(n.item())
@@ -569,28 +590,17 @@ class SAModel(FlatParams, nn.Module):
         merge (the reference does this for UNK, index 1); -1 turns it off.  `return_trace`: also the (token, parent slot) of every
         slot and step.  Eval mode, fp32 and device tensors only; beam_size may not exceed vocab_size or 8."""
         from . import _native_beam as nb
-        self._search_gate("beam_captions")
-        W, sup = int(beam_size), int(suppress_token)
-        if W < 1 or W > self.vocab_size or W > nb.XGCB_MAX_BEAM:
-            raise ValueError("1 <= beam_size <= min(vocab_size = %d, %d) expected, got %d" % (self.vocab_size, nb.XGCB_MAX_BEAM, W))
-        if sup >= self.vocab_size:
-            raise ValueError("suppress_token must lie below vocab_size = %d (-1: none), got %d" % (self.vocab_size, sup))
-        self._search_gate("beam_captions", feats_rgb, feats_opfl, feat_mask, pos_feats)
-        B, K = feats_rgb.shape[0], feats_rgb.shape[1]
-        L = self.seq_length
-        dev = feats_rgb.device
+        inputs, W, sup = (feats_rgb, feats_opfl, feat_mask, pos_feats), int(beam_size), int(suppress_token)
+        B, K, _, L, dev, d = self._search_open("beam_captions", inputs, False, beam=(W, sup))
         lib = nb.lib()
-        d = self._dims(B, K, L + 1)
-        wp, wn = self._search_workspace("_beam_ws", (B, K, L, W, str(dev)), lambda: lib.xgcb_workspace_bytes(C.byref(d), W), dev,
-                                        "xgcb_workspace_bytes: invalid dims or too many rows (B %d, W %d)" % (B, W))
-        b, keep = self._batch(feats_rgb, feats_opfl, feat_mask, pos_feats)
-        ps, bn, run = self._params_struct(), self._bn_struct(), self._run(False)
+        args, wp, wn, keep = self._search_call("_beam_ws", (B, K, L, W, str(dev)), lambda: lib.xgcb_workspace_bytes(C.byref(d), W),
+                                               "xgcb_workspace_bytes: invalid dims or too many rows (B %d, W %d)" % (B, W), inputs)
         seq = torch.empty(B, W, L, dtype=torch.int64, device=dev)
         seq_logp = torch.empty(B, W, L, dtype=torch.float32, device=dev)
         score = torch.empty(B, W, dtype=torch.float32, device=dev)
         trace = torch.empty(B, L, W, 2, dtype=torch.int32, device=dev) if return_trace else None
-        nv.check(lib.xgcb_beam_search(_stream(), C.byref(d), W, sup, C.byref(ps), C.byref(bn), C.byref(b), C.byref(run),
-                                      nv.ptr(seq), nv.ptr(seq_logp), nv.ptr(score), nv.ptr(trace), wp, wn), "xgcb_beam_search")
+        nv.check(lib.xgcb_beam_search(_stream(), C.byref(d), W, sup, *args, nv.ptr(seq), nv.ptr(seq_logp), nv.ptr(score),
+                                      nv.ptr(trace), wp, wn), "xgcb_beam_search")
         out = (seq, seq_logp, score)
         return out + (trace,) if return_trace else out
 
@@ -604,34 +614,19 @@ class SAModel(FlatParams, nn.Module):
 
         `beam_size`, `suppress_token`, `return_trace` and the order of a pair's beams as in ``beam_captions``.  Eval mode, fp32 and
         device tensors only."""
-        from . import _native_beam as nb
         from . import _native_beam_control as nbc
-        self._search_gate("beam_captions_per_video")
-        W, sup = int(beam_size), int(suppress_token)
-        if W < 1 or W > self.vocab_size or W > nb.XGCB_MAX_BEAM:
-            raise ValueError("1 <= beam_size <= min(vocab_size = %d, %d) expected, got %d" % (self.vocab_size, nb.XGCB_MAX_BEAM, W))
-        if sup >= self.vocab_size:
-            raise ValueError("suppress_token must lie below vocab_size = %d (-1: none), got %d" % (self.vocab_size, sup))
-        B, K = feats_rgb.shape[0], feats_rgb.shape[1]
-        if pos_feats.dim() != 3 or pos_feats.shape[0] != B or pos_feats.shape[1] < 1 or pos_feats.shape[2] != self.rnn_size:
-            raise ValueError("pos_feats (B = %d, S, R = %d) expected, got %s" % (B, self.rnn_size, tuple(pos_feats.shape)))
-        self._search_gate("beam_captions_per_video", feats_rgb, feats_opfl, feat_mask, pos_feats)
-        S, L = int(pos_feats.shape[1]), self.seq_length
-        dev = feats_rgb.device
+        inputs, W, sup = (feats_rgb, feats_opfl, feat_mask, pos_feats), int(beam_size), int(suppress_token)
+        B, K, S, L, dev, d = self._search_open("beam_captions_per_video", inputs, True, beam=(W, sup))
         lib = nbc.lib()
-        d = self._dims(B, K, L + 1)
-        wp, wn = self._search_workspace("_beam_control_ws", (B, K, L, S, W, str(dev)),
-                                        lambda: lib.xgbc_workspace_bytes(C.byref(d), S, W), dev,
-                                        "xgbc_workspace_bytes: invalid dims or too many rows (B %d, S %d, W %d)" % (B, S, W))
-        with torch.no_grad():
-            b, keep = self._batch(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(B * S, self.rnn_size))
-            ps, bn, run = self._params_struct(), self._bn_struct(), self._run(False)
-            seq = torch.empty(B, S, W, L, dtype=torch.int64, device=dev)
-            seq_logp = torch.empty(B, S, W, L, dtype=torch.float32, device=dev)
-            score = torch.empty(B, S, W, dtype=torch.float32, device=dev)
-            trace = torch.empty(B, S, L, W, 2, dtype=torch.int32, device=dev) if return_trace else None
-            nv.check(lib.xgbc_beam_search(_stream(), C.byref(d), S, W, sup, C.byref(ps), C.byref(bn), C.byref(b), C.byref(run),
-                                          nv.ptr(seq), nv.ptr(seq_logp), nv.ptr(score), nv.ptr(trace), wp, wn), "xgbc_beam_search")
+        args, wp, wn, keep = self._search_call("_beam_control_ws", (B, K, L, S, W, str(dev)),
+                                               lambda: lib.xgbc_workspace_bytes(C.byref(d), S, W),
+                                               "xgbc_workspace_bytes: invalid dims or too many rows (B %d, S %d, W %d)" % (B, S, W), inputs)
+        seq = torch.empty(B, S, W, L, dtype=torch.int64, device=dev)
+        seq_logp = torch.empty(B, S, W, L, dtype=torch.float32, device=dev)
+        score = torch.empty(B, S, W, dtype=torch.float32, device=dev)
+        trace = torch.empty(B, S, L, W, 2, dtype=torch.int32, device=dev) if return_trace else None
+        nv.check(lib.xgbc_beam_search(_stream(), C.byref(d), S, W, sup, *args, nv.ptr(seq), nv.ptr(seq_logp), nv.ptr(score),
+                                      nv.ptr(trace), wp, wn), "xgbc_beam_search")
         out = (seq, seq_logp, score)
         return out + (trace,) if return_trace else out
 
