@@ -341,86 +341,6 @@ attn_fwd_fast(const float* __restrict__ p, const float* __restrict__ vproj, cons
 }
 
 // backward: de_k = alpha_k (dalpha_k - sum_j alpha_j dalpha_j), dalpha_k = daf . V_k ; dp_a = w_a sum_k de_k (1 - th^2)
-template <int NQ>   // q values per thread per row: thread owns a = tid*2 (+1), rows looped; NQ = ceil(K / 1) held rows
-__global__ void __launch_bounds__(FT) attn_bwd_fast(const float* __restrict__ daf, int lddaf, const float* __restrict__ p,
-                                                     const float* __restrict__ vproj, const float* __restrict__ V,
-                                                     const float* __restrict__ w, const float* __restrict__ alpha,
-                                                     float* __restrict__ de, float* __restrict__ dp, int K, int R, int A) {
-    extern __shared__ float sm[];                     // dalpha[K]
-    XG_CHAIN_PRIO();
-    AT_STAMP(0);
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* qb = vproj + (size_t)b * K * A;
-    const float* Vb = V + (size_t)b * K * R;
-    const float* dafb = daf + (size_t)b * lddaf;
-    // first needed, first requested: the dalpha operands of this wave's rows (k = wave, wave + 16, ...; R <= 1024 here)
-    constexpr int DR = 2, DC = 4;                     // rows per wave, float4 chunks per row held in registers
-    float4 dv[DC], vv[DR][DC];
-#pragma unroll
-    for (int c = 0; c < DC; ++c) {
-        const int r = lane * 4 + 256 * c;
-        dv[c] = r < R ? *reinterpret_cast<const float4*>(dafb + r) : make_float4(0, 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < DR; ++j) {
-            const int k = wave + j * FW;
-            vv[j][c] = (r < R && k < K) ? *reinterpret_cast<const float4*>(Vb + (size_t)k * R + r) : make_float4(0, 0, 0, 0);
-        }
-    }
-    const float al_lane = lane < K ? alpha[(size_t)b * K + lane] : 0.f;
-    // thread -> two consecutive attention columns; all K rows of q for them go to registers up front
-    const int a0 = tid * 2;
-    const bool a_ok = a0 < A;
-    float2 q[NQ];
-#pragma unroll
-    for (int k = 0; k < NQ; ++k) q[k] = (a_ok && k < K) ? *reinterpret_cast<const float2*>(qb + (size_t)k * A + a0) : make_float2(0, 0);
-    const float2 pa = a_ok ? *reinterpret_cast<const float2*>(p + (size_t)b * A + a0) : make_float2(0, 0);
-    const float2 wa = a_ok ? *reinterpret_cast<const float2*>(w + a0) : make_float2(0, 0);
-    AT_STAMP(1);
-#pragma unroll
-    for (int j = 0; j < DR; ++j) {
-        const int k = wave + j * FW;
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < DC; ++c)
-            acc += dv[c].x * vv[j][c].x + dv[c].y * vv[j][c].y + dv[c].z * vv[j][c].z + dv[c].w * vv[j][c].w;
-        acc = wave_sum(acc);
-        if (lane == 0 && k < K) sm[k] = acc;
-    }
-    for (int k = wave + DR * FW; k < K; k += FW) {    // K > 32: remaining rows the slow way
-        float acc = 0.f;
-        for (int r = lane * 4; r < R; r += 256) {
-            const float4 d4 = *reinterpret_cast<const float4*>(dafb + r);
-            const float4 v4 = *reinterpret_cast<const float4*>(Vb + (size_t)k * R + r);
-            acc += d4.x * v4.x + d4.y * v4.y + d4.z * v4.z + d4.w * v4.w;
-        }
-        acc = wave_sum(acc);
-        if (lane == 0) sm[k] = acc;
-    }
-    AT_STAMP(2);
-    __syncthreads();
-    AT_STAMP(3);
-    // softmax backward once per wave, lane k holding row k:  de_k = alpha_k (dalpha_k - sum_j alpha_j dalpha_j)
-    const float da = lane < K ? sm[lane] : 0.f;
-    const float dot = wave_sum(al_lane * da);
-    const float d_lane = al_lane * (da - dot);
-    if (wave == 0 && lane < K) de[(size_t)b * K + lane] = d_lane;
-    AT_STAMP(4);
-    if (a_ok) {
-        float sx = 0.f, sy = 0.f;
-#pragma unroll
-        for (int k = 0; k < NQ; ++k) {
-            if (k < K) {
-                const float dk = xg_readlane(d_lane, k);
-                const float tx = xg_tanh(pa.x + q[k].x), ty = xg_tanh(pa.y + q[k].y);
-                sx += dk * (1.0f - tx * tx);
-                sy += dk * (1.0f - ty * ty);
-            }
-        }
-        *reinterpret_cast<float2*>(dp + (size_t)b * A + a0) = make_float2(sx * wa.x, sy * wa.y);
-    }
-    AT_STAMP(5);
-}
-
 // The same backward as TWO workgroups per video (512 threads each): every thread's work is dominated by its 2 x K tanh
 // (one 1024-thread workgroup per video keeps 128 CUs busy for ~5 us of VALU each and leaves the other 128 idle), so the
 // attention columns are halved between two CUs; both compute the K dalpha dot products (V is read twice: 53 KB per video)
@@ -619,22 +539,14 @@ int xgk_attn_bwd(hipStream_t st, const float* daf, int lddaf, const float* p, co
     const bool al16 = ((uintptr_t)p % 16 == 0) && ((uintptr_t)vproj % 16 == 0) && ((uintptr_t)V % 16 == 0) &&
                       ((uintptr_t)w % 16 == 0) && ((uintptr_t)daf % 16 == 0) && ((uintptr_t)dp % 16 == 0);
     // two 512-thread workgroups per video whenever the shapes allow: up to 32 frames they hold <= 128 VGPRs, i.e. one of
-    // them fits into the half of a CU a background GEMM workgroup leaves free (xg_gemm.hip: XGK_GEMM_BG) -- the
-    // one-workgroup form (1024 threads x 125 VGPRs) needs an EMPTY CU and waited for one for up to 240 us per step beside
-    // dW_logit.  For 33-48 frames: the staged form attn_bwd_split_lr (the one-workgroup form would spill there).
+    // them fits into the half of a CU a background GEMM workgroup leaves free (xg_gemm.hip: XGK_GEMM_BG) -- a one-workgroup
+    // form (1024 threads x 125 VGPRs, removed: this condition covered every shape it took) needs an EMPTY CU and waited for one
+    // for up to 240 us per step beside dW_logit.  For 33-48 frames: the staged form attn_bwd_split_lr.
     if (al16 && A % 4 == 0 && A <= 2048 && R % 4 == 0 && R <= 1024 && lddaf % 4 == 0 && K <= 48) {
         const size_t lds = (size_t)K * sizeof(float);
         if (K <= 16) hipLaunchKernelGGL((attn_bwd_split<16>), dim3(2 * B), dim3(512), lds, st, daf, lddaf, p, vproj, V, w, alpha, de, dp, K, R, A);
         else if (K <= 32) hipLaunchKernelGGL((attn_bwd_split<32>), dim3(2 * B), dim3(512), lds, st, daf, lddaf, p, vproj, V, w, alpha, de, dp, K, R, A);
         else hipLaunchKernelGGL((attn_bwd_split_lr<48>), dim3(2 * B), dim3(512), lds, st, daf, lddaf, p, vproj, V, w, alpha, de, dp, K, R, A);
-        XG_CHECK_LAUNCH();
-        return XG_OK;
-    }
-    if (al16 && A % 4 == 0 && A <= 2 * FT && R % 4 == 0 && R <= 1024 && lddaf % 4 == 0 && K <= 48) {
-        const size_t lds = (size_t)K * sizeof(float);
-        if (K <= 16) hipLaunchKernelGGL((attn_bwd_fast<16>), dim3(B), dim3(FT), lds, st, daf, lddaf, p, vproj, V, w, alpha, de, dp, K, R, A);
-        else if (K <= 32) hipLaunchKernelGGL((attn_bwd_fast<32>), dim3(B), dim3(FT), lds, st, daf, lddaf, p, vproj, V, w, alpha, de, dp, K, R, A);
-        else hipLaunchKernelGGL((attn_bwd_fast<48>), dim3(B), dim3(FT), lds, st, daf, lddaf, p, vproj, V, w, alpha, de, dp, K, R, A);
         XG_CHECK_LAUNCH();
         return XG_OK;
     }

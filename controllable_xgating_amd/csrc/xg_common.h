@@ -135,5 +135,4 @@ static __global__ void xg_null_kernel(int) {}
 #define hipLaunchKernelGGL(kernel_, grid_, block_, lds_, stream_, ...) do { xg_null_kernel<<<dim3(1), dim3(64), 0, (stream_)>>>(0); } while (0)
 #endif
 
-static inline int xg_cdiv(int a, int b) { return (a + b - 1) / b; }
-static inline int64_t xg_cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+#include "xg_hostmath.h"      // xg_cdiv, xg_cdiv64

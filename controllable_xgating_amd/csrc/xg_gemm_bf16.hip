@@ -28,8 +28,7 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 32;
-constexpr int LDKC = BK + 8;       // k-contiguous image: row stride in bf16 (80 B)
+using namespace xgr::b16;      // BM, BN, BK, LDKC, LDMC, tr_image, plane_elems: xg_gemm_route.h (the planner sizes LDS from them)
 
 struct BArgs {
     const float* A; const float* B; float* C; const float* bias;
@@ -44,12 +43,6 @@ struct BArgs {
     float* csum[3];
 };
 
-constexpr int LDMC = BM + 16;      // [k][m] image of an m-contiguous operand: row stride in bf16 (288 B: the 4 k rows of a
-                                   // transposing read land 8 banks apart)
-// an m-contiguous operand whose rows are 16-byte loadable keeps its memory order in LDS and is transposed by the READ
-// (ds_read_b64_tr_b16); otherwise it is transposed by the thread assignment of dword loads into the k-contiguous image
-template <bool KC, bool VEC> constexpr bool tr_image() { return !KC && VEC; }
-template <bool KC, bool VEC = false> constexpr int plane_elems() { return tr_image<KC, VEC>() ? BK * LDMC : BM * LDKC; }
 typedef short v4s __attribute__((ext_vector_type(4)));
 
 // ---- fp32 -> bf16 planes
@@ -544,53 +537,6 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm_bx_kernel(BArgs g) {
         }
 }
 
-template <int TM, int TN, int WGM, int WGN, bool AKC, bool BKC>
-int launch_bx(hipStream_t st, const BArgs& g) {
-    const int ntm = xg_cdiv(g.M, TM), ntn = xg_cdiv(g.N, TN);
-    if (g.splitk > 1 && !g.accumulate) {
-        if (g.ldc == g.N) { if (hipMemsetAsync(g.C, 0, sizeof(float) * (size_t)g.M * g.N, st) != hipSuccess) return XG_EHIP; }
-        else if (hipMemset2DAsync(g.C, sizeof(float) * g.ldc, 0, sizeof(float) * g.N, g.M, st) != hipSuccess) return XG_EHIP;
-    }
-    constexpr int lds = (TM + TN) * LDKC * (int)sizeof(unsigned short);
-    hipLaunchKernelGGL((gemm_bx_kernel<TM, TN, WGM, WGN, AKC, BKC>), dim3(ntm * ntn * g.splitk), dim3(64 * WGM * WGN), lds, st, g);
-    XG_CHECK_LAUNCH();
-    return XG_OK;
-}
-template <int NP, bool AKC, bool BKC, bool VEC, bool A16 = false, bool B16 = false>
-int launch(hipStream_t st, const BArgs& g) {
-    const int ntm = xg_cdiv(g.M, BM), ntn = xg_cdiv(g.N, BN);
-    if (g.splitk > 1 && !g.accumulate) {
-        if (g.ldc == g.N) { if (hipMemsetAsync(g.C, 0, sizeof(float) * (size_t)g.M * g.N, st) != hipSuccess) return XG_EHIP; }
-        else if (hipMemset2DAsync(g.C, sizeof(float) * g.ldc, 0, sizeof(float) * g.N, g.M, st) != hipSuccess) return XG_EHIP;
-    }
-    const size_t lds = (size_t)NP * (plane_elems<AKC, VEC>() + plane_elems<BKC, VEC>()) * sizeof(unsigned short);
-    if (lds > 65536) {
-        static std::atomic<unsigned> optin{0};
-        XG_TRY(xg_lds_optin(optin, reinterpret_cast<const void*>(&gemm_bs_kernel<NP, AKC, BKC, VEC, A16, B16>), (int)lds));
-    }
-    hipLaunchKernelGGL((gemm_bs_kernel<NP, AKC, BKC, VEC, A16, B16>), dim3(ntm * ntn * g.splitk), dim3(256), lds, st, g);
-    XG_CHECK_LAUNCH();
-    return XG_OK;
-}
-
-// plain bf16 with one or both operands already bf16 in memory
-template <bool AKC, bool BKC>
-int dispatch16(hipStream_t st, const BArgs& g) {
-    if (g.A16 && g.B16) return launch<1, AKC, BKC, true, true, true>(st, g);
-    if (g.A16) return launch<1, AKC, BKC, true, true, false>(st, g);
-    return launch<1, AKC, BKC, true, false, true>(st, g);
-}
-
-template <int NP>
-int dispatch(hipStream_t st, const BArgs& g, bool akc, bool bkc, bool vec) {
-#define XG_BS(a, b) (vec ? launch<NP, a, b, true>(st, g) : launch<NP, a, b, false>(st, g))
-    if (akc && bkc) return XG_BS(true, true);
-    if (akc && !bkc) return XG_BS(true, false);
-    if (!akc && !bkc) return XG_BS(false, false);
-    return XG_BS(false, true);
-#undef XG_BS
-}
-
 // fp32 -> bf16 (round to nearest even, v_cvt_pk_bf16_f32), 8 elements per thread: two 16-byte loads, one 16-byte store
 __global__ void __launch_bounds__(256) cvt_bf16_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, size_t n8, size_t n) {
     typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -633,70 +579,30 @@ extern "C" int xg_gemm_bf16_operands(void* stream, int transA, int transB, int M
                                      int accumulate) {
     if (M <= 0 || N <= 0) return XG_OK;
     if (K < 0 || !A || !B || !C) return XG_EINVAL;
-    return xgk_gemm_bf16x((hipStream_t)stream, 1, transA != 0, transB != 0, M, N, K, A, static_cast<const unsigned short*>(A16), lda, B,
-                          static_cast<const unsigned short*>(B16), ldb, C, ldc, bias, relu != 0, accumulate != 0, nullptr, nullptr, nullptr);
+    // plain bf16 whatever the size, with optional bf16 copies of the operands (same shape, layout and leading dimension, or null)
+    return xgk_gemm_run((hipStream_t)stream, true, 1, transA != 0, transB != 0, M, N, K, lda, ldb, ldc, relu != 0, accumulate != 0,
+                        {A, B, C, bias, static_cast<const unsigned short*>(A16), static_cast<const unsigned short*>(B16), {nullptr, nullptr, nullptr}});
 }
 
-// planes: 1 = bf16 compute, 3 = split-bf16 (fp32-class accuracy).  Only called for products large enough to tile.
-int xgk_gemm_bf16(hipStream_t st, int planes, bool transA, bool transB, int M, int N, int K, const float* A, int lda,
-                  const float* B, int ldb, float* C, int ldc, const float* bias, bool relu, bool accumulate, float* cs1, float* cs2,
-                  float* cs3) {
-    return xgk_gemm_bf16x(st, planes, transA, transB, M, N, K, A, nullptr, lda, B, nullptr, ldb, C, ldc, bias, relu, accumulate, cs1, cs2, cs3);
-}
-
-// the same with optional bf16 copies of the operands (A16 / B16: same shape, layout and leading dimension as A / B, or null):
-// where one exists and is 16-byte loadable the kernel reads it instead of converting the fp32 operand on the fly
-int xgk_gemm_bf16x(hipStream_t st, int planes, bool transA, bool transB, int M, int N, int K, const float* A, const unsigned short* A16,
-                   int lda, const float* B, const unsigned short* B16, int ldb, float* C, int ldc, const float* bias, bool relu,
-                   bool accumulate, float* cs1, float* cs2, float* cs3) {
-    // (column sums are a side output of the weight-gradient layout only: transA)
-    if (cs1 && !transA) return XG_EINVAL;
-    const bool bg = (planes & XGK_GEMM_BG) != 0;      // launched beside a latency-bound chain (xg_kernels.h)
-    planes &= ~XGK_GEMM_BG;
-    BArgs g{A, B, C, bias, M, N, K, lda, ldb, ldc, relu ? 1 : 0, accumulate ? 1 : 0, 1, 1, nullptr, nullptr, {cs1, cs2, cs3}};
-    const bool akc = !transA, bkc = transB;
-    bool vec = ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && (lda % 4 == 0) && (ldb % 4 == 0);
-    vec = vec && ((akc ? K : M) % 4 == 0) && ((bkc ? K : N) % 4 == 0);
-    if (planes == 1 && vec) {      // 16-byte loads of 8 bf16: base, pitch and contiguous extent in multiples of 8 elements
-        if (A16 && (uintptr_t)A16 % 16 == 0 && lda % 8 == 0 && (akc ? K : M) % 8 == 0 && (akc ? K : M) >= 8) g.A16 = A16;
-        if (B16 && (uintptr_t)B16 % 16 == 0 && ldb % 8 == 0 && (bkc ? K : N) % 8 == 0 && (bkc ? K : N) >= 8) g.B16 = B16;
-    }
-    const long tiles = (long)xg_cdiv(M, BM) * xg_cdiv(N, BN);
-    const int nslab = xg_cdiv(K, BK);
-    if (!relu && tiles < 512) {                     // fill the chip by splitting deep reductions (3 workgroups per CU would fit,
-                                                    // but 768 shares were measured slower: dX 52 -> 83 us, dW_logit 157 -> 169 us)
-        // ... and never PAST the 512 slots (round 5): the rule used to round up, so 104 tiles became 5 x 104 = 520 workgroups -- a
-        // second round for 8 of them -- and 416 tiles two rounds of 832.  Rounded down (split-bf16, alone): encoder embedding
-        // 98 -> 63 us, dX 110 -> 74, PRE 104 -> 59, v2a(V) 94 -> 58 (tools/ubench/bs_skmax.sh)
-        long sk = 512 / tiles;
-        if (sk > nslab / 8) sk = nslab / 8;
-        if (sk >= 2) g.splitk = (int)sk;
-    }
-    // plain bf16 with a k-contiguous A (forward and data-gradient layouts): 256 x 128 tiles, 43 flop per operand byte instead
-    // of 32 -- logits 170 -> 145 us, PRE 79 -> 59 us; hidden-1024 iteration 9.19 -> 9.02 ms.  Measured and not used: the
-    // weight-gradient layout on these tiles (dW_logit 186 -> 276 us) and 256 x 256 tiles (one workgroup per CU: 10.4 ms).
-    static const bool no_bx = xg_diag_env("XG_NO_BX") != nullptr;
-    if (planes == 1 && vec && akc && !no_bx && M >= 256 && !g.A16 && !g.B16) {
-        const long t2 = (long)xg_cdiv(M, 256) * xg_cdiv(N, 128);
-        g.splitk = 1;
-        if (!relu && t2 < 256) {
-            long sk = (256 + t2 - 1) / t2;
-            if (sk > nslab / 8) sk = nslab / 8;
-            if (sk >= 2) g.splitk = (int)sk;
+// the register-staged bf16 kernels as the route says them (xg_gemm_route.h: plan_wide): gemm_bs in 1 or 3 planes -- with one or both
+// operands read from their bf16 copies -- and the 256 x 128 gemm_bx; nothing is decided here
+int xgk_gemm_bs_launch(hipStream_t st, const XgGemmRoute& r, const XgGemmIn& in, const XgGemmPtrs& p) {
+    const BArgs g{p.A, p.B, p.C, p.bias, in.M, in.N, in.K, in.lda, in.ldb, in.ldc, in.relu ? 1 : 0, in.accumulate ? 1 : 0, r.splitk, r.gm,
+                  r.a16 ? p.A16 : nullptr, r.b16 ? p.B16 : nullptr, {p.cs[0], p.cs[1], p.cs[2]}};
+    return xgk_with_layout(r, [&](auto akc, auto bkc) {
+        constexpr bool A = decltype(akc)::value, B = decltype(bkc)::value;
+        switch (r.family == XGR_BX ? 0 : 100 * r.planes + 10 * (r.vec ? 1 : 0) + (r.a16 ? 2 : 0) + (r.b16 ? 1 : 0)) {
+        case 0:
+            if constexpr (A) return xgk_launch_route<&gemm_bx_kernel<BX_TM, BX_TN, BX_WGM, BX_WGN, true, B>>(st, r, r.lds, g);
+            else return (int)XG_EINVAL;
+        case 100: return xgk_launch_route<&gemm_bs_kernel<1, A, B, false>>(st, r, r.lds, g);
+        case 110: return xgk_launch_route<&gemm_bs_kernel<1, A, B, true>>(st, r, r.lds, g);
+        case 111: return xgk_launch_route<&gemm_bs_kernel<1, A, B, true, false, true>>(st, r, r.lds, g);
+        case 112: return xgk_launch_route<&gemm_bs_kernel<1, A, B, true, true, false>>(st, r, r.lds, g);
+        case 113: return xgk_launch_route<&gemm_bs_kernel<1, A, B, true, true, true>>(st, r, r.lds, g);
+        case 300: return xgk_launch_route<&gemm_bs_kernel<3, A, B, false>>(st, r, r.lds, g);
+        case 310: return xgk_launch_route<&gemm_bs_kernel<3, A, B, true>>(st, r, r.lds, g);
+        default: return (int)XG_EINVAL;      // (no such kernel)
         }
-        g.gm = xgk_group_rows(2 * K / g.splitk);
-        return bkc ? launch_bx<256, 128, 4, 2, true, true>(st, g) : launch_bx<256, 128, 4, 2, true, false>(st, g);
-    }
-    // both operands bf16 in memory: tiles by LDS-DMA, 64-deep slabs, one barrier per slab (xg_gemm_g16.hip)
-    static const bool no_g16 = xg_diag_env("XG_NO_G16") != nullptr;
-    if (g.A16 && g.B16 && !no_g16 && xgk_gemm_g16_ok(transA, transB, M, N, K, g.A16, lda, g.B16, ldb))
-        return xgk_gemm_g16(st, transA, transB, M, N, K, g.A16, lda, g.B16, ldb, C, ldc, bias, relu, accumulate, bg ? -1 : 0, cs1, cs2, cs3);
-    g.gm = xgk_group_rows(K / g.splitk);
-    if (g.A16 || g.B16) {
-        if (akc && bkc) return dispatch16<true, true>(st, g);
-        if (akc && !bkc) return dispatch16<true, false>(st, g);
-        if (!akc && !bkc) return dispatch16<false, false>(st, g);
-        return dispatch16<false, true>(st, g);
-    }
-    return planes == 1 ? dispatch<1>(st, g, akc, bkc, vec) : dispatch<3>(st, g, akc, bkc, vec);
+    });
 }

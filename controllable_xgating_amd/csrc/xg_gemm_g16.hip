@@ -4,7 +4,7 @@
 //   C[M,N] (+)= op(A) op(B) (+ bias, relu), fp32 accumulate, v_mfma_f32_32x32x16_bf16.
 //   128 x 128 tiles, a wave's share 64 x 64 = 2 x 2 MFMA tiles; a ring of NS LDS stages of TK-deep slabs, filled by DMA and drained
 //   by COUNT (s_waitcnt vmcnt(N) + the raw s_barrier: __syncthreads() would drain the whole DMA queue), ONE barrier per slab; the
-//   DMA instructions of the next slab sit between the MFMA groups of the slab being multiplied.  Three forms (xgk_gemm_g16 picks):
+//   DMA instructions of the next slab sit between the MFMA groups of the slab being multiplied.  Three forms (xg_gemm_route.h: plan_g16 picks):
 //     TK 64, NS 2, four waves  -- 64 KiB, two workgroups per CU: the default;
 //     TK 32, NS 3, four waves  -- 48 KiB, three workgroups per CU: the weight-gradient layout with >= 1024 tiles;
 //     TK 64, NS 4, EIGHT waves -- two groups of four share the tile and split every slab's depth, 128 KiB, one workgroup per CU:
@@ -23,7 +23,7 @@
 // Edges: the DMA goes through a buffer descriptor whose extent is the operand's; a fetch past the end writes zeros.  Rows past
 // the last row of a k-contiguous operand and k rows past K of an m-contiguous operand are therefore zero for free; columns
 // past the end of an INNER row fetch the next row's head (finite data), which only ever meets unstored outputs or a zero row
-// of the other operand -- the dispatcher (xgk_gemm_g16_ok) admits exactly the shapes for which that holds.
+// of the other operand -- the planner (xg_gemm_route.h: g16_ok) admits exactly the shapes for which that holds.
 #include "xg_common.h"
 #include "xg_kernels.h"
 #include <cstdlib>
@@ -34,10 +34,7 @@ typedef short v4s __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int TM = 128, TN = 128;
-// TK = slab depth (64 or 32), NS = LDS stages of the ring (NS - 1 slabs in flight while one is multiplied)
-template <int TK> constexpr int opb() { return 128 * TK * 2; }     // bytes of one operand's stage image
-template <int TK> constexpr int stb() { return 2 * opb<TK>(); }    // bytes of one stage
+using namespace xgr::g16;      // TM, TN, opb, stb: xg_gemm_route.h (the planner sizes LDS from them)
 
 struct GArgs {
     const unsigned short* A; const unsigned short* B; float* C; const float* bias;
@@ -329,98 +326,26 @@ __global__ void __launch_bounds__(256 * KG, 2) gemm_g16_kernel(GArgs g) {
     }
 }
 
-template <bool AKC, bool BKC, int TK, int NS, int KG>
-int launch_g16(hipStream_t st, const GArgs& g, int extra_lds = 0) {
-    const int ntm = xg_cdiv(g.M, TM), ntn = xg_cdiv(g.N, TN);
-    if (g.splitk > 1 && !g.accumulate) {
-        if (g.ldc == g.N) { if (hipMemsetAsync(g.C, 0, sizeof(float) * (size_t)g.M * g.N, st) != hipSuccess) return XG_EHIP; }
-        else if (hipMemset2DAsync(g.C, sizeof(float) * g.ldc, 0, sizeof(float) * g.N, g.M, st) != hipSuccess) return XG_EHIP;
-    }
-    const int lds = NS * stb<TK>() + extra_lds;     // (extra_lds: diag -- a product beside a chain kept to one workgroup per CU)
-    if (lds > 65536) {
-        static std::atomic<unsigned> optin{0};
-        XG_TRY(xg_lds_optin(optin, reinterpret_cast<const void*>(&gemm_g16_kernel<AKC, BKC, TK, NS, KG>), lds));
-    }
-    hipLaunchKernelGGL((gemm_g16_kernel<AKC, BKC, TK, NS, KG>), dim3(ntm * ntn * g.splitk), dim3(256 * KG), lds, st, g);
-    XG_CHECK_LAUNCH();
-    return XG_OK;
-}
-template <int TK, int NS, int KG = 1>
-int launch_g16_layout(hipStream_t st, const GArgs& g, bool akc, bool bkc, int extra_lds = 0) {
-    if (akc && bkc) return launch_g16<true, true, TK, NS, KG>(st, g, extra_lds);
-    if (akc && !bkc) return launch_g16<true, false, TK, NS, KG>(st, g, extra_lds);
-    if (!akc && !bkc) return launch_g16<false, false, TK, NS, KG>(st, g, extra_lds);
-    return launch_g16<false, true, TK, NS, KG>(st, g, extra_lds);
-}
-
 }  // namespace
 
-// Shapes the DMA kernel handles (see the header on edges): 16-byte loadable rows, 32-bit byte offsets, and a K tail only where
-// one operand supplies zeros for it (an m-contiguous operand: its k rows past K are past the end of the buffer) while the
-// other's overrun stays inside its own data (k-contiguous with lda == K: the next row's head; or m-contiguous as well).
-bool xgk_gemm_g16_ok(bool transA, bool transB, int M, int N, int K, const unsigned short* A16, int lda, const unsigned short* B16, int ldb) {
-    const bool akc = !transA, bkc = transB;
-    if (!A16 || !B16 || M < 128 || N < 128 || K < 128) return false;
-    if ((uintptr_t)A16 % 16 || (uintptr_t)B16 % 16 || lda % 8 || ldb % 8) return false;
-    if ((akc ? K : M) % 8 || (bkc ? K : N) % 8) return false;
-    const int64_t ea = (int64_t)((akc ? M : K) + 128) * lda * 2, eb = (int64_t)((bkc ? N : K) + 128) * ldb * 2;
-    if (ea >= (int64_t)1 << 31 || eb >= (int64_t)1 << 31) return false;
-    if (K % 64) {
-        const bool a_zero = !akc, b_zero = !bkc;                  // zero k rows past K for free
-        const bool a_safe = !akc || lda == K, b_safe = !bkc || ldb == K;
-        if (!((a_zero && b_safe) || (b_zero && a_safe))) return false;
-    }
-    return true;
-}
-
-int xgk_gemm_g16(hipStream_t st, bool transA, bool transB, int M, int N, int K, const unsigned short* A16, int lda,
-                 const unsigned short* B16, int ldb, float* C, int ldc, const float* bias, bool relu, bool accumulate, int splitk,
-                 float* cs1, float* cs2, float* cs3) {
-    if (cs1 && !transA) return XG_EINVAL;
-    const bool akc = !transA, bkc = transB;
-    GArgs g{A16, B16, C, bias, M, N, K, lda, ldb, ldc, relu ? 1 : 0, accumulate ? 1 : 0, 1, 1, {cs1, cs2, cs3}, 0};
-    // Configuration <wave groups, slab depth, ring stages> (tools/ubench/g16_cfg.sh / g16_burst.sh, products alone):
-    //   64-deep slabs in two stages, four waves, two workgroups per CU ("642") everywhere but the weight-gradient layout, where
-    //   - with at most one tile per CU, EIGHT waves per tile win (two groups of four that split every slab's depth; one workgroup
-    //     per CU, four-stage ring: "844"): 4096 x 1024 x 5120 58-65 against 71-73 us, 4096 x 1024 x 2688 36-40 against 48-53,
-    //     1024 x 1536 x 5120 40-43 against 48-54 -- and lose everywhere else (logits 241 against 200, dH 193 against 143);
-    //   - with >= 1024 tiles, 32-deep slabs in three stages (three workgroups per CU, "323") are 10-20 % ahead (dW_logit 143
-    //     against 173 us); wherever an operand is k-contiguous they lose (64-byte row pieces = half cache lines).
-    //   One workgroup of four waves per CU with three 64-deep stages loses everywhere (277 against 188 us on the logits): what this
-    //   kernel needs is waves to switch to, not bytes in flight.
-    const long tiles = (long)xg_cdiv(M, TM) * xg_cdiv(N, TN);
-    static const char* cfg = xg_diag_env("XG_G16_CFG");     // diag build: 642 / 643 / 322 / 323 / 324 / 325 / 843 / 844
-    const bool tn_layout = !akc && !bkc;
-    const int c = cfg ? atoi(cfg) : (tn_layout && tiles >= 1024 ? 323 : (tn_layout && tiles <= 256 ? 844 : 642));
-    // Split of the reduction across workgroups (`splitk` <= 0: this kernel's own rule; the register-staged kernel's rule
-    // filled 512 slots whenever the tiles did not).  A part's result is added with fp32 atomics behind a memset of C, and that
-    // epilogue is expensive here: 5120 x 1024 x 1536 takes 34 us unsplit and 58-70 us in two parts, 5120 x 1024 x 4096 76 against
-    // 85-114 us.  Measured rule (tools/ubench/g16_sk.sh): split only while tiles x parts stay ONE round of the slots (512 with two
-    // workgroups per CU, 256 with one) and every part keeps a reduction of >= 2560 -- 2688 x 1024 x 20000: 3 parts (158 us; 1 / 2 / 4
-    // parts: 322 / 198 / 228) -- or, while the tiles alone leave CUs empty, of >= 1024 (1024 x 1536 x 5120, 96 tiles, four waves:
-    // 87 / 65 / 55 / 51 / 52 us in 1 / 2 / 3 / 4 / 5 parts).
-    // (splitk == -1: the product was launched beside a latency-bound chain, XGK_GEMM_BG.  Keeping it to ONE workgroup per CU there
-    //  was measured at the end of round 5 and is inside the noise: gone.)
-    constexpr int extra_lds = 0;
-    if (splitk > 0) g.splitk = splitk;
-    else if (!relu) {
-        const long slots = (c >= 800 || extra_lds) ? 256 : 512;
-        const int deep = tiles < 256 ? 1024 : 2560;
-        long sk = slots / tiles;
-        if (sk > K / deep) sk = K / deep;
-        g.splitk = sk < 1 ? 1 : (int)sk;
-    }
-    g.gm = xgk_group_rows(K / g.splitk / 2);          // (an operand panel is 128 x k_depth bf16 = half the bytes the rule was made for)
-    switch (c) {
-    case 323: return launch_g16_layout<32, 3>(st, g, akc, bkc);
-    case 844: return launch_g16_layout<64, 4, 2>(st, g, akc, bkc);       // eight waves (two k groups), one workgroup per CU
+// the DMA kernel as the route says it (xg_gemm_route.h: g16_ok admits the shapes, plan_g16 picks configuration and split)
+int xgk_gemm_g16(hipStream_t st, const XgGemmRoute& r, const XgGemmIn& in, const XgGemmPtrs& p) {
+    const GArgs g{p.A16, p.B16, p.C, p.bias, in.M, in.N, in.K, in.lda, in.ldb, in.ldc, in.relu ? 1 : 0, in.accumulate ? 1 : 0, r.splitk, r.gm,
+                  {p.cs[0], p.cs[1], p.cs[2]}, 0};
+    return xgk_with_layout(r, [&](auto akc, auto bkc) {
+        constexpr bool A = decltype(akc)::value, B = decltype(bkc)::value;
+        switch (r.cfg) {      // <wave groups, slab depth, ring stages>
+        case 642: return xgk_launch_route<&gemm_g16_kernel<A, B, 64, 2, 1>>(st, r, r.lds, g);
+        case 323: return xgk_launch_route<&gemm_g16_kernel<A, B, 32, 3, 1>>(st, r, r.lds, g);
+        case 844: return xgk_launch_route<&gemm_g16_kernel<A, B, 64, 4, 2>>(st, r, r.lds, g);       // eight waves (two k groups), one workgroup per CU
 #ifdef XG_DIAG
-    case 322: return launch_g16_layout<32, 2>(st, g, akc, bkc);
-    case 843: return launch_g16_layout<64, 3, 2>(st, g, akc, bkc);
-    case 643: return launch_g16_layout<64, 3>(st, g, akc, bkc);
-    case 324: return launch_g16_layout<32, 4>(st, g, akc, bkc);
-    case 325: return launch_g16_layout<32, 5>(st, g, akc, bkc);
+        case 322: return xgk_launch_route<&gemm_g16_kernel<A, B, 32, 2, 1>>(st, r, r.lds, g);
+        case 843: return xgk_launch_route<&gemm_g16_kernel<A, B, 64, 3, 2>>(st, r, r.lds, g);
+        case 643: return xgk_launch_route<&gemm_g16_kernel<A, B, 64, 3, 1>>(st, r, r.lds, g);
+        case 324: return xgk_launch_route<&gemm_g16_kernel<A, B, 32, 4, 1>>(st, r, r.lds, g);
+        case 325: return xgk_launch_route<&gemm_g16_kernel<A, B, 32, 5, 1>>(st, r, r.lds, g);
 #endif
-    default: return launch_g16_layout<64, 2>(st, g, akc, bkc, extra_lds);
-    }
+        default: return (int)XG_EINVAL;      // (a configuration this build has no kernel for)
+        }
+    });
 }

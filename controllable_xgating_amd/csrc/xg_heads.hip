@@ -1042,49 +1042,6 @@ __global__ void ss_select_kernel(const int64_t* seq, int T, int t, int B, const 
     tok[b] = take ? sampled[b] : seq[(size_t)b * T + t];
 }
 
-// SAModel.py:200-215: unfinished &= it>0 ; it *= unfinished ; append ; n = first t with none unfinished
-__global__ void rollout_book_kernel(int t, int B, int Tm1, int replay, const int64_t* tok, const float* tok_logp,
-                                    float* unfinished, int64_t* seq, float* seq_logp, int32_t* n_steps,
-                                    int32_t* alive) {
-    // single workgroup; alive[0] = 1 while the reference's loop would still be running
-    __shared__ int any;
-    if (threadIdx.x == 0) any = 0;
-    __syncthreads();
-    for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        const int64_t it = tok[b];
-        float u = (t == 1) ? (it > 0 ? 1.f : 0.f) : unfinished[b] * (it > 0 ? 1.f : 0.f);
-        unfinished[b] = u;
-        if (u > 0.f) atomicOr(&any, 1);
-    }
-    __syncthreads();
-    const int was_alive = alive[0];
-    const int now_alive = was_alive && (any || replay);
-    for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        if (now_alive) {
-            seq[(size_t)b * Tm1 + (t - 1)] = replay ? tok[b] : (unfinished[b] > 0.f ? tok[b] : 0);
-            seq_logp[(size_t)b * Tm1 + (t - 1)] = tok_logp[b];
-        } else {
-            seq[(size_t)b * Tm1 + (t - 1)] = 0;
-            seq_logp[(size_t)b * Tm1 + (t - 1)] = 0.f;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (was_alive && !now_alive) n_steps[0] = t - 1;      // reference breaks before appending (SAModel.py:206-207)
-        alive[0] = now_alive;
-    }
-}
-
-__global__ void __launch_bounds__(RT) rollout_dlogits_kernel(const float* __restrict__ logp, const int64_t* tok,
-                                                               const float* dslp, int64_t dstride, float* dlogits, int V) {
-    const int b = blockIdx.x;
-    const float d = dslp[(size_t)b * dstride];
-    const int64_t tk = tok[b];
-    const float* y = logp + (size_t)b * V;
-    float* dx = dlogits + (size_t)b * V;
-    for (int v = threadIdx.x; v < V; v += RT) dx[v] = d * ((v == tk ? 1.f : 0.f) - expf(y[v]));
-}
-
 }  // namespace
 
 int xgk_log_softmax(hipStream_t st, const float* in, int ldin, float* out, int ldout, int rows, int V, int inner,
@@ -1235,19 +1192,6 @@ int xgk_rollout_dlogits_lse(hipStream_t st, float* logits, const float* lse, con
 int xgk_ss_select(hipStream_t st, const int64_t* seq, int T, int t, int B, const float* u_sel, float ss_prob,
                   const int64_t* sampled, int64_t* tok) {
     hipLaunchKernelGGL(ss_select_kernel, dim3(xg_cdiv(B, 256)), dim3(256), 0, st, seq, T, t, B, u_sel, ss_prob, sampled, tok);
-    XG_CHECK_LAUNCH();
-    return XG_OK;
-}
-int xgk_rollout_book(hipStream_t st, int t, int B, int Tm1, int replay, const int64_t* tok, const float* tok_logp,
-                     float* unfinished, int64_t* seq, float* seq_logp, int32_t* n_steps, int32_t* alive) {
-    hipLaunchKernelGGL(rollout_book_kernel, dim3(1), dim3(256), 0, st, t, B, Tm1, replay, tok, tok_logp, unfinished, seq,
-                       seq_logp, n_steps, alive);
-    XG_CHECK_LAUNCH();
-    return XG_OK;
-}
-int xgk_rollout_dlogits(hipStream_t st, const float* logp, const int64_t* tok, const float* dslp, int64_t dstride,
-                        float* dlogits, int B, int V) {
-    hipLaunchKernelGGL(rollout_dlogits_kernel, dim3(B), dim3(RT), 0, st, logp, tok, dslp, dstride, dlogits, V);
     XG_CHECK_LAUNCH();
     return XG_OK;
 }

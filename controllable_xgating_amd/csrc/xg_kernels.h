@@ -3,26 +3,15 @@
 #include "xg_common.h"
 #include "xg_select.h"
 #include "xg_beam_core.h"
+#include "xg_gemm_route.h"
 #include <cstddef>
+#include <type_traits>
 
 // ---- xg_gemm.hip
 // `mode` = arithmetic of the product (XgRun.gemm_mode): 0 exact fp32 MFMA, 3 split-bf16, 1 bf16 operands; modes 1 / 3 apply
-// to LARGE products only (M >= 256, N >= 64, K >= 64), everything else is fp32.  An explicit argument: no per-thread state.
-// Tile rows per group of the GEMM kernels' tile order: the ~64 tiles an XCD works on at a time span gm tile rows x 64/gm
-// tile columns, so its 4 MB L2 holds gm + 64/gm operand panels of 128 x k_depth floats instead of 1 + 64 (measured: the
-// bf16 vocabulary product re-read W from HBM at 4.3 TB/s in row-major order).  Deep reductions keep the row-major order:
-// their panels do not fit anyway and consecutive tiles should then share the bigger operand's panel.
-static inline int xgk_group_rows(int k_depth) {
-    const int g = 4096 / (k_depth > 0 ? k_depth : 1);
-    return g < 1 ? 1 : (g > 8 ? 8 : g);
-}
-// `mode | XGK_GEMM_BG`: the product is launched on a side stream beside a latency-bound chain of small launches; the
-// persistent kernel then takes half of every CU instead of all of it (xg_gemm.hip: launch_pk)
-enum { XGK_GEMM_BG = 0x100,
-       // `mode | XGK_GEMM_ALONE`: nothing latency-bound runs beside this product (the encoder's weight gradients at the tail of an
-       // iteration): the weight-gradient layout takes the operands-from-memory kernel (gemm_td_kernel), 18 % faster alone on the
-       // mid-size shapes and kept away from them elsewhere because it slows a launch chain on another stream (xg_gemm.hip: launch_td)
-       XGK_GEMM_ALONE = 0x200 };
+// to LARGE products only (xg_gemm_route.h: M >= 256, N >= 64, K >= 256), everything else is fp32.  An explicit argument: no per-thread state.
+// Which kernel a product gets is decided by xg_gemm_plan (xg_gemm_route.h: xgk_group_rows, XGK_GEMM_BG / XGK_GEMM_ALONE and the
+// tile geometry live there); the three GEMM files launch the route.
 int xgk_gemm(hipStream_t st, int mode, bool transA, bool transB, int M, int N, int K, const float* A, int lda,
              const float* B, int ldb, float* C, int ldc, const float* bias, bool relu, bool accumulate);
 // the same product for the weight-gradient layout (transA) with the column sums of A = dY^T as a side output: cs[m] += sum_k A(k, m)
@@ -35,19 +24,39 @@ int xgk_gemm_cs(hipStream_t st, int mode, bool transA, bool transB, int M, int N
 int xgk_gemm_x(hipStream_t st, int mode, bool transA, bool transB, int M, int N, int K, const float* A, const unsigned short* A16,
                int lda, const float* B, const unsigned short* B16, int ldb, float* C, int ldc, const float* bias, bool relu,
                bool accumulate, float* cs1 = nullptr, float* cs2 = nullptr, float* cs3 = nullptr);
-// xg_gemm_bf16.hip: split-bf16 / bf16 arithmetic for large products (planes = 3 or 1)
-// cs1..cs3 (optional, weight-gradient layout transA only): column sums of A = the bias gradient(s) of the same dY, a side output
-int xgk_gemm_bf16(hipStream_t st, int planes, bool transA, bool transB, int M, int N, int K, const float* A, int lda,
-                  const float* B, int ldb, float* C, int ldc, const float* bias, bool relu, bool accumulate, float* cs1 = nullptr,
-                  float* cs2 = nullptr, float* cs3 = nullptr);
-int xgk_gemm_bf16x(hipStream_t st, int planes, bool transA, bool transB, int M, int N, int K, const float* A, const unsigned short* A16,
-                   int lda, const float* B, const unsigned short* B16, int ldb, float* C, int ldc, const float* bias, bool relu,
-                   bool accumulate, float* cs1 = nullptr, float* cs2 = nullptr, float* cs3 = nullptr);
-// xg_gemm_g16.hip: both operands bf16 in memory, tiles by LDS-DMA (round 5); xgk_gemm_g16_ok says whether a product qualifies
-bool xgk_gemm_g16_ok(bool transA, bool transB, int M, int N, int K, const unsigned short* A16, int lda, const unsigned short* B16, int ldb);
-int xgk_gemm_g16(hipStream_t st, bool transA, bool transB, int M, int N, int K, const unsigned short* A16, int lda,
-                 const unsigned short* B16, int ldb, float* C, int ldc, const float* bias, bool relu, bool accumulate, int splitk,
-                 float* cs1, float* cs2, float* cs3);
+// ---- a planned product: what the planner does not see (the data) and the pieces every GEMM file launches a route with
+struct XgGemmPtrs {
+    const float* A; const float* B; float* C; const float* bias;
+    const unsigned short* A16; const unsigned short* B16;      // bf16 copies of the operands, or null
+    float* cs[3];                                              // column-sum accumulators, or null
+};
+// builds the planner's input, plans once and hands the route to its file's launcher (xg_gemm.hip)
+int xgk_gemm_run(hipStream_t st, bool wide_forced, int mode, bool transA, bool transB, int M, int N, int K, int lda, int ldb, int ldc,
+                 bool relu, bool accumulate, const XgGemmPtrs& p);
+int xgk_gemm_bs_launch(hipStream_t st, const XgGemmRoute& r, const XgGemmIn& in, const XgGemmPtrs& p);      // xg_gemm_bf16.hip: gemm_bs, gemm_bx
+// xg_gemm_g16.hip: both operands bf16 in memory, tiles by LDS-DMA (round 5)
+int xgk_gemm_g16(hipStream_t st, const XgGemmRoute& r, const XgGemmIn& in, const XgGemmPtrs& p);
+// the route's side work before the launch: C, or the rectangle the persistent kernel's tail adds into, := 0 (xg_gemm.hip)
+int xgk_gemm_clear(hipStream_t st, const XgGemmRoute& r, const XgGemmIn& in, float* C);
+// f(AKC, BKC) with the route's operand layouts as std::bool_constant
+template <class F>
+int xgk_with_layout(const XgGemmRoute& r, F&& f) {
+    if (r.akc && r.bkc) return f(std::true_type{}, std::true_type{});
+    if (r.akc && !r.bkc) return f(std::true_type{}, std::false_type{});
+    if (!r.akc && !r.bkc) return f(std::false_type{}, std::false_type{});
+    return f(std::false_type{}, std::true_type{});
+}
+// one launch as the route says it: grid, threads, dynamic LDS; a kernel that may take more than 64 KiB of it opts in once
+template <auto KERNEL, class ARGS>
+int xgk_launch_route(hipStream_t st, const XgGemmRoute& r, int optin_bytes, const ARGS& g) {
+    if (optin_bytes > 65536) {
+        static std::atomic<unsigned> optin{0};
+        XG_TRY(xg_lds_optin(optin, reinterpret_cast<const void*>(KERNEL), optin_bytes));
+    }
+    hipLaunchKernelGGL(KERNEL, dim3(r.grid), dim3(r.threads), r.lds, st, g);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
 int xgk_cvt_bf16(hipStream_t st, const float* src, unsigned short* dst, size_t n);      // fp32 -> bf16 (RNE), both 16-byte aligned
 // Y[M,N] (+)= X[M,K] W[N,K]^T + bias   (nn.Linear forward)
 static inline int xgk_linear(hipStream_t st, int mode, int M, int N, int K, const float* X, int ldx, const float* W,
@@ -115,8 +124,6 @@ int xgk_relu_drop_bwd(hipStream_t st, float* dy, const float* y, int64_t n, XgDr
 int xgk_colsum(hipStream_t st, const float* X, int ld, int N, int Cn, float* out);
 // the same sums added into up to three accumulators (out2 / out3 may be null)
 int xgk_colsum3(hipStream_t st, const float* X, int ld, int N, int Cn, float* out, float* out2, float* out3);
-// out1[c] += sum_r X*Y ; (used for BN dgamma and a2w weight grad)
-int xgk_colsum_prod(hipStream_t st, const float* X, int ldx, const float* Y, int ldy, int N, int Cn, float* out);
 
 // BatchNorm1d over rows of Z (N,R): statistics, apply (+ReLU, dropout, row mask), backward
 // train-mode BatchNorm forward in one launch: batch statistics (+ running statistics when rmean / rvar are given) and, when X is
@@ -356,12 +363,6 @@ int xgk_compact(hipStream_t st, CompactArgs& a);
 // scheduled sampling (SAModel.py:89-99): tok[b] = u_sel[b] < ss_prob ? sampled[b] : seq[b*T + t]
 int xgk_ss_select(hipStream_t st, const int64_t* seq, int T, int t, int B, const float* u_sel, float ss_prob,
                   const int64_t* sampled, int64_t* tok);
-// rollout bookkeeping (SAModel.py:200-215)
-int xgk_rollout_book(hipStream_t st, int t, int B, int Tm1, int replay, const int64_t* tok, const float* tok_logp,
-                     float* unfinished, int64_t* seq, float* seq_logp, int32_t* n_steps, int32_t* alive);
-// dlogits (B,V) row b = d * (onehot(tok) - softmax) for the sampled token (rollout backward)
-int xgk_rollout_dlogits(hipStream_t st, const float* logp, const int64_t* tok, const float* dslp, int64_t dstride,
-                        float* dlogits, int B, int V);
 
 // ---- xg_beam.hip: the captioner's beam search (include/xgate_beam.h)
 // dst row b W + slot = src row b (rows of n floats), every entry in one launch

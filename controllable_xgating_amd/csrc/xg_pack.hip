@@ -199,7 +199,7 @@ bool xgk_packed_view(const XgDims& d, const void* packed, int dtype, PackedView*
         describe_w16(d, p, we);
         off = (off + 255) & ~(size_t)255;
         for (int i = 0; i < W16_COUNT; ++i) {
-            // 16-byte loadable rows only (the GEMM falls back to the fp32 weight otherwise: xgk_gemm_bf16x checks pitch % 8)
+            // 16-byte loadable rows only (the GEMM falls back to the fp32 weight otherwise: xg_gemm_route.h: plan_wide checks pitch % 8)
             v->w16[i] = reinterpret_cast<const unsigned short*>(base + off);
             off += w16_bytes(we[i].n);
         }

@@ -475,9 +475,6 @@ int xgk_colsum(hipStream_t st, const float* X, int ld, int N, int Cn, float* out
 int xgk_colsum3(hipStream_t st, const float* X, int ld, int N, int Cn, float* out, float* out2, float* out3) {
     return colreduce<0>(st, X, ld, nullptr, 0, N, Cn, out, out2, out3);
 }
-int xgk_colsum_prod(hipStream_t st, const float* X, int ldx, const float* Y, int ldy, int N, int Cn, float* out) {
-    return colreduce<1>(st, X, ldx, Y, ldy, N, Cn, out);
-}
 // Train-mode BatchNorm forward of 16 columns per workgroup with the column strip held in registers: one read of Z, the exact
 // two-pass statistics (mean, then the sum of squared deviations) in a fixed summation order, the running statistics' update and
 // -- when X is given -- the normalised, ReLU'd, dropped and row-masked output, all in ONE launch.  The column reductions it

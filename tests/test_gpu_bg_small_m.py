@@ -1,4 +1,4 @@
-"""The background form of the persistent fp32 GEMM (xg_gemm.hip: launch_pk with XGK_GEMM_BG, one workgroup per CU) on products of
+"""The background form of the persistent fp32 GEMM (xg_gemm.hip: gemm_pk_kernel with XGK_GEMM_BG, one workgroup per CU) on products of
 a few decoder steps' rows: its unit floor is one 4-slab share for each of the 256 workgroups (tiles x slabs >= 1024), so a product
 may consist of stream-K tail only (fewer than 256 tiles: no whole-tile round), of one round plus a tail, or fall under the floor
 and take the tile kernels.  Every element against float64."""
@@ -18,13 +18,12 @@ def _need_gpu():
     import __graft_entry__ as ge
     ge.build()
 
-# M x N x K around the floor.  Tiles are 128 x 128 and slabs 32 deep: K = 64 / 468 / 512 are 2 / 15 (the last one partial) / 16
-# slabs.  640 x 2504 x 512 is 100 tiles = 1600 units: above the floor with every tile in the tail; 384 x 2504 x 512 is 960 units:
-# just under it; 128 x 128 is one tile.  M = 200 and 392, N = 1000 and 2504 leave ragged edge tiles.
+# (the shapes, M x N x K around the floor: tests/gemm_shapes.BG_SMALL_M)
 _SCRIPT = r"""
 import sys, torch
 sys.path.insert(0, %r)
 from controllable_xgating_amd import _native as nv
+from tests.gemm_shapes import BG_SMALL_M
 L = nv.lib()
 bad, n = [], 0
 def run(M, N, K, acc, it):
@@ -39,14 +38,8 @@ def run(M, N, K, acc, it):
     err = float((C.double() - want).abs().max()) / float(want.abs().max())
     if rc != 0 or not err < 6e-6:
         bad.append((M, N, K, acc, rc, err))
-for M in (128, 200, 256, 384, 392, 640):
-    for N in (128, 1000, 2504):
-        for K in (64, 468, 512):
-            run(M, N, K, 0, n); n += 1
-run(640, 2504, 512, 1, n); n += 1      # += C on the all-tail shape: every share adds with atomics, nothing is zeroed
-run(392, 2504, 468, 1, n); n += 1
-run(384, 20000, 512, 0, n); n += 1     # three decoder steps of the flagship shape: 471 tiles = one round + a 215-tile tail
-run(256, 20000, 512, 0, n); n += 1     # two steps: 314 tiles = one round + 58
+for M, N, K, acc in BG_SMALL_M:
+    run(M, N, K, acc, n); n += 1
 print("shapes", n, "BAD", bad)
 sys.exit(1 if bad else 0)
 """

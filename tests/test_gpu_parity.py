@@ -10,6 +10,7 @@ import torch
 
 from oracle import paramgen as pg
 from oracle import xgate_oracle as xo
+from tests import gemm_shapes as gs
 from tests.util import CFG, WEIGHT_CLASS, ZERO_GRAD_PARAMS, assert_grads_close, load_golden, make_model, oracle_grads, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -23,9 +24,8 @@ def _need_gpu():
 
 
 # ---------------------------------------------------------------- GEMM building block
-@pytest.mark.parametrize("M,N,K", [(128, 2048, 1536), (2688, 512, 468), (37, 53, 29), (8, 1536, 1024),
-                                   (300, 260, 131), (64, 64, 32), (1, 5, 7), (513, 129, 1000)])
-@pytest.mark.parametrize("ta,tb", [(0, 1), (0, 0), (1, 0), (1, 1)])
+@pytest.mark.parametrize("M,N,K", gs.LAYOUTS)
+@pytest.mark.parametrize("ta,tb", gs.LAYOUT_CASES)
 def test_gemm_layouts(M, N, K, ta, tb):
     from controllable_xgating_amd import _native as nv
     L = nv.lib()
@@ -49,9 +49,8 @@ def test_gemm_layouts(M, N, K, ta, tb):
         assert float((got - want).abs().max()) <= tol * max(1.0, float(want.abs().max())), (relu, acc)
 
 
-@pytest.mark.parametrize("M,N,K", [(2688, 2000, 516), (1300, 9000, 200), (1408, 512, 20000), (3000, 3000, 256),
-                                   (2688, 20000, 512), (4100, 2052, 96)])
-@pytest.mark.parametrize("ta,tb", [(0, 1), (0, 0), (1, 0), (1, 1)])
+@pytest.mark.parametrize("M,N,K", gs.PERSISTENT)
+@pytest.mark.parametrize("ta,tb", gs.LAYOUT_CASES)
 def test_gemm_persistent_kernel_shapes(M, N, K, ta, tb):
     """Shapes large enough for the persistent 128x128 kernel (whole-tile rounds + stream-K tail with atomics, partial last
     slab, ragged edges, ReLU without splitting, += C): every element of C against fp64."""
@@ -129,9 +128,10 @@ _GEMM_W1 = r"""
 import sys, numpy as np, torch
 sys.path.insert(0, %r)
 from controllable_xgating_amd import _native as nv
+from tests.gemm_shapes import W1_SHAPES
 L = nv.lib()
 bad = []
-for (M, N, K) in ((1000, 516, 512), (3328, 512, 1536), (260, 2052, 256)):
+for (M, N, K) in W1_SHAPES:
     for ta, tb in ((0, 1), (0, 0), (1, 0), (1, 1)):
         g = torch.Generator(device="cuda").manual_seed(M + 3 * N + 5 * K + ta * 2 + tb)
         A = torch.randn((K, M) if ta else (M, K), generator=g, device="cuda")
@@ -152,7 +152,7 @@ sys.exit(1 if bad else 0)
 """
 
 
-@pytest.mark.parametrize("tile", ["auto", "64,64", "64,128", "128,64", "128,128", "128,192", "192,128", "128,256", "256,128"])
+@pytest.mark.parametrize("tile", gs.W1_TILE_CASES)
 def test_gemm_one_workgroup_per_cu_kernel(tile):
     """xg_gemm.hip's deep-slab kernel for products of about one round of tiles (gemm_w1_kernel: two register sets of global
     loads, MFMAs interleaved with the LDS / global instructions): every tile shape forced onto ragged products (XG_W1_TILE of the
@@ -199,10 +199,10 @@ _GEMM_TD = r"""
 import sys, numpy as np, torch
 sys.path.insert(0, %r)
 from controllable_xgating_amd import _native as nv
+from tests.gemm_shapes import TD_SHAPES
 L = nv.lib()
 bad = []
-for (M, N, K) in ((2048, 512, 2688), (20000, 512, 2688), (512, 512, 3328), (516, 468, 1040), (1536, 512, 2688), (2048, 468, 2688),
-                  (512, 1024, 3328), (4100, 260, 272)):
+for (M, N, K) in TD_SHAPES:
     g = torch.Generator(device="cuda").manual_seed(M + 3 * N + 5 * K)
     A = torch.randn(K, M, generator=g, device="cuda")
     B = torch.randn(K, N, generator=g, device="cuda")
@@ -220,13 +220,13 @@ sys.exit(1 if bad else 0)
 """
 
 
-@pytest.mark.parametrize("rule", ["production", "every_eligible_product", "split_2", "depth_4"])
+@pytest.mark.parametrize("rule", list(gs.TD_RULES))
 def test_gemm_weight_gradient_layout_from_memory(rule):
     """C (+)= A^T B with both operands stored (K, .): xg_gemm.hip's gemm_td_kernel (v_mfma_f32_16x16x4_f32 fed by 16-byte global loads
     in the instruction's own operand layout, no LDS image; four waves per 64 x 64 tile on interleaved k-steps, added through LDS;
     a cross-workgroup split of the reduction with atomics when there are few tiles; persistent rounds when there are many).
     Ragged edges (extents that are multiples of 4 but not of 64), plain store and += C, every element against fp64.  The
-    production rule sends only the vocabulary head's weight gradient there (20000 x 512: see launch_td); the -DXG_DIAG library's
+    production rule sends only the vocabulary head's weight gradient there (20000 x 512: see xg_gemm_route.h, plan_td); the -DXG_DIAG library's
     XG_TD_ALL=1 every eligible product (few tiles: split reductions; XG_TD_KS / XG_TD_DEPTH force the split and the ring depth)."""
     import subprocess
     import sys
@@ -904,9 +904,8 @@ def test_scheduled_sampling_vs_oracle():
 
 
 # ---------------------------------------------------------------- bf16 matrix-core modes (BASELINE.json configs[4])
-@pytest.mark.parametrize("ta,tb", [(0, 1), (0, 0), (1, 0), (1, 1)])
-@pytest.mark.parametrize("M,N,K", [(256, 256, 128), (2688, 1000, 1024), (328, 2048, 2688), (1408, 512, 20000), (136, 264, 200),
-                                   (5120, 1024, 1536)])
+@pytest.mark.parametrize("ta,tb", gs.LAYOUT_CASES)
+@pytest.mark.parametrize("M,N,K", gs.BF16_OPERANDS)
 def test_gemm_bf16_operands_in_memory(M, N, K, ta, tb):
     """Both operands bf16 in memory (xg_gemm_bf16_operands; round 5: tiles by LDS-DMA, xg_gemm_g16.hip, where the shape
     qualifies -- ragged M / N edges, a K tail next to an m-contiguous operand, deep reductions split across workgroups; the
@@ -932,8 +931,8 @@ def test_gemm_bf16_operands_in_memory(M, N, K, ta, tb):
         assert err <= (2e-6 * np.sqrt(K) * 4 + 1e-6) * max(1.0, float(want.abs().max())), (relu, acc, err)
 
 
-@pytest.mark.parametrize("ta,tb", [(0, 1), (0, 0), (1, 0), (1, 1)])
-@pytest.mark.parametrize("M,N,K", [(512, 384, 300), (300, 200, 129), (2688, 512, 468)])
+@pytest.mark.parametrize("ta,tb", gs.LAYOUT_CASES)
+@pytest.mark.parametrize("M,N,K", gs.BF16_MODES)
 def test_gemm_bf16_modes(M, N, K, ta, tb):
     """mode 3 (split-bf16, 6 MFMAs) must be fp32-class; mode 1 (bf16 operands) within bf16 round-off."""
     from controllable_xgating_amd import _native as nv

@@ -3,26 +3,7 @@ XG_GEMM_FORCE="tile,splitk" overrides the fp32 kernel's heuristic.  usage: gemm_
 import os, sys, subprocess, json
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-SHAPES = [  # name, ta, tb, M, N, K, acc
-    ("logits fwd NT", 0, 1, 2688, 20000, 512, 0),
-    ("dW_logit TN", 1, 0, 20000, 512, 2688, 1),
-    ("dH NN K=20000", 0, 0, 2688, 512, 20000, 0),
-    ("wgrad TN 2048x512 K=2688", 1, 0, 2048, 512, 2688, 1),
-    ("enc embed NT 3328x512 K=1536", 0, 1, 3328, 512, 1536, 0),
-    ("PRE NT 3328x2048 K=512", 0, 1, 3328, 2048, 512, 0),
-    ("vproj NT 3328x1536 K=512", 0, 1, 3328, 1536, 512, 0),
-    ("dX NN 3328x512 K=2048", 0, 0, 3328, 512, 2048, 0),
-    ("rollout logits NT 128x20000 K=512", 0, 1, 128, 20000, 512, 0),
-    ("rollout logits NT 64x20000 K=512", 0, 1, 64, 20000, 512, 0),
-    ("dH NN 1920x512 K=20000", 0, 0, 1920, 512, 20000, 0),
-    ("dH half NN 1408x512 K=20000", 0, 0, 1408, 512, 20000, 0),
-    ("dH half NN 1280x512 K=20000", 0, 0, 1280, 512, 20000, 0),
-    # the teacher-forced forward's vocabulary product in step-sized chunks (with XG_GEMM_FORCE_BG=1: the background form they run in)
-    ("logits chunk NT 256x20000 K=512", 0, 1, 256, 20000, 512, 0),
-    ("logits chunk NT 384x20000 K=512", 0, 1, 384, 20000, 512, 0),
-    ("logits chunk NT 512x20000 K=512", 0, 1, 512, 20000, 512, 0),
-    ("logits chunk NT 1280x20000 K=512", 0, 1, 1280, 20000, 512, 0),
-]
+from tests.gemm_shapes import GEMM_BENCH as SHAPES      # name, ta, tb, M, N, K, acc
 if os.environ.get("XG_GEMM_SHAPES"):
     SHAPES = [s for s in SHAPES if any(k in s[0] for k in os.environ["XG_GEMM_SHAPES"].split(","))]
 def run(mode):

@@ -2,7 +2,10 @@
 // part of the slab loop costs the matrix pipe its time (results are wrong in those builds; only the clock matters).
 #include "../../controllable_xgating_amd/csrc/xg_gemm.hip"
 #include <vector>
-int xgk_gemm_bf16(hipStream_t, int, bool, bool, int, int, int, const float*, int, const float*, int, float*, int, const float*, bool, bool) { return 0; }
+// (mode 0 only: the bf16 families' launchers and the scalar-load column sums are not linked in)
+int xgk_gemm_bs_launch(hipStream_t, const XgGemmRoute&, const XgGemmIn&, const XgGemmPtrs&) { return 0; }
+int xgk_gemm_g16(hipStream_t, const XgGemmRoute&, const XgGemmIn&, const XgGemmPtrs&) { return 0; }
+int xgk_colsum3(hipStream_t, const float*, int, int, int, float*, float*, float*) { return 0; }
 static float* dalloc(size_t n, float v) { float* p; (void)hipMalloc(&p, n * 4); std::vector<float> h(n, v);
     if (getenv("GEMM_RANDOM")) { unsigned x = 12345u; for (auto& f : h) { x = x * 1664525u + 1013904223u; f = ((x >> 8) * (1.0f / 16777216.0f) - 0.5f); } } (void)hipMemcpy(p, h.data(), n * 4, hipMemcpyHostToDevice); return p; }
 int main() {
