@@ -1073,13 +1073,23 @@ int xgk_gemm_clear(hipStream_t st, const XgGemmRoute& r, const XgGemmIn& in, flo
     return XG_OK;
 }
 
+#ifdef XG_DIAG
+int xgk_gemm_run(hipStream_t st, bool wide_forced, int mode, bool transA, bool transB, int M, int N, int K, int lda, int ldb, int ldc,
+                 bool relu, bool accumulate, const XgGemmPtrs& p, const XgGemmTuning* tune, XgGemmRoute* launched) {
+#else
 int xgk_gemm_run(hipStream_t st, bool wide_forced, int mode, bool transA, bool transB, int M, int N, int K, int lda, int ldb, int ldc,
                  bool relu, bool accumulate, const XgGemmPtrs& p) {
+#endif
     const auto align = [](const void* q) { return (int)((uintptr_t)q % 16); };
     const XgGemmIn in{mode & ~(XGK_GEMM_BG | XGK_GEMM_ALONE), wide_forced, transA, transB, M, N, K, lda, ldb, ldc,
                       align(p.A), align(p.B), align(p.C), p.bias != nullptr, relu, accumulate, p.cs[0] != nullptr,
                       (mode & XGK_GEMM_BG) != 0, (mode & XGK_GEMM_ALONE) != 0, p.A16 != nullptr, p.B16 != nullptr, align(p.A16), align(p.B16)};
+#ifdef XG_DIAG
+    const XgGemmRoute r = xg_gemm_plan(in, tune ? *tune : gemm_tuning());
+    if (launched) *launched = r;
+#else
     const XgGemmRoute r = xg_gemm_plan(in, gemm_tuning());
+#endif
     if (r.rc != XG_OK) return r.rc;
     if (r.colsum == XGR_CS_PASS) XG_TRY(xgk_colsum3(st, p.A, lda, K, M, p.cs[0], p.cs[1], p.cs[2]));      // (scalar-load kernels: separate pass)
     XG_TRY(xgk_gemm_clear(st, r, in, p.C));
@@ -1129,3 +1139,37 @@ extern "C" int xg_gemm(void* stream, int transA, int transB, int M, int N, int K
     return xgk_gemm((hipStream_t)stream, 0, transA != 0, transB != 0, M, N, K, A, lda, B, ldb, C, ldc, bias,
                     relu != 0, accumulate != 0);
 }
+
+#ifdef XG_DIAG
+// Diagnosis only (tests/test_gpu_gemm_variants.py; not in include/xgate.h): one product launched exactly as a planner input
+// describes it, through xgk_gemm_run like every other product, with the tuning of THIS call instead of the process's.
+//   in[14]:   mode wide_forced transA transB M N K lda ldb ldc relu accumulate bg alone (alignments, bias, colsum and the mirrors
+//             come from the pointers, as they always do)
+//   tune[19]: XgGemmTuning in the key order of tools/gemm_route_dump.cc: no_pk pk_min no_bg force_bg no_w1 w1_bm w1_bn force_tile
+//             force_splitk x3_fp32 no_td td_all td_ks td_depth no_bx no_g16 g16_cfg, then w1_tile and force (0 / 1: whether w1_bm /
+//             force_tile were named at all)
+//   route_out[26]: the route that was planned and launched: rc family planes bm bn bk vec fast a16 b16 splitk grid threads gm rounds
+//             tail_wgs ring cfg lds pad_lds clear r0 c0 rows cols colsum (XgGemmFamily / planes; the rectangle is zero unless
+//             clear == XGR_CLEAR_RECT)
+extern "C" int xg_debug_gemm_planned(void* stream, const int32_t* in, const int32_t* tune, const float* A, const void* A16, const float* B,
+                                     const void* B16, float* C, const float* bias, float* cs1, float* cs2, float* cs3, int32_t* route_out) {
+    if (!in || !tune || !route_out || !A || !B || !C) return XG_EINVAL;
+    const int mode = in[0], M = in[4], N = in[5], K = in[6];
+    if ((mode != 0 && mode != 1 && mode != 3) || M <= 0 || N <= 0 || K < 0) return XG_EINVAL;
+    XgGemmTuning t;
+    t.no_pk = tune[0] != 0; t.pk_min = tune[1]; t.no_bg = tune[2] != 0; t.force_bg = tune[3] != 0; t.no_w1 = tune[4] != 0;
+    t.w1_bm = tune[5]; t.w1_bn = tune[6]; t.force_tile = tune[7]; t.force_splitk = tune[8]; t.x3_fp32 = tune[9];
+    t.no_td = tune[10] != 0; t.td_all = tune[11]; t.td_ks = tune[12]; t.td_depth = tune[13]; t.no_bx = tune[14] != 0;
+    t.no_g16 = tune[15] != 0; t.g16_cfg = tune[16]; t.w1_tile = tune[17] != 0; t.force = t.force_ok = tune[18] != 0;
+    XgGemmRoute r;
+    const int rc = xgk_gemm_run((hipStream_t)stream, in[1] != 0, mode | (in[12] ? XGK_GEMM_BG : 0) | (in[13] ? XGK_GEMM_ALONE : 0),
+                                in[2] != 0, in[3] != 0, M, N, K, in[7], in[8], in[9], in[10] != 0, in[11] != 0,
+                                {A, B, C, bias, (const unsigned short*)A16, (const unsigned short*)B16, {cs1, cs2, cs3}}, &t, &r);
+    const bool rect = r.clear == XGR_CLEAR_RECT;
+    const int32_t out[26] = {r.rc, r.family, r.planes, r.bm, r.bn, r.bk, r.vec, r.fast, r.a16, r.b16, r.splitk, r.grid, r.threads, r.gm,
+                             r.rounds, r.tail_wgs, r.ring, r.cfg, r.lds, r.pad_lds, r.clear, rect ? r.r0 : 0, rect ? r.c0 : 0,
+                             rect ? r.rows : 0, rect ? r.cols : 0, r.colsum};
+    for (int i = 0; i < 26; ++i) route_out[i] = out[i];
+    return rc;
+}
+#endif

@@ -31,8 +31,14 @@ struct XgGemmPtrs {
     float* cs[3];                                              // column-sum accumulators, or null
 };
 // builds the planner's input, plans once and hands the route to its file's launcher (xg_gemm.hip)
+#ifdef XG_DIAG
+// (diagnosis build: `tune` replaces the process-wide tuning for this one call, `launched` receives the route -- xg_debug_gemm_planned)
+int xgk_gemm_run(hipStream_t st, bool wide_forced, int mode, bool transA, bool transB, int M, int N, int K, int lda, int ldb, int ldc,
+                 bool relu, bool accumulate, const XgGemmPtrs& p, const XgGemmTuning* tune = nullptr, XgGemmRoute* launched = nullptr);
+#else
 int xgk_gemm_run(hipStream_t st, bool wide_forced, int mode, bool transA, bool transB, int M, int N, int K, int lda, int ldb, int ldc,
                  bool relu, bool accumulate, const XgGemmPtrs& p);
+#endif
 int xgk_gemm_bs_launch(hipStream_t st, const XgGemmRoute& r, const XgGemmIn& in, const XgGemmPtrs& p);      // xg_gemm_bf16.hip: gemm_bs, gemm_bx
 // xg_gemm_g16.hip: both operands bf16 in memory, tiles by LDS-DMA (round 5)
 int xgk_gemm_g16(hipStream_t st, const XgGemmRoute& r, const XgGemmIn& in, const XgGemmPtrs& p);

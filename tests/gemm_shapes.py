@@ -1,7 +1,8 @@
 """The GEMM shape lists of the GPU tests and of tools/ubench/gemm_bench.py in one place, and the table of planner inputs
 (csrc/xg_gemm_route.h: xg_gemm_plan) that tools/gen_gemm_routes_golden.py records and tests/test_gemm_routes_cpu.py pins.
 
-A planner input is a dict of the keys tools/gemm_route_dump.cc reads (anything absent is 0 / the tuning default)."""
+A planner input is a dict of the keys tools/gemm_route_dump.cc reads (anything absent is 0 / the tuning default).  `cs` counts the
+column-sum accumulators (1 to 3): the planner only sees that there are some, tests/test_gpu_gemm_variants.py passes that many."""
 LAYOUT_CASES = [(0, 1), (0, 0), (1, 0), (1, 1)]                      # (ta, tb): NT forward, NN data gradient, TN weight gradient, TT
 EPILOGUES = ((0, 0), (1, 0), (0, 1))                                 # (relu, accumulate) every GEMM test runs
 
@@ -200,10 +201,83 @@ def threshold_inputs():
     return out
 
 
+# tests/test_gpu_gemm_routes.py: per family the cheapest shape its `cheapest` fixture finds -- (planner input of the public entry, bias,
+# (M, N, K), the layouts the planner routes to the family).  tests/test_gemm_routes_cpu.py recomputes this table from the planner.
+ENTRY_INPUTS = {"xg_gemm": dict(mode=0), "xg_gemm_mode_3": dict(mode=3, wide=1), "xg_gemm_mode_1": dict(mode=1, wide=1),
+                "xg_gemm_bf16_operands": dict(mode=1, wide=1, a16=1, b16=1)}
+CHEAPEST = {
+    "gemm_kernel": ("xg_gemm", 1, (1, 5, 7), [(0, 1), (0, 0), (1, 0), (1, 1)]),
+    "gemm_bs3": ("xg_gemm_mode_3", 1, (1, 5, 7), [(0, 1), (0, 0), (1, 0), (1, 1)]),
+    "gemm_bs1": ("xg_gemm_mode_1", 1, (1, 5, 7), [(0, 1), (0, 0), (1, 0), (1, 1)]),
+    "gemm_bx": ("xg_gemm_mode_1", 1, (256, 128, 64), [(0, 1), (0, 0)]),
+    "g16": ("xg_gemm_bf16_operands", 1, (136, 264, 200), [(0, 0), (1, 0), (1, 1)]),
+    "gemm_w1": ("xg_gemm", 1, (384, 2504, 512), [(0, 1), (0, 0), (1, 0), (1, 1)]),
+    "gemm_td": ("xg_gemm", 0, (3000, 3000, 256), [(1, 0)]),
+    "gemm_pk": ("xg_gemm", 1, (1280, 512, 20000), [(0, 1), (0, 0), (1, 0), (1, 1)]),
+}
+# the cheapest shape of gemm_kernel / gemm_bs1 / gemm_bs3 loads scalars (gemm_kernel: column sums in a separate pass; gemm_bs*: the one-row
+# branch of its column sums); this one takes 16-byte loads, the branch the model's shapes take, with M % 128 == 32
+COLSUM_VECTOR_SHAPE = (160, 64, 96)
+COLSUM_VECTOR_FAMILIES = ("gemm_kernel", "gemm_bs1", "gemm_bs3")
+
+
+def row_lengths(e):
+    """(A, B, C) row lengths in elements: the pitch an input has where it names none"""
+    return (e["M"] if e["ta"] else e["K"], e["K"] if e["tb"] else e["N"], e["N"])
+
+
+def pitched_inputs():
+    """The cheapest shape of every family (CHEAPEST), in every layout the family takes, as the model hands the library its
+    sub-blocks: pitches padded by 4 and by 8 elements (rows stay 16-byte loadable), by 1 (lda / ldb: the scalar-load kernels; ldc: a
+    tail rectangle that cannot be cleared, gemm_td refused), operands off the 16-byte grid -- and, in the weight-gradient layout,
+    the column sums into one, two and three accumulators (`cs` = their number) with M % 128 == 32, so that the clamped rows of the
+    last tile row have to stay out of the sums."""
+    out = []
+    for family in FAMILIES:
+        entry, bias, (M, N, K), layouts = CHEAPEST[family]
+        for ta, tb in layouts:
+            e = _p(M, N, K, ta, tb, bias=bias, **{k: v for k, v in ENTRY_INPUTS[entry].items()})
+            la, lb, lc = row_lengths(e)
+            for pad in (4, 8):
+                out.append(dict(e, lda=la + pad, ldb=lb + pad, ldc=lc + pad))
+            out.append(dict(e, lda=la + 1, ldb=lb + 1))
+            out.append(dict(e, ldc=lc + 1))
+            out += [dict(e, aA=4), dict(e, aB=8), dict(e, aC=4)]
+            if (ta, tb) == (1, 0):
+                shapes = [(M + (32 - M) % 128, N, K)] + ([COLSUM_VECTOR_SHAPE] if family in COLSUM_VECTOR_FAMILIES else [])
+                out += [dict(e, M=m, N=n, K=k, bias=0, acc=1, cs=ncs) for m, n, k in shapes for ncs in (1, 2, 3)]
+    return out
+
+
+VARIANT_FIELDS = ("rc", "family", "bm", "bn", "bk", "ta", "tb", "vec", "fast", "a16", "b16", "split", "clear", "colsum", "ring", "cfg",
+                  "pad_lds", "relu", "acc", "bias", "rounds", "tail", "padded", "ncs")
+
+
+def variant(e, route):
+    """What selects a template instance or a distinct code path inside a kernel: the key under which two table inputs run the same
+    code.  `route`: the planner's route of `e` as a dict of the recorded table's keys.  Fields: VARIANT_FIELDS."""
+    padded = any(e.get(k, 0) not in (0, n) for k, n in zip(("lda", "ldb", "ldc"), row_lengths(e)))
+    return (route["rc"], route["family"], route["bm"], route["bn"], route["bk"], e["ta"], e["tb"], route["vec"], route["fast"],
+            route["a16"], route["b16"], int(route["splitk"] > 1), route["clear"], route["colsum"], route["ring"], route["cfg"],
+            route["pad_lds"], e.get("relu", 0), e.get("acc", 0), e.get("bias", 0), int(route["rounds"] > 0), int(route["tail_wgs"] > 0),
+            int(padded), e.get("cs", 0))
+
+
+def variant_cases(golden):
+    """{variant: input} over the recorded table: per variant the input with the fewest M * N * K (ties: the smaller key(e))"""
+    best = {}
+    for e in table_inputs():
+        v = variant(e, dict(zip(golden["keys"], golden["routes"][key(e)])))
+        rank = (e["M"] * e["N"] * e["K"], key(e))
+        if v not in best or rank < best[v][0]:
+            best[v] = (rank, e)
+    return {v: e for v, (_, e) in best.items()}
+
+
 def table_inputs():
     """every input of the recorded table, each once, in a fixed order"""
     seen, out = set(), []
-    for e in [e for v in gpu_test_inputs().values() for e in v] + policy_inputs() + threshold_inputs():
+    for e in [e for v in gpu_test_inputs().values() for e in v] + policy_inputs() + threshold_inputs() + pitched_inputs():
         if key(e) not in seen:
             seen.add(key(e))
             out.append(e)
