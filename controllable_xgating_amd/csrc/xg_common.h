@@ -31,13 +31,20 @@ __host__ __device__ __forceinline__ uint32_t xg_hash(uint32_t seed, uint32_t sit
 }
 
 // Dropout descriptor passed by value to kernels.  scale == 1 and thresh == 0 when inactive.
+// split: the flat element index from which a SECOND realisation takes over -- element idx >= split draws from
+// (seed_hi, site, step, idx - split), i.e. what a call of its own under seed_hi would draw for element idx - split (the greedy
+// half of the one-pass SCST pair, include/xgate_pair.h).  XG_NO_SPLIT: one realisation (no element index reaches 2^32 - 1).
+constexpr uint32_t XG_NO_SPLIT = 0xFFFFFFFFu;
 struct XgDrop {
     uint32_t seed, site, step, thresh;
     float scale;
+    uint32_t seed_hi = 0u, split = XG_NO_SPLIT;
 };
 __host__ __forceinline__ XgDrop xg_make_drop(const XgRun* run, uint32_t site, uint32_t step) {
     XgDrop d;
     d.seed = run->seed;
+    d.seed_hi = run->seed;
+    d.split = XG_NO_SPLIT;
     d.site = site;
     d.step = step;
     if (run->train && run->drop_p > 0.f) {
@@ -53,7 +60,8 @@ __host__ __forceinline__ XgDrop xg_make_drop(const XgRun* run, uint32_t site, ui
 // multiplier (0 or scale) for flat element index idx
 __device__ __forceinline__ float xg_keep(const XgDrop& d, uint32_t idx) {
     if (d.thresh == 0u) return 1.0f;
-    return xg_hash(d.seed, d.site, d.step, idx) >= d.thresh ? d.scale : 0.0f;
+    const bool hi = idx >= d.split;
+    return xg_hash(hi ? d.seed_hi : d.seed, d.site, d.step, hi ? idx - d.split : idx) >= d.thresh ? d.scale : 0.0f;
 }
 
 // dropout sites (oracle/xgate_oracle.py header)

@@ -15,6 +15,7 @@
 #include "../../include/xgate_beam.h"
 #include "../../include/xgate_control.h"
 #include "../../include/xgate_beam_control.h"
+#include "../../include/xgate_pair.h"
 
 #include <new>
 #include <cstdlib>
@@ -573,7 +574,15 @@ struct StepIO {
     bool half_attn;       // stand-alone attention in its half-CU form (a background product runs beside the steps)
     int rows_per_video;   // 0: V / vproj hold one (K,.) block per row.  S > 0 (include/xgate_control.h): one per VIDEO, row / S; the attention is then the stand-alone group launch (xg_control.hip) in every tier
     const RollSelectArgs* sel;   // rollout steps t >= 1 (packed form, xt == null): the step's first launch CHOOSES the tokens (xg_select.h) and writes tok / mask / xt rows itself
+    int drop_split_rows; uint32_t drop_seed_hi;   // > 0 (include/xgate_pair.h): rows from this one on take their masks from drop_seed_hi, as rows 0 .. of a call of their own
 };
+
+// the step's dropout descriptor of one decoder site (5, 6, 7: element index row * R + col), with the second realisation when the step has one
+inline XgDrop step_drop(const XgRun& run, uint32_t site, const StepIO& s, int R) {
+    XgDrop d = xg_make_drop(&run, site, s.t);
+    if (s.drop_split_rows > 0) { d.seed_hi = s.drop_seed_hi; d.split = (uint32_t)s.drop_split_rows * (uint32_t)R; }
+    return d;
+}
 
 // the packed-weight form of the step needs 16-byte rows everywhere (R % 8 covers R; E and A are checked here)
 inline bool step_packed(const Ws& w, const XgDims& d) { return w.packed && d.R % 8 == 0 && d.E % 4 == 0 && d.A % 4 == 0; }
@@ -604,7 +613,7 @@ inline LstmFwdArgs cell_fwd_args(int layer, const StepIO& s, const XgRun& run, i
     a.c_prev = l1 ? s.c1 : s.c2; a.ldcp = R; a.h_prev = l1 ? s.h1 : s.h2; a.ldhp = R; a.mask = s.mask; a.ldm = s.ldm;
     a.gates = l1 ? s.g1 : s.g2; a.ldg = 4 * R; a.c_out = l1 ? s.c1o : s.c2o; a.ldco = R; a.h_out = l1 ? s.h1o : s.h2o; a.ldho = R;
     a.B = B; a.R = R; a.order = XG_ORDER_IFOG; a.mask_mode = XG_MASK_HOLD;
-    a.drop = xg_make_drop(&run, l1 ? XG_SITE_L1 : XG_SITE_L2, s.t);
+    a.drop = step_drop(run, l1 ? XG_SITE_L1 : XG_SITE_L2, s, R);
     return a;
 }
 
@@ -656,7 +665,7 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
         a2.h2a_b = p.h2a_b; a2.dgate_b = p.dgate_b; a2.l1_i2h_b = p.l1_i2h_b; a2.l1_a2h_b = p.l1_a2h_b; a2.l1_h2h_b = p.l1_h2h_b;
         a2.l2_i2h_b = p.l2_i2h_b; a2.l2_a2h_b = p.l2_a2h_b; a2.l2_h2h_b = p.l2_h2h_b;
         a2.ctr = w.dsync;
-        a2.drop_gate = xg_make_drop(&run, XG_SITE_DGATE, s.t); a2.drop_l1 = a.drop; a2.drop_l2 = c.drop;
+        a2.drop_gate = step_drop(run, XG_SITE_DGATE, s, R); a2.drop_l1 = a.drop; a2.drop_l2 = c.drop;
         return xgk_dstep(st, a2, w.gm);
     }
 #endif
@@ -681,7 +690,7 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
         j.epi = SK_EPI_GATE; j.nseg = 1;
         j.seg[0] = xt_seg(PK_DGATE, p.dgate_w); j.bias[0] = p.dgate_b;
         j.gate_t = s.pos; j.ldt = R; j.gate_y = s.posg; j.ldy = R;
-        j.drop = xg_make_drop(&run, XG_SITE_DGATE, s.t);
+        j.drop = step_drop(run, XG_SITE_DGATE, s, R);
     };
     auto p_job = [&](SkJob& j) {                          // p = h2a([h1 ; h2])                                               :677
         j = job_store(B, A, s.P, A, false);
@@ -823,7 +832,7 @@ int core_step(hipStream_t st, const XgDims& d, const XgParams& p, const XgRun& r
     if (!w.S || !w.S2) return XG_EINVAL;
     if (!s.pre1) {
         XG_TRY(xgk_linear(st, w.gm, B, R, E, s.xt, E, p.dgate_w, p.dgate_b, s.gp, R, true));
-        XG_TRY(xgk_gate_fwd(st, s.gp, R, s.pos, R, 0, s.posg, R, B, R, xg_make_drop(&run, XG_SITE_DGATE, s.t), B, 1 << 30, 1, B));
+        XG_TRY(xgk_gate_fwd(st, s.gp, R, s.pos, R, 0, s.posg, R, B, R, step_drop(run, XG_SITE_DGATE, s, R), B, 1 << 30, 1, B));
     }
     XG_TRY(xgk_gemm(st, w.gm, false, true, B, A, R, s.h1, R, p.h2a_w, 2 * R, s.P, A, p.h2a_b, false, false));
     XG_TRY(xgk_gemm(st, w.gm, false, true, B, A, R, s.h2, R, p.h2a_w + R, 2 * R, s.P, A, nullptr, false, true));
@@ -1731,6 +1740,9 @@ struct RolloutCall {
     RolloutForm form = RolloutForm::Plain;
     const XgDims* d1 = nullptr; Ws* enc = nullptr;      // PairVideos, RowsPerVideo: the videos' dims and the workspace their encoder runs in
     int rows_per_video = 0;                             // RowsPerVideo
+    // PairVideos under train-mode dropout (include/xgate_pair.h): rows [split, B) take every mask -- encoder and decoder -- from
+    // seed_greedy, as rows 0 .. of a call of their own (rollout_open_pair_videos_two_seeds; StepIO.drop_split_rows)
+    bool two_seeds = false; uint32_t seed_greedy = 0;
 };
 static RolloutCall pair_call(const float* uniforms, float temperature, int n_sample, float* logits_alt = nullptr) {
     RolloutCall c;
@@ -1763,6 +1775,29 @@ static int rollout_open_pair_videos(Streams& es, const XgDims& d1, const XgParam
     return xgk_compact(st, ca);
 }
 
+// The same rows under TWO dropout realisations (xgpr_rollout_pair_videos): the reference's two sample() calls in train mode draw
+// independent masks in the encoder as well, so the encoder, init_hidden and v2a(V) run once per seed on the d1.B videos -- under
+// run.seed in `enc`, where the sampled half's backward reads them, and under seed_greedy in the row prefix of `w`, whose results
+// then move to rows [m, 2m) before rows [0, m) are filled from `enc`.  Each pass makes its own running-statistics update (the
+// BatchNorm input does not depend on the masks: the two updates are the ones of the two calls).  Everything read is written first.
+static int rollout_open_pair_videos_two_seeds(Streams& es, const XgDims& d1, const XgParams& p, const XgBnState* bn, const XgBatch& x,
+                                              const XgRun& run, uint32_t seed_greedy, Ws& w, Ws& enc) {
+    hipStream_t st = es.main;
+    const size_t B1 = d1.B, N1 = B1 * d1.K, R = d1.R;
+    XG_TRY(encode_and_init(es, d1, p, bn, x, run, enc));
+    XgRun run_g = run; run_g.seed = seed_greedy;
+    XG_TRY(encode_and_init(es, d1, p, bn, x, run_g, w));
+    struct Half { float* dst; const float* lo; size_t n; };
+    const Half hv[6] = {{w.Venc, enc.Venc, N1 * R}, {w.vproj, enc.vproj, N1 * d1.A}, {w.H1, enc.H1, B1 * R}, {w.C1, enc.C1, B1 * R},
+                        {w.H2, enc.H2, B1 * R}, {w.C2, enc.C2, B1 * R}};
+    CompactArgs up{}, lo{};                       // two launches: the second overwrites what the first reads
+    auto put = [](CompactArgs& ca, float* dst, const float* src, size_t n) { ca.e[ca.n++] = CompactEntry{dst, src, (int64_t)n, (int64_t)n, (int64_t)n}; };
+    for (const Half& h : hv) { put(up, h.dst + h.n, h.dst, h.n); put(lo, h.dst, h.lo, h.n); }
+    for (int h = 0; h < 2; ++h) put(up, w.DPOSG + h * B1 * R, x.pos_feats, B1 * R);   // (a backward-only buffer, as in rollout_open_pair_videos)
+    XG_TRY(xgk_compact(st, up));
+    return xgk_compact(st, lo);
+}
+
 static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, const XgBnState* bn, const XgBatch* x,
                         const XgRun* run, Ws& w, int64_t* seq, float* seq_logp, int32_t* n_steps, RolloutCall& c) {
     const int B = d->B, R = d->R, E = d->E, T = d->T, mode = c.mode, split = c.split;
@@ -1775,7 +1810,10 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
     auto slot = [&](int t) { return rows ? 0 : t; };
     switch (c.form) {
     case RolloutForm::Plain: XG_TRY(encode_and_init(es, *d, *p, bn, *x, *run, w)); break;
-    case RolloutForm::PairVideos: XG_TRY(rollout_open_pair_videos(es, *c.d1, *p, bn, *x, *run, w, *c.enc)); break;
+    case RolloutForm::PairVideos:
+        if (c.two_seeds) XG_TRY(rollout_open_pair_videos_two_seeds(es, *c.d1, *p, bn, *x, *run, c.seed_greedy, w, *c.enc));
+        else XG_TRY(rollout_open_pair_videos(es, *c.d1, *p, bn, *x, *run, w, *c.enc));
+        break;
     case RolloutForm::RowsPerVideo: XG_TRY(videos_once(es, *c.d1, *p, bn, *x, *run, *c.enc, CapBeamRepeatArgs{}, state0, c.rows_per_video)); break;
     }
     XG_TRY(zero_dsync(st, w));
@@ -1819,6 +1857,7 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
             s.g1 = nullptr; s.g2 = nullptr; s.t = t; s.rows_per_video = c.rows_per_video;
         }
         if (in_step) { s.sel = &sel; s.xt = nullptr; s.tok = tok; }
+        if (c.two_seeds) { s.drop_split_rows = split; s.drop_seed_hi = c.seed_greedy; }
         // The reference runs the core once more at t = L and discards what it computes (SAModel.py:182,217: the loop ends before
         // those logits are ever read, and no state is returned): that step feeds neither an output nor a gradient and is not run.
         if (t + 1 == T) break;
@@ -1926,10 +1965,10 @@ extern "C" int xg_rollout_pair_compact(void* stream, const XgDims* d2, const XgP
     return compact_impl((hipStream_t)stream, d2, w, d1, b, c.used_alt);
 }
 
-extern "C" int xg_rollout_pair_videos(void* stream, const XgDims* d2, const XgParams* p, const XgBnState* bn, const XgBatch* x1,
-                                      const XgRun* run, const float* uniforms, float temperature, void* ws2, size_t ws2_bytes,
-                                      const XgDims* d1, void* ws1, size_t ws1_bytes, int compact, int64_t* seq, float* seq_logp,
-                                      int32_t* n_steps) {
+// seed_greedy: null for xg_rollout_pair_videos; else the second dropout realisation of xgpr_rollout_pair_videos (include/xgate_pair.h)
+static int pair_videos_impl(void* stream, const XgDims* d2, const XgParams* p, const XgBnState* bn, const XgBatch* x1, const XgRun* run,
+                            const uint32_t* seed_greedy, const float* uniforms, float temperature, void* ws2, size_t ws2_bytes,
+                            const XgDims* d1, void* ws1, size_t ws1_bytes, int compact, int64_t* seq, float* seq_logp, int32_t* n_steps) {
     Ws w, b;
     XG_TRY(check(d2, ws2, ws2_bytes, &w));
     XG_TRY(check(d1, ws1, ws1_bytes, &b));
@@ -1939,8 +1978,28 @@ extern "C" int xg_rollout_pair_videos(void* stream, const XgDims* d2, const XgPa
     attach_packed(b, *d1, run);
     RolloutCall c = pair_call(uniforms, temperature, d1->B, compact ? b.LOGITS : nullptr);
     c.form = RolloutForm::PairVideos; c.d1 = d1; c.enc = &b;
+    if (seed_greedy) { c.two_seeds = true; c.seed_greedy = *seed_greedy; }
     XG_TRY(rollout_impl((hipStream_t)stream, d2, p, bn, x1, run, w, seq, seq_logp, n_steps, c));
     return compact ? compact_impl((hipStream_t)stream, d2, w, d1, b, c.used_alt, true) : XG_OK;
+}
+
+extern "C" int xg_rollout_pair_videos(void* stream, const XgDims* d2, const XgParams* p, const XgBnState* bn, const XgBatch* x1,
+                                      const XgRun* run, const float* uniforms, float temperature, void* ws2, size_t ws2_bytes,
+                                      const XgDims* d1, void* ws1, size_t ws1_bytes, int compact, int64_t* seq, float* seq_logp,
+                                      int32_t* n_steps) {
+    return pair_videos_impl(stream, d2, p, bn, x1, run, nullptr, uniforms, temperature, ws2, ws2_bytes, d1, ws1, ws1_bytes, compact, seq,
+                            seq_logp, n_steps);
+}
+
+// include/xgate_pair.h
+extern "C" int xgpr_version(void) { return XGPR_VERSION; }
+
+extern "C" int xgpr_rollout_pair_videos(void* stream, const XgDims* d2, const XgParams* p, const XgBnState* bn, const XgBatch* x1,
+                                        const XgRun* run, uint32_t seed_greedy, const float* uniforms, float temperature, void* ws2,
+                                        size_t ws2_bytes, const XgDims* d1, void* ws1, size_t ws1_bytes, int compact, int64_t* seq,
+                                        float* seq_logp, int32_t* n_steps) {
+    return pair_videos_impl(stream, d2, p, bn, x1, run, &seed_greedy, uniforms, temperature, ws2, ws2_bytes, d1, ws1, ws1_bytes, compact,
+                            seq, seq_logp, n_steps);
 }
 
 // ================================================================== the captioner's device searches

@@ -718,9 +718,9 @@ struct SkSegHot { const float* A; const float* Bp; const int64_t* gather; int ld
 struct SkEpiIn { const float* bias[3]; const float* add; const float* c_prev; const float* h_prev; const float* mask;
                  int ldadd, ldcp, ldhp, ldm, accumulate, relu, order, mask_mode; const float* gate_t; int ldt, ldy; float* gate_y; };
 struct SkEpiOut { float* gates; float* c_out; float* h_out; int ldg, ldco, ldho, cell_cols; XgDrop drop; int pad_; };
-static_assert(sizeof(SkHeadBlk) == 64 && sizeof(SkSegHot) == 48 && sizeof(SkEpiIn) == 112 && sizeof(SkEpiOut) == 64, "descriptor blocks");
+static_assert(sizeof(SkHeadBlk) == 64 && sizeof(SkSegHot) == 48 && sizeof(SkEpiIn) == 112 && sizeof(SkEpiOut) == 72, "descriptor blocks");
 static_assert(offsetof(SkJob, tickets) == 56 && offsetof(SkSeg, sflags) == 44 && offsetof(SkJob, bias) + 112 == offsetof(SkJob, gates) &&
-              offsetof(SkJob, gate_y) + 8 == offsetof(SkJob, gates) && offsetof(SkJob, drop) + 20 <= offsetof(SkJob, gates) + 64,
+              offsetof(SkJob, gate_y) + 8 == offsetof(SkJob, gates) && offsetof(SkJob, drop) + sizeof(XgDrop) <= offsetof(SkJob, gates) + 72,
               "descriptor blocks mirror SkJob's layout (xg_kernels.h)");
 // The blocks are read as typed struct copies (adjacent scalar loads of one basic block are merged into s_load_dwordx8 / x4) and
 // HELD right behind the copy: an empty asm statement takes every field as an in/out scalar-register operand.  Two effects: all of
@@ -751,7 +751,7 @@ __device__ __forceinline__ void sk_hold(RollSelectArgs& q) {
 }
 __device__ __forceinline__ void sk_hold(SkEpiOut& e) {
     asm volatile("" : "+s"(e.gates), "+s"(e.c_out), "+s"(e.h_out), "+s"(e.ldg), "+s"(e.ldco), "+s"(e.ldho), "+s"(e.cell_cols), "+s"(e.drop.seed),
-                 "+s"(e.drop.site), "+s"(e.drop.step), "+s"(e.drop.thresh), "+s"(e.drop.scale));
+                 "+s"(e.drop.site), "+s"(e.drop.step), "+s"(e.drop.thresh), "+s"(e.drop.scale), "+s"(e.drop.seed_hi), "+s"(e.drop.split));
 }
 
 // ---- addressing of the fast kernel (round 5).  In-kernel stamps showed the launches' fixed parts to be INSTRUCTION-ISSUE bound: a

@@ -131,7 +131,7 @@ def _second_bn_update(bns, r0):
                 m.num_batches_tracked += 1
 
 
-def scst_rollouts(model, feat1, feat2, feat_mask, pos_feat, overlap=True, mode=None, uniforms=None, trim=True):
+def scst_rollouts(model, feat1, feat2, feat_mask, pos_feat, overlap=True, mode=None, uniforms=None, trim=True, one_pass=False):
     """The two rollouts of one SCST iteration (starttrain.py:131 + myutils.py:45-48): the sampled rollout (keeps its
     activations for the policy-gradient backward) and the greedy baseline.  They are independent given the batch:
       mode "batched" (default): ONE pass over 2m rows (rows [0,m) sample, rows [m,2m) greedy; SAModel.sample_pair) --
@@ -139,6 +139,8 @@ def scst_rollouts(model, feat1, feat2, feat_mask, pos_feat, overlap=True, mode=N
       mode "streams": two m-row rollouts on two streams;   mode "sequential": the reference's order.
     trim=False (batched mode): returns (gen (m,L), slp (m,L), greedy (m,L), n (2,) device int32) with NO host sync -- feed
     them to RewardCriterion(..., n=n[0]); the reference's trimmed views are gen[:, :n[0]] etc.
+    one_pass (batched mode): under train-mode dropout sample_pair otherwise runs two m-row rollouts; with it, one 2m-row pass
+    with a dropout seed per half (SAModel.sample_pair, docs/SCST_DROPOUT.md).  Without dropout it changes nothing.
     All three give the reference's results: both rollouts see the same batch statistics (BatchNorm's input does not
     depend on dropout, and statistics of a repeated batch equal those of the batch), and the running statistics receive
     the reference's TWO momentum updates (the second one is reconstructed exactly)."""
@@ -154,6 +156,8 @@ def scst_rollouts(model, feat1, feat2, feat_mask, pos_feat, overlap=True, mode=N
         return gen, slp, greedy
     bns = [model.two_spatial_encoder.visual_emb_rgb[1], model.two_spatial_encoder.visual_emb_opfl[1]]
     if mode == "batched":                                           # (the BatchNorm bookkeeping of the pair is sample_pair's)
+        if one_pass:
+            s_opt["one_pass"] = True
         gen, slp, greedy, n = model.sample_pair(feat1, feat2, feat_mask, pos_feat, s_opt)
         if not trim:                                                # no host sync at all: full-width tensors + device-side n
             return gen, slp, greedy, n

@@ -379,10 +379,20 @@ class SAModel(FlatParams, nn.Module):
         In train mode the BatchNorm running statistics end up exactly where the reference's TWO sample() calls leave
         them (two momentum updates with the unbiased N/(N-1) variance of the un-repeated batch).  With train-mode dropout
         (drop_prob_lm > 0) the two rollouts run as two calls with independent masks, like the reference's -- unless
-        self.dropout_seed is set: then both calls take that one seed and so the same masks (a checker regenerates both from it)."""
+        self.dropout_seed is set: then both calls take that one seed and so the same masks (a checker regenerates both from it).
+        opt["one_pass"] (train-mode dropout only; inert otherwise): the two rollouts still run as ONE 2m-row pass, each half under
+        its own seed -- the two seeds the two calls would take, drawn in the same order (docs/SCST_DROPOUT.md).
+        opt["return_greedy_logprobs"]: the greedy rollout's (m,L) log-probs as a fifth value."""
         temperature = float(opt.get("temperature", 1.0))
         params = self._param_list()
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        want_glp = bool(opt.get("return_greedy_logprobs", False))
+        if self.training and self.drop_prob_lm > 0.0 and opt.get("one_pass", False):
+            # ... in ONE 2m-row pass all the same (docs/SCST_DROPOUT.md): the library gives rows [m, 2m) the masks of a call of their
+            # own under a second seed and runs the encoder once per seed (xgpr_rollout_pair_videos)
+            out = _RolloutPairFunction.apply(self, feats_rgb, feats_opfl, feat_mask, pos_feats, opt.get("uniforms", None),
+                                             temperature, need_grad, True, *params)
+            return out if want_glp else out[:4]
         if self.training and self.drop_prob_lm > 0.0:
             # Train-mode dropout: the reference's two sample() calls (starttrain.py:131, myutils.py:45) draw INDEPENDENT masks,
             # in the encoder and img_embed as well as in the decoder.  The one-batch form below runs the encoder once and would
@@ -392,11 +402,13 @@ class SAModel(FlatParams, nn.Module):
             gen, slp, n_s = _RolloutFunction.apply(self, feats_rgb, feats_opfl, feat_mask, pos_feats, nv.XG_ROLLOUT_SAMPLE, uni,
                                                    None, temperature, need_grad, True, *params)
             with torch.no_grad():
-                greedy, _, n_g = _RolloutFunction.apply(self, feats_rgb, feats_opfl, feat_mask, pos_feats, nv.XG_ROLLOUT_GREEDY,
-                                                        None, None, 1.0, False, True, *params)
-            return gen, slp, greedy, torch.cat([n_s.reshape(1), n_g.reshape(1)])
-        return _RolloutPairFunction.apply(self, feats_rgb, feats_opfl, feat_mask, pos_feats, opt.get("uniforms", None),
-                                          temperature, need_grad, *params)
+                greedy, glp, n_g = _RolloutFunction.apply(self, feats_rgb, feats_opfl, feat_mask, pos_feats, nv.XG_ROLLOUT_GREEDY,
+                                                          None, None, 1.0, False, True, *params)
+            out = (gen, slp, greedy, torch.cat([n_s.reshape(1), n_g.reshape(1)]))
+            return out + (glp,) if want_glp else out
+        out = _RolloutPairFunction.apply(self, feats_rgb, feats_opfl, feat_mask, pos_feats, opt.get("uniforms", None),
+                                         temperature, need_grad, False, *params)
+        return out if want_glp else out[:4]
 
     def init_hidden(self, feat, feat_mask):
         """SAModel.init_hidden (SAModel.py:58-65) -> [(h1,c1),(h2,c2)], each (1,m,R)."""
@@ -790,10 +802,13 @@ class _RolloutFunction(torch.autograd.Function):
 
 class _RolloutPairFunction(torch.autograd.Function):
     """Sampled rollout + greedy baseline of one SCST iteration as ONE batch of 2m rows (xg_rollout_pair); the sampled
-    half's activations are compacted into an m-row workspace, so backward is xg_rollout_bwd of the sampled rollout alone."""
+    half's activations are compacted into an m-row workspace, so backward is xg_rollout_bwd of the sampled rollout alone.
+    two_seeds (train-mode dropout): a dropout seed per half (xgpr_rollout_pair_videos, include/xgate_pair.h); the backward is the
+    same one, since the sampled rows keep the first seed and the element indices of an m-row call.
+    Returns (gen, sample_logprobs, greedy, n, greedy_logprobs)."""
 
     @staticmethod
-    def forward(ctx, model, feats_rgb, feats_opfl, feat_mask, pos_feats, uniforms, temperature, need_grad, *params):
+    def forward(ctx, model, feats_rgb, feats_opfl, feat_mask, pos_feats, uniforms, temperature, need_grad, two_seeds, *params):
         B, K, _ = feats_rgb.shape
         T = model.seq_length + 1
         dev = feats_rgb.device
@@ -816,24 +831,29 @@ class _RolloutPairFunction(torch.autograd.Function):
         # rollout + compaction of the sampled half into the m-row workspace (what the backward reads) as one call: the encoder
         # runs there in the first place, and the sampled rows' logits are written there by the rollout itself
         ws1, wp1, wn1 = _take_workspace(model, d1, dev, need_grad)
-        nv.check(nv.lib().xg_rollout_pair_videos(_stream(), C.byref(d2), C.byref(ps), C.byref(bn), C.byref(b1), C.byref(run),
-                                                 nv.ptr(uniforms), temperature, wp2, wn2, C.byref(d1), wp1, wn1, 1 if need_grad else 0,
-                                                 nv.ptr(seq), nv.ptr(slp), nv.ptr(n)), "xg_rollout_pair_videos")
+        tail = (nv.ptr(uniforms), temperature, wp2, wn2, C.byref(d1), wp1, wn1, 1 if need_grad else 0, nv.ptr(seq), nv.ptr(slp), nv.ptr(n))
+        head = (_stream(), C.byref(d2), C.byref(ps), C.byref(bn), C.byref(b1), C.byref(run))
+        if two_seeds:
+            # the greedy call's seed: the NEXT one of the model's counter, as when the two rollouts run as two calls (sampled first)
+            from . import _native_pair as npr
+            nv.check(npr.lib().xgpr_rollout_pair_videos(*head, model._run(False).seed, *tail), "xgpr_rollout_pair_videos")
+        else:
+            nv.check(nv.lib().xg_rollout_pair_videos(*head, *tail), "xg_rollout_pair_videos")
         if not need_grad:
             ws1 = None
         model._bump_bn(2)                         # two sample() calls of the reference: two running-statistics updates (in the library)
         ctx.model, ctx.d, ctx.ws, ctx.run, ctx.need_grad = model, d1, ws1, run, need_grad
         ctx.keep = (feats_rgb, feats_opfl, feat_mask, pos_feats)
         gen, greedy = seq[:B], seq[B:]
-        slp_s = slp[:B]
-        ctx.mark_non_differentiable(gen, greedy, n)
+        slp_s, slp_g = slp[:B], slp[B:]
+        ctx.mark_non_differentiable(gen, greedy, n, slp_g)
         if not need_grad:
             ctx.mark_non_differentiable(slp_s)
-        return gen, slp_s, greedy, n
+        return gen, slp_s, greedy, n, slp_g
 
     @staticmethod
-    def backward(ctx, dgen, dslp, dgreedy, dn):
-        return _rollout_backward(ctx, dslp, 8)
+    def backward(ctx, dgen, dslp, dgreedy, dn, dglp):
+        return _rollout_backward(ctx, dslp, 9)
 
 
 # ====================================================================== criteria
