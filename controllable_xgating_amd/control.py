@@ -112,6 +112,34 @@ def beam_captions_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, fe
     return seq, seq_logp, score, tag_logp.sum(2)
 
 
+def score_captions_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, captions, cross=False):
+    """Score GIVEN captions of each of the B videos under its S POS templates, on one captioner encoder pass: (tok_logp, score,
+    count, template_score (B,S)).  The forced POS rollout (``pos_model.sample_forced``) leaves `pos_feats` (B*S,R) on the device and
+    ``cap_model.score_captions_per_video`` (include/xgate_score.h; `captions` (B,N,L'), `cross` and the three results as there:
+    (B,S,..) for caption s under template s, (B,S,N,..) with cross=True for every caption under every template) takes the B videos
+    once; nothing is read back between the two or after them.  `templates` as in ``caption_with_templates``.  Inference only: both
+    models run under ``torch.no_grad()``."""
+    with torch.no_grad():
+        tag_logp, _, _, pos_feats = pos_model.sample_forced(feats_rgb, feats_opfl, feat_mask, templates, collect_states=False,
+                                                            trim=False)
+        B, S = tag_logp.shape[:2]
+        tok_logp, score, count = cap_model.score_captions_per_video(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(B, S, -1),
+                                                                    captions, cross=cross)
+    return tok_logp, score, count, tag_logp.sum(2)
+
+
+def template_recovery(score):
+    """(B,S) bool for a cross score (B,S,S) -- ``score[b, s, n]``: caption n under template s, as ``score_captions_per_video(...,
+    cross=True)`` returns it for the S captions generated under the S templates: True where caption s is most likely under ITS OWN
+    template s, i.e. no other template gives it a higher score (a tie with another template still counts as recovered).  Torch ops
+    on the tensor's device; nothing is read back."""
+    t = torch.as_tensor(score)
+    if t.dim() != 3 or t.shape[1] != t.shape[2]:
+        raise ValueError("score (B,S,S) expected, got %s" % (tuple(t.shape),))
+    own = torch.diagonal(t, dim1=1, dim2=2)                                  # (B,S): caption s under template s
+    return own >= t.max(dim=1).values                                        # ... against its best template
+
+
 def first_occurrences(templates):
     """(B,S) bool for templates (B,S,L): True where no EARLIER template of the same video is identical (slot 0 always is), so
     ``templates[first]`` are a video's distinct templates in the order they were drawn.  Torch ops on the tensor's device; nothing

@@ -390,6 +390,23 @@ struct CapBeamMergeArgs {
 int xgk_cap_beam_merge(hipStream_t st, int B, CapBeamMergeArgs a);
 int xgk_cap_beam_backtrace(hipStream_t st, int B, const BeamBook<int64_t>& book, int64_t* seq, float* seq_logp, float* score);
 
+// ---- xg_score.hip: scoring given captions (include/xgate_score.h)
+// Per row b Q + q of tokens (M, L) int64, clamped into [0, V): fed (L, M) the token step j consumes (BOS = 0 at j = 0), tgt (L, M)
+// the token step j is scored on, unf (L, M) 1 while every token before column j is non-zero, count (M) = the counted columns
+int xgk_score_prep(hipStream_t st, const int64_t* tokens, int M, int L, int V, int64_t* fed, int32_t* tgt, float* unf, int32_t* count);
+constexpr int XGK_SCORE_TILE = 32;               // vocabulary columns per tile statistic of the fast form
+int xgk_score_tiles(int R, int V, const float* H, const float* W);     // tile statistics per row: cdiv(V, 32) in the fast form, else 1
+// rows x R hidden rows against the (V, R) logit weights WITHOUT the rows x V logits: part[(tile * rows + row) * 2 + {0, 1}] = the
+// tile's max and sum exp(x - max) of the row, tlogit[row] = the logit of column tgt[row] (written by the tile that owns it)
+int xgk_score_part(hipStream_t st, int rows, int R, int V, const float* H, const float* W, const float* bias, const int32_t* tgt,
+                   float* part, float* tlogit);
+// the reduce over the tiles of `steps` steps of M rows (chunk rows s M + m, columns step0 + s of the output):
+// tok_logp[m L + j] = j < count[m] ? tlogit - log-sum-exp : 0
+int xgk_score_reduce(hipStream_t st, const float* part, const float* tlogit, int ntiles, int M, int L, int step0, int steps,
+                     const int32_t* count, float* tok_logp);
+// score[m] = sum_j tok_logp[m L + j], in column order
+int xgk_score_sum(hipStream_t st, const float* tok_logp, int M, int L, float* score);
+
 // ---- xg_optim.hip
 int xgk_clip_adam(hipStream_t st, int64_t n, float* p, float* g, float* m, float* v, float lr, float b1, float b2,
                   float eps, float wd, int step, float clip, bool zero_grad = false);

@@ -14,6 +14,7 @@
 #include "xg_kernels.h"
 #include "../../include/xgate_beam.h"
 #include "../../include/xgate_control.h"
+#include "../../include/xgate_score.h"
 #include "../../include/xgate_beam_control.h"
 #include "../../include/xgate_pair.h"
 
@@ -2025,8 +2026,9 @@ struct BeamWs : SearchWs {
 
 inline XgDims beam_dims(const XgDims& d, int B) { XgDims e = d; e.B = B; e.T = 1; return e; }
 
-// The shared head over M step rows; the returned carver stands behind it.  whole_scratch: carve_step_scratch
-Carver search_carve(const XgDims& d, size_t M, bool whole_scratch, void* base, SearchWs& w) {
+// The shared head over M step rows; the returned carver stands behind it.  whole_scratch: carve_step_scratch; logits == false: a
+// caller that never holds a step's raw logits (sc_carve)
+Carver search_carve(const XgDims& d, size_t M, bool whole_scratch, void* base, SearchWs& w, bool logits = true) {
     w.enc = carve(beam_dims(d, d.B), base);
     w.enc.sh16 = nullptr; w.enc.bytes = w.enc.core_bytes;          // fp32 only: no bf16 mirror region
     Carver c{static_cast<char*>(base), w.enc.core_bytes};
@@ -2035,7 +2037,7 @@ Carver search_carve(const XgDims& d, size_t M, bool whole_scratch, void* base, S
     carve_step_scratch(c, s, M, R, whole_scratch);
     s.Xe = c.take<float>(M * E); s.GP = c.take<float>(M * R); s.POSG = c.take<float>(M * R);
     s.P = c.take<float>(M * A); s.ALPHA = c.take<float>(M * K); s.AF = c.take<float>(M * R);
-    s.LOGITS = c.take<float>(M * V);                               // one step's raw logits
+    if (logits) s.LOGITS = c.take<float>(M * V);                   // one step's raw logits
     return c;
 }
 
@@ -2192,6 +2194,107 @@ extern "C" int xgcc_rollout(void* stream, const XgDims* d, int32_t S, const XgPa
     c.mode = mode; c.uniforms = uniforms; c.temperature = temperature; c.split = M;
     c.form = RolloutForm::RowsPerVideo; c.d1 = &de; c.enc = &w.enc; c.rows_per_video = S;
     return rollout_impl((hipStream_t)stream, &dm, p, bn, x, run, w.step, seq, seq_logp, n_steps, c);
+}
+
+// ---- scoring given captions (include/xgate_score.h): Q caption rows per video, M = B Q rows, the videos once (videos_once) and
+// core_step in its rows-per-video form, as in the rollout above.  The tokens are known up front: one launch (xgk_score_prep) leaves
+// what every step feeds (`fed`), is scored on (`tgt`) and masks by (`unf`), and the rows' counted columns.  The loop is then L
+// core_steps with nothing between them -- the reference's dead last step is not run -- and the vocabulary side (xg_score.hip: tile
+// statistics + reduce, no logits; the rows' scores behind the last chunk) follows it in chunks of SC_CHUNK whole steps on the
+// auxiliary stream.  h2' lives in a ring of 2 SC_CHUNK + 1 row blocks: block 0 is the initial state, step t writes block
+// 1 + t % (2 SC_CHUNK), so a chunk's rows are contiguous and the loop only waits for the chunk two behind it before it overwrites
+// that chunk's blocks.  The tile statistics are one chunk's: the chunks follow each other on one stream.  The embedding rows of all
+// steps are not materialised (L E floats per row would pass the workspace bound of include/xgate_score.h on their own with the
+// rest): the packed step gathers them by `fed` inside its products, the other forms take one gather launch per step.
+namespace {
+
+constexpr int SC_CHUNK = 3;
+struct ScoreWs : SearchWs {
+    float* h2;                     // (2 SC_CHUNK + 1, M, R)
+    int64_t* fed; int32_t* tgt; float* unf;      // (L, M) each
+    float *part, *tlogit;          // one chunk: (tiles, SC_CHUNK M, 2), (SC_CHUNK M)
+};
+
+ScoreWs sc_carve(const XgDims& d, int Q, void* base) {
+    ScoreWs w{};
+    const size_t M = (size_t)d.B * Q, R = d.R, L = d.T - 1, nt = xg_cdiv(d.V, XGK_SCORE_TILE);
+    Carver c = search_carve(d, M, false, base, w, /*logits=*/false);
+    Ws& s = w.step;
+    s.H1 = c.take<float>(2 * M * R); s.C1 = c.take<float>(2 * M * R); s.C2 = c.take<float>(2 * M * R);
+    w.h2 = c.take<float>((2 * SC_CHUNK + 1) * M * R);
+    w.fed = c.take<int64_t>(L * M); w.tgt = c.take<int32_t>(L * M); w.unf = c.take<float>(L * M);
+    w.part = c.take<float>(nt * SC_CHUNK * M * 2); w.tlogit = c.take<float>(SC_CHUNK * M);
+    w.bytes = (c.off + 255) & ~(size_t)255;
+    return w;
+}
+
+}  // namespace
+
+extern "C" int xgsc_version(void) { return XGSC_VERSION; }
+
+extern "C" size_t xgsc_workspace_bytes(const XgDims* d, int32_t Q) {
+    return cc_dims_ok(d, Q) ? sc_carve(*d, Q, nullptr).bytes : 0;
+}
+
+extern "C" int xgsc_score_captions(void* stream, const XgDims* d, int32_t Q, const XgParams* p, const XgBnState* bn, const XgBatch* x,
+                                   const XgRun* run, const int64_t* tokens, float* tok_logp, float* score, int32_t* count, void* ws,
+                                   size_t ws_bytes) {
+    if (!cc_dims_ok(d, Q) || !ws) return XG_EINVAL;
+    ScoreWs w = sc_carve(*d, Q, ws);
+    if (ws_bytes < w.bytes) return XG_EWORKSPACE;
+    XG_TRY(search_args(true, p, bn, x, run, tokens, tok_logp, score, ws));
+    if (!count) return XG_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = d->B, M = B * Q, R = d->R, E = d->E, V = d->V, L = d->T - 1;
+    const XgDims de = beam_dims(*d, B);
+    XgDims dm = *d; dm.B = M;
+    attach_packed(w.enc, de, run);
+    attach_packed(w.step, dm, run);
+    if (!step_scratch_ok(w.step, false, true)) return XG_EINVAL;
+    Streams ss(st, run);
+    const size_t MR = (size_t)M * R;
+    float* const state0[4] = {w.step.H1, w.step.C1, w.h2, w.step.C2};
+    XG_TRY(videos_once(ss, de, *p, bn, *x, *run, w.enc, CapBeamRepeatArgs{}, state0, Q));
+    XG_TRY(xgk_score_prep(st, tokens, M, L, V, w.fed, w.tgt, w.unf, count));
+    XG_TRY(zero_dsync(st, w.step));
+    const bool pk = step_packed(w.step, dm);
+    const int ntiles = xgk_score_tiles(R, V, w.h2, p->logit_w);
+    int done = 0, marks[2] = {-1, -1};                    // steps whose scoring is under way; the end of the last two chunks on aux
+    XG_TRY(record_prof(run->prof_event0, st));
+    for (int t = 0; t < L; ++t) {
+        // the first step of a chunk overwrites the h2' blocks of the chunk two behind it: that chunk's scoring has to be through
+        if (t % SC_CHUNK == 0 && t >= 2 * SC_CHUNK) XG_TRY(ss.wait_mark(marks[(t / SC_CHUNK) & 1]));
+        StepIO s{};
+        if (pk) s.tok = w.fed + (size_t)t * M;            // token rows gathered by index inside the products
+        else {
+            XG_TRY(xgk_embed_gather(st, p->embed_w, E, w.fed + (size_t)t * M, M, 1, 0, M, V, w.step.Xe, E));
+            s.xt = w.step.Xe;
+        }
+        const size_t in = (size_t)(t & 1) * MR, out = (size_t)((t + 1) & 1) * MR;
+        s.pos = x->pos_feats; s.gp = w.step.GP; s.posg = w.step.POSG; s.pre1 = nullptr; s.mask = w.unf + (size_t)t * M; s.ldm = 1;
+        s.h1 = w.step.H1 + in; s.c1 = w.step.C1 + in; s.c2 = w.step.C2 + in;
+        s.h1o = w.step.H1 + out; s.c1o = w.step.C1 + out; s.c2o = w.step.C2 + out;
+        s.h2 = w.h2 + (t == 0 ? 0 : 1 + (t - 1) % (2 * SC_CHUNK)) * MR;
+        s.h2o = w.h2 + (1 + t % (2 * SC_CHUNK)) * MR;
+        s.P = w.step.P; s.alpha = w.step.ALPHA; s.af = w.step.AF; s.g1 = nullptr; s.g2 = nullptr; s.t = t;
+        s.rows_per_video = Q;
+        XG_TRY(core_step(st, dm, *p, *run, w.step, w.enc.Venc, w.enc.vproj, s));
+        const int n = t + 1;                              // steps finished
+        if (n % SC_CHUNK == 0 || n == L) {
+            const int steps = n - done, rows = steps * M;
+            const float* Hc = w.h2 + (1 + done % (2 * SC_CHUNK)) * MR;
+            XG_TRY(ss.fork());
+            XG_TRY(xgk_score_part(ss.aux, rows, R, V, Hc, p->logit_w, p->logit_b, w.tgt + (size_t)done * M, w.part, w.tlogit));
+            XG_TRY(xgk_score_reduce(ss.aux, w.part, w.tlogit, ntiles, M, L, done, steps, count, tok_logp));
+            if (n == L) XG_TRY(xgk_score_sum(ss.aux, tok_logp, M, L, score));
+            const int mk = ss.mark();
+            if (mk == -2) return XG_EHIP;
+            marks[(done / SC_CHUNK) & 1] = mk;
+            done = n;
+        }
+    }
+    XG_TRY(record_prof(run->prof_event1, st));
+    return ss.join();
 }
 
 extern "C" int xg_rollout_bwd(void* stream, const XgDims* d, const XgParams* p, const XgParams* g, const XgBatch* x,

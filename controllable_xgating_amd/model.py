@@ -642,6 +642,56 @@ class SAModel(FlatParams, nn.Module):
         out = (seq, seq_logp, score)
         return out + (trace,) if return_trace else out
 
+    def score_captions_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, captions, cross=False):
+        """The log-probability the captioner gives GIVEN captions, on ONE encoder pass (include/xgate_score.h): the B videos are
+        handed over once, `pos_feats` is (B,S,R) and `captions` (B,N,L') integer tokens with L' <= seq_length, zero = EOS (padded
+        with zeros to L = seq_length on their own device).  A row's result is what ``sample`` with `forced_tokens` gives on the
+        batch with every video repeated per row: tok_logp, the untempered log-probability of token j at step j in the COUNTED
+        columns -- column 0 and every column whose preceding tokens are all non-zero; the first EOS is counted -- and 0 elsewhere;
+        count (int32), the number of counted columns; score, the sum of tok_logp.
+
+        cross=False: caption s is scored under template s (N == S) -> (tok_logp (B,S,L), score (B,S), count (B,S)).
+        cross=True: every caption under every template, rows ordered (b, s, n) -> (B,S,N,L), (B,S,N), (B,S,N).
+
+        Eval mode, fp32 and device tensors only; one enqueue, nothing here synchronises with the host, token values are clamped
+        into [0, vocab_size) by the kernels and nothing returned carries an autograd graph."""
+        from . import _native_score as nsc
+        inputs = (feats_rgb, feats_opfl, feat_mask, pos_feats)
+        # the captions' own checks come before the device gate of _search_open (they hold on any device), behind the mode's
+        self._search_gate("score_captions_per_video")
+        cap, B, L = captions, feats_rgb.shape[0], self.seq_length
+        if not torch.is_tensor(cap) or cap.is_floating_point() or cap.is_complex() or cap.dtype == torch.bool:
+            raise ValueError("captions are integer tokens")
+        if cap.dim() != 3 or cap.shape[0] != B or cap.shape[1] < 1:
+            raise ValueError("captions (B = %d, N, L') expected, got %s" % (B, tuple(cap.shape)))
+        N = int(cap.shape[1])
+        if cap.shape[2] > L:
+            raise ValueError("captions have %d tokens, seq_length is %d" % (cap.shape[2], L))
+        if not cross and pos_feats.dim() == 3 and N != pos_feats.shape[1]:
+            raise ValueError("%d captions per video for %d templates: N == S expected (cross=True scores every caption under every "
+                             "template)" % (N, pos_feats.shape[1]))
+        B, K, S, L, dev, d = self._search_open("score_captions_per_video", inputs, True)
+        self._search_gate("score_captions_per_video", cap)
+        with torch.no_grad():
+            cap = torch.nn.functional.pad(cap.detach().long(), (0, L - cap.shape[2]))
+            pos = pos_feats.detach()
+            if cross:                                    # rows (b, s, n): template s with caption n
+                pos = pos.unsqueeze(2).expand(B, S, N, pos.shape[2]).reshape(B, S * N, pos.shape[2])
+                cap = cap.unsqueeze(1).expand(B, S, N, L).reshape(B, S * N, L)
+            cap = cap.contiguous()
+        Q = S * N if cross else S
+        lib = nsc.lib()
+        args, wp, wn, keep = self._search_call("_score_ws", (B, K, L, Q, str(dev)), lambda: lib.xgsc_workspace_bytes(C.byref(d), Q),
+                                               "xgsc_workspace_bytes: invalid dims or too many rows (B %d, Q %d)" % (B, Q),
+                                               inputs[:3] + (pos,))
+        shape = (B, S, N) if cross else (B, S)
+        tok_logp = torch.empty(*shape, L, dtype=torch.float32, device=dev)
+        score = torch.empty(*shape, dtype=torch.float32, device=dev)
+        count = torch.empty(*shape, dtype=torch.int32, device=dev)
+        nv.check(lib.xgsc_score_captions(_stream(), C.byref(d), Q, *args, nv.ptr(cap), nv.ptr(tok_logp), nv.ptr(score), nv.ptr(count),
+                                         wp, wn), "xgsc_score_captions")
+        return tok_logp, score, count
+
 
 # ====================================================================== autograd glue
 def _grads_struct(model, device=None):
