@@ -10,7 +10,9 @@ captions under them.  Eval mode, fp32, one GPU.  By default the captioner runs o
 template; ``share_encoder=True`` hands the videos over once (``SAModel.sample_per_video``, include/xgate_control.h): the captioner's
 encoder, init_hidden and v2a(V) then run once per video and a step's attention reads them once per group of a video's templates.
 ``beam_captions_with_templates`` is the captioner's BEAM SEARCH under the templates on one encoder pass
-(``SAModel.beam_captions_per_video``, include/xgate_beam_control.h).
+(``SAModel.beam_captions_per_video``, include/xgate_beam_control.h).  All of that steers; ``beam_captions_following_templates``
+GUARANTEES: the same search admitting at position t only words whose POS category the template allows there
+(``SAModel.beam_captions_allowed``, include/xgate_beam_allow.h; ``allow_masks`` builds the sets, ``template_adherence`` checks a result).
 """
 from __future__ import annotations
 
@@ -110,6 +112,108 @@ def beam_captions_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, fe
         seq, seq_logp, score = cap_model.beam_captions_per_video(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(B, S, -1),
                                                                  beam_size=beam_size, suppress_token=suppress_token)
     return seq, seq_logp, score, tag_logp.sum(2)
+
+
+ANY_WORD = 0xFFFFFFFF                       # the mask that admits every category
+
+
+def _mask_of(tag):
+    """One position of a nested-list constraint: a tag, or -1 (any word)."""
+    c = int(tag)
+    if not -1 <= c < 32:
+        raise ValueError("tags must lie in [-1, 32), got %d" % c)
+    return ANY_WORD if c < 0 else 1 << c
+
+
+def allow_masks(constraints, seq_length, built=False):
+    """Per-position sets of admitted POS categories as the (B,S,L) int64 tensor of uint32 masks ``SAModel.beam_captions_allowed``
+    takes, L = seq_length (include/xgate_beam_allow.h: bit c set = category c admitted).
+
+    `constraints`: integer tags (B,S,L') or (B,L'), L' <= L, as an array / tensor or as nested lists ``[video][template][tag]``
+    (ragged in the last level; ``[video][tag]``: one template per video).  A tag c becomes ``1 << c`` and -1 becomes 0xFFFFFFFF (any
+    word).  Positions behind the last one are padded with tag 0's mask, 1: only words of the end category.  ``built=True``:
+    `constraints` already holds masks, (B,S,L) integers -- the way to a set of several categories ("noun or adjective": two
+    bits) --; it passes through as int64.  Raises ValueError for L' > L, a video with another number of templates than the
+    first, and a tag outside [-1, 32).  A tensor that already lives on the GPU is converted there and its tags are NOT read (that
+    would synchronise): they are taken modulo 32, negative ones as -1."""
+    L = int(seq_length)
+    if built:
+        t = torch.as_tensor(constraints)
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError("masks are integers")
+        if t.dim() != 3 or t.shape[2] != L:
+            raise ValueError("masks (B,S,L = %d) expected, got %s" % (L, tuple(t.shape)))
+        return t.long().contiguous()
+    if _is_seq(constraints):
+        rows = list(constraints)
+        if not rows:
+            raise ValueError("no constraints")
+        if not any(_is_seq(v) for r in rows for v in r):
+            rows = [[r] for r in rows]                      # [video][tag]: one template per video
+        S = len(rows[0])
+        if S < 1:
+            raise ValueError("every video needs at least one template")
+        out = np.ones((len(rows), S, L), dtype=np.int64)
+        for b, r in enumerate(rows):
+            if len(r) != S:
+                raise ValueError("video %d has %d templates, video 0 has %d" % (b, len(r), S))
+            for s, tags in enumerate(r):
+                if len(tags) > L:
+                    raise ValueError("template %d of video %d has %d tags, seq_length is %d" % (s, b, len(tags), L))
+                out[b, s, :len(tags)] = [_mask_of(e) for e in tags]
+        return torch.from_numpy(out)
+    t = torch.as_tensor(constraints)
+    if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError("constraints are integer tags")
+    if t.dim() == 2:
+        t = t.unsqueeze(1)
+    if t.dim() != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("constraints (B,S,L') or (B,L') expected, got %s" % (tuple(t.shape),))
+    if t.shape[2] > L:
+        raise ValueError("constraints have %d tags, seq_length is %d" % (t.shape[2], L))
+    t = t.long()
+    if not t.is_cuda and t.numel() and (int(t.min()) < -1 or int(t.max()) >= 32):
+        raise ValueError("tags must lie in [-1, 32)")
+    m = torch.where(t < 0, torch.full_like(t, ANY_WORD), torch.ones_like(t) << (t & 31))
+    return F.pad(m, (0, L - t.shape[2]), value=1).contiguous()
+
+
+def beam_captions_following_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, word_cat, constraints=None,
+                                      beam_size=5, suppress_token=1, built=False):
+    """``beam_captions_with_templates`` with the hard guarantee: (seq (B,S,W,L) int64, seq_logp (B,S,W,L), score (B,S,W),
+    template_score (B,S)).  The forced POS rollout (``pos_model.sample_forced``) gives the soft guidance `pos_feats` as before; then
+    ``cap_model.beam_captions_allowed`` (include/xgate_beam_allow.h) admits at position t of a (video, template) pair's captions only
+    words whose category -- `word_cat` (V,) uint8 on the device, ``data.word_category_table`` -- the pair's constraint allows at t.
+    `constraints` as ``allow_masks`` takes them (`built` as there); None: the templates themselves, so every caption with a score
+    above -500 has exactly its template's tag sequence and length (given that word 0 alone has category 0).  Nothing is read back
+    between the two calls or after them.  Inference only: both models run under ``torch.no_grad()``."""
+    with torch.no_grad():
+        tag_logp, _, _, pos_feats = pos_model.sample_forced(feats_rgb, feats_opfl, feat_mask, templates, collect_states=False,
+                                                            trim=False)
+        B, S, L = tag_logp.shape
+        allow = allow_masks(templates if constraints is None else constraints, L, built=built and constraints is not None)
+        seq, seq_logp, score = cap_model.beam_captions_allowed(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(B, S, -1), word_cat,
+                                                               allow.to(pos_feats.device), beam_size=beam_size,
+                                                               suppress_token=suppress_token)
+    return seq, seq_logp, score, tag_logp.sum(2)
+
+
+def template_adherence(seq, allow, word_cat):
+    """(B,S,W) bool for captions seq (B,S,W,L), masks allow (B,S,L) and the table word_cat (V,): True where every token up to and
+    including the caption's first 0 (all L when it has none) is allowed at its position, by the rule of include/xgate_beam_allow.h
+    -- a mask that admits no word of the table counts as 0xFFFFFFFF.  Torch ops on `seq`'s device; nothing is read back."""
+    seq = torch.as_tensor(seq)
+    dev = seq.device
+    allow, cat = torch.as_tensor(allow).to(dev).long() & ANY_WORD, torch.as_tensor(word_cat).to(dev).long() & 31
+    if seq.dim() != 4 or allow.dim() != 3 or cat.dim() != 1 or allow.shape != seq.shape[:2] + seq.shape[3:]:
+        raise ValueError("seq (B,S,W,L), allow (B,S,L) and word_cat (V,) expected, got %s, %s, %s"
+                         % (tuple(seq.shape), tuple(allow.shape), tuple(cat.shape)))
+    present = ((torch.bincount(cat, minlength=32) > 0).long() << torch.arange(32, device=dev)).sum()
+    allow = torch.where((allow & present) == 0, torch.full_like(allow, ANY_WORD), allow)
+    ok = ((allow.unsqueeze(2) >> cat[seq.long()]) & 1).bool()
+    open_ = (seq != 0).long().cumprod(3).bool()
+    counted = torch.cat([torch.ones_like(open_[..., :1]), open_[..., :-1]], 3)
+    return (ok | ~counted).all(3)
 
 
 def score_captions_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, captions, cross=False):

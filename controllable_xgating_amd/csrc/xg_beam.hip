@@ -7,6 +7,8 @@
 //                          logits that round to one lp are ordered by word index like the host search's torch.topk over lp.
 //   cap_beam_topw_thr_kernel  the same outputs, the insertion replaced by a threshold from the threads' maxima and a short candidate
 //                          list (the search over S templates per video, include/xgate_beam_control.h, has S times the rows).
+//   cap_beam_topw_allow_kernel  the threshold form over a row's ALLOWED words (include/xgate_beam_allow.h): the log-sum-exp runs over
+//                          them alone and every other word is lowered by 1000 like the suppressed one.
 //   cap_beam_merge_kernel  one workgroup per video: fills the candidate tables from topv / topi, runs steps 3-5 of the rule
 //                          (beam_merge, xg_beam_core.h), and every thread gathers h1, c1, h2, c2 of slot v from its parent out of
 //                          the step's OUTPUT buffer into its INPUT buffer.
@@ -238,6 +240,203 @@ __global__ void __launch_bounds__(TW_TPB) cap_beam_topw_thr_kernel(const float* 
     }
 }
 
+// ---- the selection under a per-row set of ALLOWED words (include/xgate_beam_allow.h; only xgba_beam_search launches it)
+// Which of the row's words are allowed: word i iff bit (word_cat[i] & 31) of the row's mask.  Staged, a thread's elements are
+// i = tid + k TW_TPB in every pass over LDS, so the predicate is ONE bit per element in a 64-bit register, built by one coalesced
+// pass of byte loads over word_cat; unstaged, every pass reads the byte again beside the row (docs/CAPTION_ALLOW.md).
+static_assert(CB_STAGE_BYTES / 4 <= 64 * TW_TPB, "a staged row's elements per thread fit the 64-bit predicate");
+template <bool STAGE>
+struct TopwAllowed {
+    const uint8_t* cat; uint32_t mask; unsigned long long bits;
+    __device__ __forceinline__ bool operator()(int i) const {
+        if constexpr (STAGE) return (bits >> (i >> 10)) & 1ull;
+        else return (mask >> (cat[i] & 31)) & 1u;
+    }
+};
+static_assert(TW_TPB == 1 << 10, "TopwAllowed: element i of a staged row is bit i >> 10 of its thread");
+
+// topw_by_insertion with the value of an element left to the caller (val(x, i); the source of cap_beam_topw_kernel's selection
+// stays as it is: docs/CAPTION_BEAM_CONTROL.md on what re-factoring it did to its machine code)
+template <int W, bool STAGE, typename Val>
+__device__ __forceinline__ void topw_by_insertion_of(const TopwRow<STAGE>& r, Val&& val, float* cv, int* ci, float* __restrict__ topv,
+                                                     int32_t* __restrict__ topi) {
+    const int tid = r.tid, lane = tid & 63, wave = tid >> 6, V = r.V;
+    float bv[W];
+    int bi[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) { bv[k] = -INFINITY; bi[k] = CB_EMPTY; }
+    r.each([&](float x, int i) {
+        float v = val(x, i);
+        int ix = i;
+        if (beam_before(v, ix, bv[W - 1], bi[W - 1])) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                if (beam_before(v, ix, bv[k], bi[k])) {
+                    const float tv = bv[k]; const int ti = bi[k];
+                    bv[k] = v; bi[k] = ix; v = tv; ix = ti;
+                }
+            }
+        }
+    });
+#pragma unroll
+    for (int rd = 0; rd < W; ++rd) {
+        float v = bv[0];
+        int ix = bi[0];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(v, off);
+            const int oi = __shfl_xor(ix, off);
+            if (beam_before(ov, oi, v, ix)) { v = ov; ix = oi; }
+        }
+        if (lane == 0) { cv[wave * W + rd] = v; ci[wave * W + rd] = ix; }
+        if (bi[0] == ix) {
+#pragma unroll
+            for (int k = 0; k + 1 < W; ++k) { bv[k] = bv[k + 1]; bi[k] = bi[k + 1]; }
+            bv[W - 1] = -INFINITY; bi[W - 1] = CB_EMPTY;
+        }
+    }
+    __syncthreads();
+    if (tid < TW_WAVES * W) {
+        const float v = cv[tid];
+        const int ix = ci[tid];
+        int rank = 0;
+        for (int j = 0; j < TW_WAVES * W; ++j) {
+            const float ov = cv[j];
+            const int oi = ci[j];
+            rank += (beam_before(ov, oi, v, ix) || (ov == v && oi == ix && j < tid)) ? 1 : 0;
+        }
+        if (rank < W) {
+            topv[(size_t)blockIdx.x * W + rank] = v;
+            topi[(size_t)blockIdx.x * W + rank] = (ix >= 0 && ix < V) ? ix : 0;
+        }
+    }
+}
+
+// The contract and outputs of cap_beam_topw_thr_kernel with lp = logit - lse_a, lse_a the log-sum-exp over the row's ALLOWED words,
+// less 1000 at every word that is not allowed and less 1000 at `suppress`.  Row m belongs to group m / W and its mask is
+// allow[(m / W) * astride] (the step's column of the (G,L) table).  A mask that admits no word of the vocabulary counts as all ones.
+template <int W, bool STAGE>
+__global__ void __launch_bounds__(TW_TPB) cap_beam_topw_allow_kernel(const float* __restrict__ logits, int64_t ld, int V, int suppress,
+                                                                     const uint8_t* __restrict__ word_cat,
+                                                                     const uint32_t* __restrict__ allow, int64_t astride,
+                                                                     float* __restrict__ topv, int32_t* __restrict__ topi) {
+    extern __shared__ float4 cb_lds4[];
+    __shared__ float red[TW_WAVES], cv[TW_WAVES * W], lv[TW_CAND], tau_s;
+    __shared__ int ci[TW_WAVES * W], li[TW_CAND], cnt_s, any_w[TW_WAVES];
+    const TopwRow<STAGE> r(logits, ld, V, cb_lds4);
+    const int tid = r.tid, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) cnt_s = 0;                                      // (barriers below come before its first use)
+    TopwAllowed<STAGE> ok{word_cat, allow[(size_t)(blockIdx.x / W) * astride], 0ull};
+    // ---- the row's one trip from memory (staged) and the predicate; does the mask admit any word at all?
+    bool any = false;
+    if constexpr (STAGE) {
+        for (int i = tid, k = 0; i < V; i += TW_TPB, ++k)
+            ok.bits |= (unsigned long long)((ok.mask >> (word_cat[i] & 31)) & 1u) << k;
+        any = ok.bits != 0;
+        if (tid < r.head) r.row[tid] = r.g[tid];
+        for (int j = tid; j < r.nvec; j += TW_TPB) *reinterpret_cast<float4*>(r.row + r.head + 4 * j) = r.g4[j];
+        if (r.tail0 + tid < V) r.row[r.tail0 + tid] = r.g[r.tail0 + tid];
+    } else {
+        for (int i = tid; i < V; i += TW_TPB) any = any || ok(i);
+    }
+    const unsigned long long some = __ballot(any);
+    if (lane == 0) any_w[wave] = some != 0 ? 1 : 0;
+    __syncthreads();                                              // (the staged row is complete behind it too)
+    int found = 0;
+#pragma unroll
+    for (int k = 0; k < TW_WAVES; ++k) found |= any_w[k];
+    if (!found) { ok.mask = 0xFFFFFFFFu; ok.bits = ~0ull; }       // uniform over the workgroup: never an empty softmax
+    // ---- maximum and log-sum-exp over the allowed words: thread, wave (DPP), then the waves in one fixed order
+    float mx = -INFINITY;
+    r.each([&](float x, int i) { if (ok(i)) mx = fmaxf(mx, x); });
+    mx = wave_max(mx);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = red[0];
+#pragma unroll
+    for (int k = 1; k < TW_WAVES; ++k) mx = fmaxf(mx, red[k]);
+    __syncthreads();
+    float s = 0.f;
+    r.each([&](float x, int i) { if (ok(i)) s += __expf(x - mx); });
+    s = wave_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int k = 0; k < TW_WAVES; ++k) tot += red[k];
+    const float lse = mx + logf(tot);
+    auto val = [&](float x, int i) {
+        float v = x - lse;
+        if (!ok(i)) v -= 1000.0f;
+        if (i == suppress) v -= 1000.0f;
+        return v;
+    };
+    // ---- the threshold selection of cap_beam_topw_thr_kernel over val
+    float tm = -INFINITY;
+    r.each([&](float x, int i) { tm = fmaxf(tm, val(x, i)); });
+#pragma unroll
+    for (int rd = 0; rd < W; ++rd) {
+        const float m = wave_max(tm);
+        const unsigned long long holders = __ballot(tm == m);
+        if (lane == 0) cv[wave * W + rd] = m;
+        if (holders != 0 && lane == __ffsll(holders) - 1) tm = -INFINITY;
+    }
+    __syncthreads();
+    if (tid < TW_WAVES * W) {
+        const float v = cv[tid];
+        int rank = 0;
+        for (int j = 0; j < TW_WAVES * W; ++j) {
+            const float ov = cv[j];
+            rank += (ov > v || (ov == v && j < tid)) ? 1 : 0;
+        }
+        if (rank == W - 1) tau_s = v;
+    }
+    __syncthreads();
+    const float tau = tau_s;
+    r.each([&](float x, int i) {
+        const float v = val(x, i);
+        if (v >= tau) {
+            const int at = atomicAdd(&cnt_s, 1);
+            if (at < TW_CAND) { lv[at] = v; li[at] = i; }
+        }
+    });
+    __syncthreads();
+    const int n = cnt_s;
+    if (n < W || n > TW_CAND) {                                   // uniform over the workgroup
+        topw_by_insertion_of<W, STAGE>(r, val, cv, ci, topv, topi);
+        return;
+    }
+    if (tid < n) {
+        const float v = lv[tid];
+        const int ix = li[tid];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += beam_before(lv[j], li[j], v, ix) ? 1 : 0;
+        if (rank < W) {
+            topv[(size_t)blockIdx.x * W + rank] = v;
+            topi[(size_t)blockIdx.x * W + rank] = ix;             // (an index of `each`: inside [0, V))
+        }
+    }
+}
+
+template <int W>
+int launch_topw_allow(hipStream_t st, const float* logits, int64_t ld, int M, int V, int suppress, const uint8_t* word_cat,
+                      const uint32_t* allow, int64_t astride, float* topv, int32_t* topi) {
+    const size_t lds = ((size_t)V + 8) * sizeof(float);
+    if (lds <= (size_t)CB_STAGE_BYTES) {
+        if (lds > 64 * 1024) {
+            static std::atomic<unsigned> optin{0};
+            XG_TRY(xg_lds_optin(optin, reinterpret_cast<const void*>(cap_beam_topw_allow_kernel<W, true>), CB_STAGE_BYTES));
+        }
+        hipLaunchKernelGGL((cap_beam_topw_allow_kernel<W, true>), dim3(M), dim3(TW_TPB), lds, st, logits, ld, V, suppress, word_cat,
+                           allow, astride, topv, topi);
+    } else {
+        hipLaunchKernelGGL((cap_beam_topw_allow_kernel<W, false>), dim3(M), dim3(TW_TPB), 0, st, logits, ld, V, suppress, word_cat,
+                           allow, astride, topv, topi);
+    }
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+
 template <int W, bool THR>
 int launch_topw(hipStream_t st, const float* logits, int64_t ld, int M, int V, int suppress, float* topv, int32_t* topi) {
     using Kernel = void (*)(const float*, int64_t, int, int, float*, int32_t*);
@@ -356,6 +555,23 @@ int xgk_cap_beam_topw(hipStream_t st, const float* logits, int64_t ld, int M, in
 
 int xgk_cap_beam_topw_thr(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, float* topv, int32_t* topi) {
     return topw_any<true>(st, logits, ld, M, V, W, suppress, topv, topi);
+}
+
+int xgk_cap_beam_topw_allow(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, const uint8_t* word_cat,
+                            const uint32_t* allow, int64_t astride, float* topv, int32_t* topi) {
+    if (M <= 0 || V <= 0 || W < 1 || W > CB_MAX || W > V || ld < V || suppress >= V || !word_cat || !allow || astride < 1 || M % W)
+        return XG_EINVAL;
+    if (suppress < 0) suppress = -1;
+    switch (W) {
+        case 1: return launch_topw_allow<1>(st, logits, ld, M, V, suppress, word_cat, allow, astride, topv, topi);
+        case 2: return launch_topw_allow<2>(st, logits, ld, M, V, suppress, word_cat, allow, astride, topv, topi);
+        case 3: return launch_topw_allow<3>(st, logits, ld, M, V, suppress, word_cat, allow, astride, topv, topi);
+        case 4: return launch_topw_allow<4>(st, logits, ld, M, V, suppress, word_cat, allow, astride, topv, topi);
+        case 5: return launch_topw_allow<5>(st, logits, ld, M, V, suppress, word_cat, allow, astride, topv, topi);
+        case 6: return launch_topw_allow<6>(st, logits, ld, M, V, suppress, word_cat, allow, astride, topv, topi);
+        case 7: return launch_topw_allow<7>(st, logits, ld, M, V, suppress, word_cat, allow, astride, topv, topi);
+        default: return launch_topw_allow<8>(st, logits, ld, M, V, suppress, word_cat, allow, astride, topv, topi);
+    }
 }
 
 int xgk_cap_beam_merge(hipStream_t st, int B, CapBeamMergeArgs a) {

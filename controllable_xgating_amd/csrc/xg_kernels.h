@@ -381,6 +381,11 @@ int xgk_cap_beam_repeat(hipStream_t st, const CapBeamRepeatArgs& a, int B, int W
 int xgk_cap_beam_topw(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, float* topv, int32_t* topi);
 // the same contract and outputs, the selection behind a threshold from the threads' maxima (xgbc_beam_search's form)
 int xgk_cap_beam_topw_thr(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, float* topv, int32_t* topi);
+// the same outputs under a per-group set of allowed words (include/xgate_beam_allow.h): rows m of group m / W (M % W == 0), word v
+// allowed iff bit (word_cat[v] & 31) of allow[(m / W) * astride]; lp = logit - log-sum-exp over the allowed words, less 1000 at every
+// other word and at `suppress`; a mask that admits no word counts as all ones
+int xgk_cap_beam_topw_allow(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, const uint8_t* word_cat,
+                            const uint32_t* allow, int64_t astride, float* topv, int32_t* topi);
 struct CapBeamMergeArgs {
     const float* topv; const int32_t* topi;   // (M,W) of this step
     BeamBook<int64_t> book;

@@ -16,6 +16,7 @@
 #include "../../include/xgate_control.h"
 #include "../../include/xgate_score.h"
 #include "../../include/xgate_beam_control.h"
+#include "../../include/xgate_beam_allow.h"
 #include "../../include/xgate_pair.h"
 
 #include <new>
@@ -2090,11 +2091,15 @@ int search_args(bool dims, const XgParams* p, const XgBnState* bn, const XgBatch
 
 // Both beam searches (S as in beam_carve).  videos_once, which also takes the initial state to each video's rows; pos_feats goes to
 // each group's W slots; V and v2a(V) are row-repeated for S == 0 only.  With S >= 1 core_step is told the rows per video (the
-// stand-alone group attention over the per-video V / v2a(V)) and the selection is the threshold form.
+// stand-alone group attention over the per-video V / v2a(V)) and the selection is the threshold form; under a constraint `al`
+// (include/xgate_beam_allow.h) step t's selection is the allowed form over column t of the (G,L) masks.  Without one the launches,
+// their order and their arguments are what they were.
+struct BeamAllow { const uint8_t* word_cat; const uint32_t* allow; };
 int beam_search_impl(void* stream, const XgDims* d, int S, int W, int32_t suppress_token, const XgParams* p, const XgBnState* bn,
                      const XgBatch* x, const XgRun* run, int64_t* seq, float* seq_logp, float* score, int32_t* trace, void* ws,
-                     size_t ws_bytes) {
+                     size_t ws_bytes, const BeamAllow* al = nullptr) {
     XG_TRY(search_args(beam_dims_ok(d, S, W, suppress_token), p, bn, x, run, seq, seq_logp, score, ws));
+    if (al && (!al->word_cat || !al->allow)) return XG_EINVAL;
     BeamWs w = beam_carve(*d, S, W, ws);
     if (ws_bytes < w.bytes) return XG_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -2135,7 +2140,8 @@ int beam_search_impl(void* stream, const XgDims* d, int S, int W, int32_t suppre
         s.rows_per_video = shared ? S * W : 0;
         XG_TRY(core_step(st, dm, *p, *run, w.step, Venc, vproj, s));
         XG_TRY(xgk_linear(st, 0, M, V, R, s.h2o, R, p->logit_w, p->logit_b, w.step.LOGITS, V));
-        XG_TRY((shared ? xgk_cap_beam_topw_thr : xgk_cap_beam_topw)(st, w.step.LOGITS, V, M, V, W, suppress_token, w.topv, w.topi));
+        if (al) XG_TRY(xgk_cap_beam_topw_allow(st, w.step.LOGITS, V, M, V, W, suppress_token, al->word_cat, al->allow + t, L, w.topv, w.topi));
+        else XG_TRY((shared ? xgk_cap_beam_topw_thr : xgk_cap_beam_topw)(st, w.step.LOGITS, V, M, V, W, suppress_token, w.topv, w.topi));
         ma.book.t = t;
         XG_TRY(xgk_cap_beam_merge(st, G, ma));
     }
@@ -2168,6 +2174,20 @@ extern "C" int xgbc_beam_search(void* stream, const XgDims* d, int32_t S, int32_
                                 float* score, int32_t* trace, void* ws, size_t ws_bytes) {
     if (S < 1) return XG_EINVAL;
     return beam_search_impl(stream, d, S, W, suppress_token, p, bn, x, run, seq, seq_logp, score, trace, ws, ws_bytes);
+}
+
+// ---- that search with every step's words held to the group's allowed categories (include/xgate_beam_allow.h); the predicate needs
+// no table of its own, so the workspace is the unconstrained search's
+extern "C" int xgba_version(void) { return XGBA_VERSION; }
+
+extern "C" size_t xgba_workspace_bytes(const XgDims* d, int32_t S, int32_t W) { return xgbc_workspace_bytes(d, S, W); }
+
+extern "C" int xgba_beam_search(void* stream, const XgDims* d, int32_t S, int32_t W, int32_t suppress_token, const uint8_t* word_cat,
+                                const uint32_t* allow, const XgParams* p, const XgBnState* bn, const XgBatch* x, const XgRun* run,
+                                int64_t* seq, float* seq_logp, float* score, int32_t* trace, void* ws, size_t ws_bytes) {
+    if (S < 1) return XG_EINVAL;
+    const BeamAllow al{word_cat, allow};
+    return beam_search_impl(stream, d, S, W, suppress_token, p, bn, x, run, seq, seq_logp, score, trace, ws, ws_bytes, &al);
 }
 
 // ---- the captioner under S templates per video (include/xgate_control.h): rollout_impl over M = B S rows in its rows-per-video form

@@ -102,6 +102,28 @@ def word_categories(category_words, words):
     return out
 
 
+def word_category_table(category, wtoi, V):
+    """The (V,) uint8 table ``SAModel.beam_captions_allowed`` takes (include/xgate_beam_allow.h: word_cat): entry ``wtoi[word]`` is
+    ``category[word]`` for every word of ``wtoi`` that ``category`` (the dict ``word_categories`` returns) knows, every other
+    index in 2 .. V-1 is 1 (unknown), index 0 is 0 (<EOS>) and index 1 is 1 (unknown) whatever the dicts say.  Raises ValueError
+    for a category outside [0, 32) -- the masks are 32 bits wide -- and for a word index outside [0, V)."""
+    V = int(V)
+    if V < 2:
+        raise ValueError("a vocabulary holds at least <EOS> and the unknown word, V = %d" % V)
+    table = np.ones(V, dtype=np.uint8)
+    for wd, ix in wtoi.items():
+        if wd not in category:
+            continue
+        c, ix = int(category[wd]), int(ix)
+        if not 0 <= c < 32:
+            raise ValueError("category %d of word %r is outside [0, 32)" % (c, wd))
+        if not 0 <= ix < V:
+            raise ValueError("index %d of word %r is outside [0, %d)" % (ix, wd, V))
+        table[ix] = c
+    table[0], table[1] = 0, 1
+    return table
+
+
 def vocab_size(worddict):
     """data_io.get_nwords (:122-123): the pickled dictionary starts at index 2; 0 = <EOS> / BOS / pad, 1 = unknown."""
     return len(worddict) + 2

@@ -642,6 +642,50 @@ class SAModel(FlatParams, nn.Module):
         out = (seq, seq_logp, score)
         return out + (trace,) if return_trace else out
 
+    def beam_captions_allowed(self, feats_rgb, feats_opfl, feat_mask, pos_feats, word_cat, allow, beam_size=5, suppress_token=1,
+                              return_trace=False):
+        """``beam_captions_per_video`` in which position t of a (video, template) pair's captions admits only words of the POS
+        categories the pair allows there (include/xgate_beam_allow.h).  `word_cat` (V,) uint8: every word's category, below 32
+        (``data.word_category_table``); `allow` (B,S,L) integers holding uint32 masks, bit c set = category c admitted
+        (``control.allow_masks``; 0xFFFFFFFF: any word; a mask that admits no word of the vocabulary counts as that).  The softmax of
+        a step runs over the allowed words alone and every other word is lowered by 1000 like the suppressed one, so every
+        returned beam with a score above -500 holds allowed words only.  Returns what ``beam_captions_per_video`` returns; one
+        enqueue, nothing here synchronises with the host.
+
+        Raises as that method does, plus ValueError for a `word_cat` that is not (V,) uint8 or an `allow` that is not (B,S,L)
+        integers.  Eval mode, fp32 and device tensors only."""
+        from . import _native_beam_allow as nba
+        name = "beam_captions_allowed"
+        inputs, W, sup = (feats_rgb, feats_opfl, feat_mask, pos_feats), int(beam_size), int(suppress_token)
+        self._search_gate(name)
+        if not torch.is_tensor(word_cat) or word_cat.dtype != torch.uint8 or tuple(word_cat.shape) != (self.vocab_size,):
+            raise ValueError("word_cat (V = %d,) uint8 expected, got %s" % (
+                self.vocab_size, (tuple(word_cat.shape), word_cat.dtype) if torch.is_tensor(word_cat) else type(word_cat)))
+        if not torch.is_tensor(allow) or allow.is_floating_point() or allow.is_complex() or allow.dtype == torch.bool:
+            raise ValueError("allow holds integer masks")
+        # (the constraint's own checks hold on any device: they come before the device gate of _search_open, behind the mode's)
+        if pos_feats.dim() == 3 and tuple(allow.shape) != tuple(pos_feats.shape[:2]) + (self.seq_length,):
+            raise ValueError("allow (B = %d, S = %d, L = %d) expected, got %s" % (pos_feats.shape[0], pos_feats.shape[1],
+                                                                                  self.seq_length, tuple(allow.shape)))
+        B, K, S, L, dev, d = self._search_open(name, inputs, True, beam=(W, sup))
+        self._search_gate(name, word_cat, allow)
+        with torch.no_grad():                        # the uint32 bit patterns in int32 storage
+            a = allow.detach().long() & 0xFFFFFFFF
+            a = torch.where(a >= 1 << 31, a - (1 << 32), a).to(torch.int32).contiguous()
+            wc = word_cat.detach().contiguous()
+        lib = nba.lib()
+        args, wp, wn, keep = self._search_call("_beam_allow_ws", (B, K, L, S, W, str(dev)),
+                                               lambda: lib.xgba_workspace_bytes(C.byref(d), S, W),
+                                               "xgba_workspace_bytes: invalid dims or too many rows (B %d, S %d, W %d)" % (B, S, W), inputs)
+        seq = torch.empty(B, S, W, L, dtype=torch.int64, device=dev)
+        seq_logp = torch.empty(B, S, W, L, dtype=torch.float32, device=dev)
+        score = torch.empty(B, S, W, dtype=torch.float32, device=dev)
+        trace = torch.empty(B, S, L, W, 2, dtype=torch.int32, device=dev) if return_trace else None
+        nv.check(lib.xgba_beam_search(_stream(), C.byref(d), S, W, sup, nv.ptr(wc), nv.ptr(a), *args, nv.ptr(seq), nv.ptr(seq_logp),
+                                      nv.ptr(score), nv.ptr(trace), wp, wn), "xgba_beam_search")
+        out = (seq, seq_logp, score)
+        return out + (trace,) if return_trace else out
+
     def score_captions_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, captions, cross=False):
         """The log-probability the captioner gives GIVEN captions, on ONE encoder pass (include/xgate_score.h): the B videos are
         handed over once, `pos_feats` is (B,S,R) and `captions` (B,N,L') integer tokens with L' <= seq_length, zero = EOS (padded
