@@ -11,9 +11,10 @@ from ._native import XgError, lib, LIB_PATH  # noqa: F401,E402
 from .model import (SAModel, LanguageModelCriterion, ClassiferCriterion, RewardCriterion, make_opt)  # noqa: F401,E402
 from .control import (pad_templates, caption_with_templates, caption_sampled, caption_beam, first_occurrences,  # noqa: F401,E402
                       beam_captions_with_templates, score_captions_with_templates, template_recovery, allow_masks,
-                      beam_captions_following_templates, template_adherence)
+                      beam_captions_following_templates, template_adherence, diverse_beam_captions_with_templates,
+                      caption_beam_diverse)
 
 __all__ = ["SAModel", "LanguageModelCriterion", "ClassiferCriterion", "RewardCriterion", "make_opt", "XgError", "lib", "pad_templates",
            "caption_with_templates", "caption_sampled", "caption_beam", "first_occurrences", "beam_captions_with_templates",
            "score_captions_with_templates", "template_recovery", "allow_masks", "beam_captions_following_templates",
-           "template_adherence"]
+           "template_adherence", "diverse_beam_captions_with_templates", "caption_beam_diverse"]

@@ -114,6 +114,23 @@ def beam_captions_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, fe
     return seq, seq_logp, score, tag_logp.sum(2)
 
 
+def diverse_beam_captions_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, groups, group_size,
+                                         diversity=0.5, suppress_token=1):
+    """``beam_captions_with_templates`` with the diverse search: per (video, template) pair Gd = groups beam searches of width
+    Wg = group_size that are steered apart (``cap_model.beam_captions_diverse``, include/xgate_beam_diverse.h; `groups`,
+    `group_size`, `diversity`, `suppress_token` and the order of a group's beams as there): (seq (B,S,Gd,Wg,L) int64, seq_logp
+    (B,S,Gd,Wg,L), score (B,S,Gd,Wg), template_score (B,S)).  The forced POS rollout leaves `pos_feats` on the device and the
+    captioner takes the B videos once; nothing is read back between the two or after them.  Inference only: both models run under
+    ``torch.no_grad()``."""
+    with torch.no_grad():
+        tag_logp, _, _, pos_feats = pos_model.sample_forced(feats_rgb, feats_opfl, feat_mask, templates, collect_states=False,
+                                                            trim=False)
+        B, S = tag_logp.shape[:2]
+        seq, seq_logp, score = cap_model.beam_captions_diverse(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(B, S, -1),
+                                                               groups, group_size, diversity=diversity, suppress_token=suppress_token)
+    return seq, seq_logp, score, tag_logp.sum(2)
+
+
 ANY_WORD = 0xFFFFFFFF                       # the mask that admits every category
 
 
@@ -297,3 +314,25 @@ def caption_beam(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, beam_si
         seq, slp, _ = caption_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, opt,
                                              share_encoder=share_encoder)
     return seq, slp, templates, score
+
+
+def caption_beam_diverse(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, groups, group_size, diversity=0.5, suppress_tag=1,
+                         opt={}, share_encoder=False):
+    """``caption_beam`` over the DIVERSE POS search: caption each of the B videos under the N = groups * group_size templates of
+    ``pos_model.beam_templates_diverse`` (`groups`, `group_size`, `diversity`, `suppress_tag` as there; include/
+    xgate_pos_beam_diverse.h): (seq (B,N,n) int64, seqLogprobs (B,N,n), templates (B,N,L) int64, score (B,N), first (B,N) bool).
+    Template g * group_size + k is the k-th best of group g; `score` is its penalised sum at the finish; `first` marks each
+    video's distinct templates (``first_occurrences``).  The search runs without a host synchronisation and its templates go
+    through ``caption_with_templates`` (`opt`, `share_encoder` as in ``caption_beam``).  Inference only: both models run under
+    ``torch.no_grad()``."""
+    if share_encoder and opt.get("beam_size", 1) > 1:
+        raise NotImplementedError("share_encoder=True has no beam search: beam_size must be 1 (beam_captions_with_templates "
+                                  "is the beam search on one encoder pass)")
+    with torch.no_grad():
+        templates, _, score, _ = pos_model.beam_templates_diverse(feats_rgb, feats_opfl, feat_mask, groups, group_size,
+                                                                  diversity=diversity, suppress_tag=suppress_tag, trim=False)
+        templates, score = templates.flatten(1, 2), score.flatten(1, 2)
+        seq, slp, _ = caption_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, opt,
+                                             share_encoder=share_encoder)
+        first = first_occurrences(templates)
+    return seq, slp, templates, score, first

@@ -591,3 +591,55 @@ int xgk_cap_beam_backtrace(hipStream_t st, int B, const BeamBook<int64_t>& book,
     XG_CHECK_LAUNCH();
     return XG_OK;
 }
+
+// ---- the diverse search (include/xgate_beam_diverse.h): a pair's N = Gd Wg rows hold their N best words each (topv / topi (M,N), the
+// selection kernel at W = N; a row's Wg best PENALISED words lie inside its unpenalised top N, docs/CAPTION_DIVERSE.md).  One
+// workgroup per pair, the groups in series: each row of group j is re-ranked under the penalty of the earlier groups' live new
+// words, beam_group_merge commits the group into the book carved as (pairs Gd, Wg, L), then every thread gathers slot v's state
+// from its parent row of the pair.
+namespace {
+
+__global__ void __launch_bounds__(CB_TPB) cap_beam_merge_diverse_kernel(CapBeamMergeArgs a, int Gd, float lambda) {
+    __shared__ BeamGroupTables G;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int R = a.R, Wg = a.book.W, N = Gd * Wg;
+    const size_t pair = blockIdx.x, row0 = pair * N;
+    const int rows = a.book.t == 0 ? 1 : Wg;  // (every slot holds the video's initial state at t = 0: a group's first row stands for it)
+    beam_group_begin(G);
+    for (int j = 0; j < Gd; ++j) {
+        for (int q = wave; q < rows; q += CB_TPB / 64) {
+            const size_t at = (row0 + (size_t)j * Wg + q) * N;
+            beam_group_rerank(G, q, a.topv + at, a.topi + at, N, a.V - 1, Wg, lambda, lane);
+        }
+        beam_group_merge(G, a.book, pair, Gd, j, rows);
+    }
+    if (a.vec) {
+        const int R4 = R >> 2;
+        for (int i = tid; i < 4 * N * R4; i += CB_TPB) {
+            const int k = i / (N * R4), rem = i - k * (N * R4);
+            const int v = rem / R4, j = rem - v * R4;
+            reinterpret_cast<float4*>(a.dst[k] + (row0 + v) * R)[j] = reinterpret_cast<const float4*>(a.src[k] + (row0 + G.par[v]) * R)[j];
+        }
+    } else {
+        for (int i = tid; i < 4 * N * R; i += CB_TPB) {
+            const int k = i / (N * R), rem = i - k * (N * R);
+            const int v = rem / R, j = rem - v * R;
+            a.dst[k][(row0 + v) * R + j] = a.src[k][(row0 + G.par[v]) * R + j];
+        }
+    }
+}
+
+}  // namespace
+
+int xgk_cap_beam_merge_diverse(hipStream_t st, int pairs, CapBeamMergeArgs a, int Gd, float lambda) {
+    const BeamBook<int64_t>& k = a.book;
+    if (pairs <= 0 || Gd < 1 || Gd > CB_MAX || k.W < 1 || k.W > CB_MAX || Gd * k.W > CB_MAX || Gd * k.W > a.V || a.R <= 0 || k.L <= 0 ||
+        k.t < 0 || k.t >= k.L || !(lambda >= 0.0f) || lambda == INFINITY)
+        return XG_EINVAL;
+    uintptr_t bits = 0;
+    for (int i = 0; i < 4; ++i) bits |= reinterpret_cast<uintptr_t>(a.src[i]) | reinterpret_cast<uintptr_t>(a.dst[i]);
+    a.vec = (a.R % 4 == 0 && bits % 16 == 0) ? 1 : 0;
+    hipLaunchKernelGGL(cap_beam_merge_diverse_kernel, dim3(pairs), dim3(CB_TPB), 0, st, a, Gd, lambda);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}

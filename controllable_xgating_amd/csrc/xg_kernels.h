@@ -393,6 +393,9 @@ struct CapBeamMergeArgs {
     int R, V, vec;                // (vec: set by the launcher)
 };
 int xgk_cap_beam_merge(hipStream_t st, int B, CapBeamMergeArgs a);
+// the diverse form (include/xgate_beam_diverse.h): a.book carved as (pairs Gd, Wg, L), topv / topi (pairs Gd Wg, Gd Wg) from the
+// selection at W = Gd Wg; the groups of a pair merged in series under lambda times the earlier groups' live new words
+int xgk_cap_beam_merge_diverse(hipStream_t st, int pairs, CapBeamMergeArgs a, int Gd, float lambda);
 int xgk_cap_beam_backtrace(hipStream_t st, int B, const BeamBook<int64_t>& book, int64_t* seq, float* seq_logp, float* score);
 
 // ---- xg_score.hip: scoring given captions (include/xgate_score.h)

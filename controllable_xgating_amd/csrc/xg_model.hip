@@ -17,6 +17,7 @@
 #include "../../include/xgate_score.h"
 #include "../../include/xgate_beam_control.h"
 #include "../../include/xgate_beam_allow.h"
+#include "../../include/xgate_beam_diverse.h"
 #include "../../include/xgate_pair.h"
 
 #include <new>
@@ -2044,7 +2045,8 @@ Carver search_carve(const XgDims& d, size_t M, bool whole_scratch, void* base, S
 
 // S == 0: xgcb_beam_search, one group of W rows per video.  S >= 1: xgbc_beam_search (include/xgate_beam_control.h), G = B S groups of
 // W rows, a video's S W rows share its V and v2a(V) in the per-video part: no (M,K,R) or (M,K,A) block.
-BeamWs beam_carve(const XgDims& d, int S, int W, void* base) {
+// Gd > 1 (include/xgate_beam_diverse.h): the W rows of a group are Gd diversity groups of W / Gd, each a "video" of the book.
+BeamWs beam_carve(const XgDims& d, int S, int W, void* base, int Gd = 1) {
     BeamWs w{};
     const size_t G = (size_t)d.B * (S > 0 ? S : 1), M = G * W, K = d.K, R = d.R, A = d.A, L = d.T - 1;
     Carver c = search_carve(d, M, true, base, w);      // (S == 0 may take the fused attention; both forms carve alike)
@@ -2052,7 +2054,7 @@ BeamWs beam_carve(const XgDims& d, int S, int W, void* base) {
     w.pos = c.take<float>(M * R);
     for (int i = 0; i < 2; ++i) for (int k = 0; k < 4; ++k) w.st[i][k] = c.take<float>(M * R);
     w.topv = c.take<float>(M * W); w.topi = c.take<int32_t>(M * W);
-    w.book = beam_book_carve<int64_t>(c, G, W, L);
+    w.book = beam_book_carve<int64_t>(c, G * Gd, W / Gd, L);
     w.bytes = (c.off + 255) & ~(size_t)255;
     return w;
 }
@@ -2093,14 +2095,18 @@ int search_args(bool dims, const XgParams* p, const XgBnState* bn, const XgBatch
 // each group's W slots; V and v2a(V) are row-repeated for S == 0 only.  With S >= 1 core_step is told the rows per video (the
 // stand-alone group attention over the per-video V / v2a(V)) and the selection is the threshold form; under a constraint `al`
 // (include/xgate_beam_allow.h) step t's selection is the allowed form over column t of the (G,L) masks.  Without one the launches,
-// their order and their arguments are what they were.
+// their order and their arguments are what they were.  Under `dv` (include/xgate_beam_diverse.h) W = Gd Wg: the selection is the
+// threshold form at W = N, unchanged, the book is carved as (G Gd, Wg, L) and the merge is the diverse one; without it likewise.
 struct BeamAllow { const uint8_t* word_cat; const uint32_t* allow; };
+struct BeamDiverse { int Gd, Wg; float lambda; };
 int beam_search_impl(void* stream, const XgDims* d, int S, int W, int32_t suppress_token, const XgParams* p, const XgBnState* bn,
                      const XgBatch* x, const XgRun* run, int64_t* seq, float* seq_logp, float* score, int32_t* trace, void* ws,
-                     size_t ws_bytes, const BeamAllow* al = nullptr) {
+                     size_t ws_bytes, const BeamAllow* al = nullptr, const BeamDiverse* dv = nullptr) {
     XG_TRY(search_args(beam_dims_ok(d, S, W, suppress_token), p, bn, x, run, seq, seq_logp, score, ws));
     if (al && (!al->word_cat || !al->allow)) return XG_EINVAL;
-    BeamWs w = beam_carve(*d, S, W, ws);
+    // (W = Gd Wg is the entry point's; the merge launcher refuses a negative, infinite or NaN lambda, but only once work is enqueued)
+    if (dv && (al || !(dv->lambda >= 0.0f) || dv->lambda == INFINITY)) return XG_EINVAL;
+    BeamWs w = beam_carve(*d, S, W, ws, dv ? dv->Gd : 1);
     if (ws_bytes < w.bytes) return XG_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const bool shared = S > 0;
@@ -2143,9 +2149,10 @@ int beam_search_impl(void* stream, const XgDims* d, int S, int W, int32_t suppre
         if (al) XG_TRY(xgk_cap_beam_topw_allow(st, w.step.LOGITS, V, M, V, W, suppress_token, al->word_cat, al->allow + t, L, w.topv, w.topi));
         else XG_TRY((shared ? xgk_cap_beam_topw_thr : xgk_cap_beam_topw)(st, w.step.LOGITS, V, M, V, W, suppress_token, w.topv, w.topi));
         ma.book.t = t;
-        XG_TRY(xgk_cap_beam_merge(st, G, ma));
+        if (dv) XG_TRY(xgk_cap_beam_merge_diverse(st, G, ma, dv->Gd, dv->lambda));
+        else XG_TRY(xgk_cap_beam_merge(st, G, ma));
     }
-    return xgk_cap_beam_backtrace(st, G, w.book, seq, seq_logp, score);
+    return xgk_cap_beam_backtrace(st, dv ? G * dv->Gd : G, w.book, seq, seq_logp, score);
 }
 
 }  // namespace
@@ -2188,6 +2195,27 @@ extern "C" int xgba_beam_search(void* stream, const XgDims* d, int32_t S, int32_
     if (S < 1) return XG_EINVAL;
     const BeamAllow al{word_cat, allow};
     return beam_search_impl(stream, d, S, W, suppress_token, p, bn, x, run, seq, seq_logp, score, trace, ws, ws_bytes, &al);
+}
+
+// ---- diverse beam search (include/xgate_beam_diverse.h): the rows-per-video search at W = Gd Wg slots per pair, merged group by group
+namespace {
+int diverse_width(int Gd, int Wg) { return Gd >= 1 && Wg >= 1 && Gd <= XGDB_MAX_BEAM && Wg <= XGDB_MAX_BEAM ? Gd * Wg : 0; }
+}  // namespace
+
+extern "C" int xgdb_version(void) { return XGDB_VERSION; }
+
+extern "C" size_t xgdb_workspace_bytes(const XgDims* d, int32_t S, int32_t Gd, int32_t Wg) {
+    const int N = diverse_width(Gd, Wg);
+    return S >= 1 && beam_dims_ok(d, S, N, -1) ? beam_carve(*d, S, N, nullptr, Gd).bytes : 0;
+}
+
+extern "C" int xgdb_beam_search(void* stream, const XgDims* d, int32_t S, int32_t Gd, int32_t Wg, float lambda, int32_t suppress_token,
+                                const XgParams* p, const XgBnState* bn, const XgBatch* x, const XgRun* run, int64_t* seq,
+                                float* seq_logp, float* score, int32_t* trace, void* ws, size_t ws_bytes) {
+    if (S < 1) return XG_EINVAL;
+    const BeamDiverse dv{Gd, Wg, lambda};
+    return beam_search_impl(stream, d, S, diverse_width(Gd, Wg), suppress_token, p, bn, x, run, seq, seq_logp, score, trace, ws, ws_bytes,
+                            nullptr, &dv);
 }
 
 // ---- the captioner under S templates per video (include/xgate_control.h): rollout_impl over M = B S rows in its rows-per-video form

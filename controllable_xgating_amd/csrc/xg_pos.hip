@@ -1731,3 +1731,124 @@ extern "C" int xgpb_beam_templates(void* stream, const XgpDims* d, int32_t W, in
     XG_CHECK_LAUNCH();
     return XG_OK;
 }
+
+// ==================================================================================================================================
+// Diverse beam templates (include/xgate_pos_beam_diverse.h): Gd groups of Wg slots per video, N = Gd Wg rows, each group a beam search
+// of width Wg, the groups of a video merged in series within a step under the Hamming penalty of the earlier groups' live new tags
+// (the group form of xg_beam_core.h).  The launches are the plain search's at W = N; the step's fourth launch is
+// pos_beam_merge_diverse_kernel, ONE workgroup per video: the plain merge kernel's cell, head and log-sum-exp over the video's N rows,
+// then per group the re-rank of its rows' full C-way log-probabilities (they sit in LDS, so the penalty is applied to them directly)
+// and beam_group_merge, then every slot's h and c from its parent.  The book is carved as (B Gd, Wg, L): the backtrace is the plain one.
+// ==================================================================================================================================
+#include "../../include/xgate_pos_beam_diverse.h"
+
+namespace {
+
+static_assert(sizeof(BeamGroupTables) + 128 <= 1536, "the fixed part of XGPD_LDS_BYTES (1536) holds the group tables");
+
+__global__ void __launch_bounds__(STEP_TPB) pos_beam_merge_diverse_kernel(BeamArgs a, int Gd, float lambda) {
+    extern __shared__ float lds[];
+    __shared__ BeamGroupTables G;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int R = a.R, C = a.C, Wg = a.book.W, N = Gd * Wg, t = a.book.t;
+    const size_t b = blockIdx.x, row0 = b * N;
+    float* hs = lds;                          // N x R
+    float* cs = hs + (size_t)N * R;           // N x R
+    float* lg = cs + (size_t)N * R;           // N x C: the logits, then the log-probabilities
+    beam_group_begin(G);
+    for (int i = tid; i < N * R; i += STEP_TPB) {
+        const int q = i / R, j = i - q * R;
+        const size_t row = row0 + q;
+        const int64_t tk = t == 0 ? 0 : pos_clamp_tag(a.book.tok[row], C);
+        const PosCell o = pos_cell(a.S + row * 4 * R, a.tab + (size_t)tk * 4 * R, R, j, a.c[row * R + j], a.X[row * 2 * R + R + j], 1.0f);
+        hs[i] = o.hn;
+        cs[i] = o.cn;
+    }
+    const int rows = t == 0 ? 1 : N;          // (every slot holds the video's initial state at t = 0: row 0 stands for each group's)
+    for (int q = 0; q < rows; ++q) pos_head_logits(a.logit_w, a.logit_b, hs + (size_t)q * R, lg + (size_t)q * C, R, C);
+    if (wave < rows) {                        // wave q: the log-probabilities of row q, in place
+        float* lr = lg + (size_t)wave * C;
+        float mx;
+        if (C <= 64) {
+            const float v = lane < C ? lr[lane] : -INFINITY;
+            const float lse = pos_lse_lanes(v, lane < C, mx);
+            float lp = v - lse;
+            if (lane == a.suppress) lp -= 1000.0f;
+            if (lane < C) lr[lane] = lp;
+        } else if (lane == 0) {
+            const float lse = pos_lse_serial(lr, C, mx);
+            for (int cc = 0; cc < C; ++cc) lr[cc] -= lse;
+            if (a.suppress >= 0) lr[a.suppress] -= 1000.0f;
+        }
+    }
+    __syncthreads();
+    const int grows = t == 0 ? 1 : Wg;
+    for (int j = 0; j < Gd; ++j) {            // the groups in series: group j sees the live new tags of groups 0 .. j-1
+        if (wave < grows) beam_group_rerank(G, wave, lg + (size_t)(t == 0 ? 0 : j * Wg + wave) * C, nullptr, C, C - 1, Wg, lambda, lane);
+        beam_group_merge(G, a.book, b, Gd, j, grows);
+    }
+    for (int i = tid; i < N * R; i += STEP_TPB) {
+        const int v = i / R, j = i - v * R;
+        const int q = G.par[v];
+        a.X[(row0 + v) * 2 * R + R + j] = hs[(size_t)q * R + j];
+        a.c[(row0 + v) * R + j] = cs[(size_t)q * R + j];
+    }
+}
+
+// the workspace: the forced call's at S = N, then the book of the B Gd groups
+BWs dws_layout(const XgpDims* d, int Gd, int Wg, void* base) {
+    BWs w;
+    w.c = cws_layout(d, Gd * Wg, base);
+    Carve cv{(float*)base, w.c.floats};
+    w.book = beam_book_carve<int32_t>(cv, (size_t)d->B * Gd, Wg, d->T - 1);
+    w.floats = cv.off;
+    return w;
+}
+
+bool diverse_dims_ok(const XgpDims* d, int Gd, int Wg, int suppress) {
+    if (Gd < 1 || Wg < 1 || Gd > BEAM_MAX || Wg > BEAM_MAX || Gd * Wg > BEAM_MAX) return false;
+    const int N = Gd * Wg;
+    if (!ctrl_dims_ok(d, N) || N > d->C || suppress >= d->C) return false;
+    return XGPD_LDS_BYTES(N, d->R, d->C) <= XGPD_MAX_LDS_BYTES;
+}
+
+}  // namespace
+
+extern "C" int xgpd_version(void) { return XGPD_VERSION; }
+
+extern "C" size_t xgpd_workspace_bytes(const XgpDims* d, int32_t Gd, int32_t Wg) {
+    if (!diverse_dims_ok(d, Gd, Wg, -1)) return 0;
+    return dws_layout(d, Gd, Wg, nullptr).floats * sizeof(float);
+}
+
+extern "C" int xgpd_beam_templates(void* stream, const XgpDims* d, int32_t Gd, int32_t Wg, float lambda, int32_t suppress_tag,
+                                   const XgpParams* p, const XgBnState* bn, const float* feats_rgb, const float* feats_opfl,
+                                   const float* feat_mask, int64_t* templates, float* tag_logp, float* score, float* masks,
+                                   int32_t* n_out, int32_t* trace, void* ws, size_t ws_bytes) {
+    if (!diverse_dims_ok(d, Gd, Wg, suppress_tag) || !(lambda >= 0.0f) || lambda == INFINITY || !templates || !tag_logp || !score ||
+        !masks || !n_out)
+        return XG_EINVAL;
+    XG_TRY(args_gate(p, bn_ok(bn), feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, dws_layout(d, Gd, Wg, nullptr).floats));
+    hipStream_t st = (hipStream_t)stream;
+    const BWs w = dws_layout(d, Gd, Wg, ws);
+    const int B = d->B, R = d->R, C = d->C, L = d->T - 1, N = Gd * Wg, M = B * N;
+    XG_TRY(rows_prologue(st, d, N, p, bn, feats_rgb, feats_opfl, feat_mask, w.c));
+    BeamArgs a{};
+    a.S = w.c.S; a.tab = w.c.v.tab; a.logit_w = p->logit_w; a.logit_b = p->logit_b; a.X = w.c.X; a.c = w.c.c;
+    a.book = w.book; a.book.trace_out = trace;
+    a.R = R; a.C = C; a.suppress = suppress_tag < 0 ? -1 : suppress_tag;
+    const size_t lds_merge = XGPD_LDS_BYTES(N, R, C) - 1536;
+    const StepPlan pl = step_plan(d, N);         // (a video's N slots are one attention group)
+    for (int t = 0; t < L; ++t) {
+        XG_TRY(step_front(st, d, p, pl, w.c.v, w.c.X, w.c.P, w.c.S));
+        a.book.t = t;
+        hipLaunchKernelGGL(pos_beam_merge_diverse_kernel, dim3(B), dim3(STEP_TPB), lds_merge, st, a, Gd, lambda);
+        XG_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(pos_beam_backtrace_kernel, dim3(xg_cdiv(M, POS_TPB)), dim3(POS_TPB), 0, st, w.book, templates, tag_logp,
+                       score, masks, M);
+    XG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(pos_first_zero_col_kernel, dim3(1), dim3(POS_TPB), 0, st, nullptr, masks, M, L + 1, 1, n_out);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}

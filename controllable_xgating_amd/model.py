@@ -686,6 +686,45 @@ class SAModel(FlatParams, nn.Module):
         out = (seq, seq_logp, score)
         return out + (trace,) if return_trace else out
 
+    def beam_captions_diverse(self, feats_rgb, feats_opfl, feat_mask, pos_feats, groups, group_size, diversity=0.5, suppress_token=1,
+                              return_trace=False):
+        """Diverse beam search (include/xgate_beam_diverse.h) for S `pos_feats` rows per video on ONE encoder pass: per (video,
+        template) pair Gd = groups beam searches of width Wg = group_size, a group steered away from the words the groups before
+        it took at the same step by `diversity` (lambda >= 0) per live slot that took them.  `pos_feats` is (B,S,R).  Returns (seq
+        (B,S,Gd,Wg,L) int64, seq_logp (B,S,Gd,Wg,L), score (B,S,Gd,Wg)[, trace (B,S,L,N,2) int32]), N = Gd Wg <= min(vocab_size, 8).
+
+        A group's beams come best first, ranked by the PENALISED sum `score` at the moment they finished; seq_logp holds the
+        unpenalised log-probabilities, so ``seq_logp.sum(-1)`` is the pure sum.  groups = 1 is ``beam_captions_per_video`` at
+        beam_size = group_size bit for bit; the trace's parents are slot indices of the pair.  `suppress_token` and
+        `return_trace` as in ``beam_captions``.  Eval mode, fp32 and device tensors only; one enqueue, nothing here synchronises
+        with the host."""
+        from . import _native_beam_diverse as ndb
+        name = "beam_captions_diverse"
+        inputs, sup = (feats_rgb, feats_opfl, feat_mask, pos_feats), int(suppress_token)
+        self._search_gate(name)
+        Gd, Wg, lam = int(groups), int(group_size), float(diversity)
+        most = min(self.vocab_size, ndb.XGDB_MAX_BEAM)
+        # (the search's own checks hold on any device: they come before the device gate of _search_open, behind the mode's)
+        if Gd < 1 or Wg < 1 or Gd * Wg > most:
+            raise ValueError("groups, group_size >= 1 and groups * group_size <= min(vocab_size = %d, %d) expected, got %d, %d"
+                             % (self.vocab_size, ndb.XGDB_MAX_BEAM, Gd, Wg))
+        if not (0.0 <= lam < float("inf")):
+            raise ValueError("diversity must be finite and >= 0, got %r" % (diversity,))
+        N = Gd * Wg
+        B, K, S, L, dev, d = self._search_open(name, inputs, True, beam=(N, sup))
+        lib = ndb.lib()
+        args, wp, wn, keep = self._search_call("_beam_diverse_ws", (B, K, L, S, Gd, Wg, str(dev)),
+                                               lambda: lib.xgdb_workspace_bytes(C.byref(d), S, Gd, Wg),
+                                               "xgdb_workspace_bytes: invalid dims or too many rows (B %d, S %d, N %d)" % (B, S, N), inputs)
+        seq = torch.empty(B, S, Gd, Wg, L, dtype=torch.int64, device=dev)
+        seq_logp = torch.empty(B, S, Gd, Wg, L, dtype=torch.float32, device=dev)
+        score = torch.empty(B, S, Gd, Wg, dtype=torch.float32, device=dev)
+        trace = torch.empty(B, S, L, N, 2, dtype=torch.int32, device=dev) if return_trace else None
+        nv.check(lib.xgdb_beam_search(_stream(), C.byref(d), S, Gd, Wg, lam, sup, *args, nv.ptr(seq), nv.ptr(seq_logp), nv.ptr(score),
+                                      nv.ptr(trace), wp, wn), "xgdb_beam_search")
+        out = (seq, seq_logp, score)
+        return out + (trace,) if return_trace else out
+
     def score_captions_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, captions, cross=False):
         """The log-probability the captioner gives GIVEN captions, on ONE encoder pass (include/xgate_score.h): the B videos are
         handed over once, `pos_feats` is (B,S,R) and `captions` (B,N,L') integer tokens with L' <= seq_length, zero = EOS (padded

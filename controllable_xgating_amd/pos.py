@@ -379,6 +379,53 @@ class PosModel(FlatParams, nn.Module):
         out = (templates, tag_logp, score, masks)
         return out + (trace,) if return_trace else out
 
+    def beam_templates_diverse(self, feats_rgb, feats_opfl, feat_mask, groups, group_size, diversity=0.5, suppress_tag=1, trim=True,
+                               return_trace=False):
+        """Diverse beam search (include/xgate_pos_beam_diverse.h): Gd = groups beam searches of width Wg = group_size per video, a
+        group steered away from the tags the groups before it took at the same step by `diversity` (lambda >= 0) per live slot that
+        took them.  Returns (templates (B,Gd,Wg,n) int64, tag_logp (B,Gd,Wg,n), score (B,Gd,Wg), masks (B,Gd,Wg,n+1)[, trace
+        (B,L,N,2) int32]), N = Gd Wg <= min(category_size, 8).
+
+        A group's beams come best first, ranked by the PENALISED sum `score` at the moment they finished; tag_logp holds the
+        unpenalised log-probabilities.  `templates.flatten(1, 2)` is a valid input of `sample_forced`.  groups = 1 is
+        `beam_templates(beam_size=group_size)` bit for bit.  suppress_tag, trim and return_trace as in `beam_templates`; the
+        trace's parents are slot indices of the video."""
+        from . import _native_pos_beam_diverse as npd
+        if self.training:
+            self._check_eval()                          # (raises: eval mode only)
+        Gd, Wg, sup, lam = int(groups), int(group_size), int(suppress_tag), float(diversity)
+        most = min(self.category_size, npd.XGPD_MAX_BEAM)
+        # (the search's own checks hold on any device: behind the mode's gate, ahead of the device's, as in the captioner's search)
+        if Gd < 1 or Wg < 1 or Gd * Wg > most:
+            raise ValueError("groups, group_size >= 1 and groups * group_size <= min(category_size = %d, %d) expected, got %d, %d"
+                             % (self.category_size, npd.XGPD_MAX_BEAM, Gd, Wg))
+        if not (0.0 <= lam < float("inf")):
+            raise ValueError("diversity must be finite and >= 0, got %r" % (diversity,))
+        if sup >= self.category_size:
+            raise ValueError("suppress_tag must lie below category_size = %d (-1: none), got %d" % (self.category_size, sup))
+        fr, fo, fm, B, K = self._rows_feats(feats_rgb, feats_opfl, feat_mask)
+        L = self.seq_length
+        dev = fr.device
+        lib = npd.lib()
+        N = Gd * Wg
+        dims, P, bn, ws, n_out = self._rows_setup(lambda d, n: lib.xgpd_workspace_bytes(d, Gd, Wg), B, K, N, dev,
+                                                  "xgpd_workspace_bytes: invalid dims, too many rows (B %d, N %d) or N * rnn_size beyond "
+                                                  "the merge kernel's LDS" % (B, N))
+        templates = torch.empty(B, Gd, Wg, L, dtype=torch.int64, device=dev)
+        tag_logp = torch.empty(B, Gd, Wg, L, device=dev)
+        score = torch.empty(B, Gd, Wg, device=dev)
+        masks = torch.empty(B, Gd, Wg, L + 1, device=dev)
+        trace = torch.empty(B, L, N, 2, dtype=torch.int32, device=dev) if return_trace else None
+        nv.check(lib.xgpd_beam_templates(_stream(), C.byref(dims), Gd, Wg, lam, sup, C.byref(P), C.byref(bn), fr.data_ptr(),
+                                         fo.data_ptr(), fm.data_ptr(), templates.data_ptr(), tag_logp.data_ptr(), score.data_ptr(),
+                                         masks.data_ptr(), n_out.data_ptr(), None if trace is None else trace.data_ptr(), ws.data_ptr(),
+                                         ws.numel()), "xgpd_beam_templates")
+        if trim:
+            n = int(n_out.item())                       # the one host synchronisation of the call
+            templates, tag_logp, masks = templates[..., :n], tag_logp[..., :n], masks[..., :n + 1]
+        out = (templates, tag_logp, score, masks)
+        return out + (trace,) if return_trace else out
+
 class _PosTrainFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, fr, fo, fm, cap, nm, *params):
