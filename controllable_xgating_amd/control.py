@@ -10,7 +10,8 @@ captions under them.  Eval mode, fp32, one GPU.  By default the captioner runs o
 template; ``share_encoder=True`` hands the videos over once (``SAModel.sample_per_video``, include/xgate_control.h): the captioner's
 encoder, init_hidden and v2a(V) then run once per video and a step's attention reads them once per group of a video's templates.
 ``beam_captions_with_templates`` is the captioner's BEAM SEARCH under the templates on one encoder pass
-(``SAModel.beam_captions_per_video``, include/xgate_beam_control.h).  All of that steers; ``beam_captions_following_templates``
+(``SAModel.beam_captions_per_video``, include/xgate_beam_control.h); ``caption_truncated_with_templates`` is the SAMPLED rollout
+under them with top-k / nucleus truncation (``SAModel.sample_truncated_per_video``, include/xgate_truncate.h).  All of that steers; ``beam_captions_following_templates``
 GUARANTEES: the same search admitting at position t only words whose POS category the template allows there
 (``SAModel.beam_captions_allowed``, include/xgate_beam_allow.h; ``allow_masks`` builds the sets, ``template_adherence`` checks a result).
 """
@@ -95,6 +96,24 @@ def caption_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mas
         B, S = tag_logp.shape[:2]
         seq, slp = _caption_rows(cap_model, feats_rgb, feats_opfl, feat_mask, pos_feats, B, S, opt, share_encoder)
     return seq, slp, tag_logp.sum(2)
+
+
+def caption_truncated_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, top_k=0, top_p=1.0,
+                                     temperature=1.0, uniforms=None, return_stats=False):
+    """``caption_with_templates`` with TOP-K / NUCLEUS sampling on one captioner encoder pass: (seq (B,S,n) int64, seqLogprobs
+    (B,S,n), template_score (B,S)), and with ``return_stats=True`` seq_logq (B,S,n) and kept (B,S,n) int32 after them.  The forced
+    POS rollout (``pos_model.sample_forced``) leaves `pos_feats` (B*S,R) on the device and
+    ``cap_model.sample_truncated_per_video`` (include/xgate_truncate.h; `top_k`, `top_p`, `temperature`, `uniforms` (L + 1, B*S)
+    and the statistics as there) takes the B videos once; nothing is read back between the two.  Inference only: both models run
+    under ``torch.no_grad()``."""
+    with torch.no_grad():
+        tag_logp, _, _, pos_feats = pos_model.sample_forced(feats_rgb, feats_opfl, feat_mask, templates, collect_states=False,
+                                                            trim=False)
+        B, S = tag_logp.shape[:2]
+        out = cap_model.sample_truncated_per_video(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(B, S, -1), top_k=top_k,
+                                                   top_p=top_p, temperature=temperature, uniforms=uniforms,
+                                                   return_stats=return_stats)
+    return out[:2] + (tag_logp.sum(2),) + out[2:]
 
 
 def beam_captions_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, beam_size=5, suppress_token=1):

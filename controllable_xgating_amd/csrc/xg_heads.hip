@@ -527,6 +527,228 @@ __global__ void __launch_bounds__(RT) rollout_step_kernel(RollStepArgs a) {
     const int64_t tk = s_tok;
     for (int e = tid; e < a.E; e += RT) a.xt[(size_t)b * a.E + e] = a.table[(size_t)tk * a.E + e];
 }
+
+// ------------------------------------------------------------------------------------------------
+// The choice of a step t >= 1 as a TRUNCATED draw (docs/CAPTION_TRUNCATED.md): top-k, then the nucleus inside it, ties at either
+// threshold kept, then the inverse-CDF draw of rollout_step_kernel over the kept columns only.  One workgroup per row; STAGE as above.
+// The kept set is {v : x_v >= thr} for ONE float threshold, so everything after the search is the plain draw under a predicate.
+//
+// The threshold search runs over the order-preserving integer key of a float.  A pass probes TR_NC = 3 candidates that quarter the
+// open key range, so a search takes at most 16 passes (plain bisection, one candidate per pass, took 32: docs/CAPTION_TRUNCATED.md).  A pass compares the row's FLOATS
+// with the candidates turned back into floats, so -0.0 and +0.0 are one class without any canonical form.  It reduces the count
+// or the mass of {x >= candidate} in a fixed order -- per-thread float over the thread's strided columns, DPP sums in double inside
+// a row of 16 lanes (every lane ends with the same bits), the four rows and then the 16 waves added in order -- so the mass is
+// monotone in the candidate (a superset summed in the same order never rounds lower) and a call gives the same bits twice.  No
+// float atomics.
+constexpr int TR_NC = 3;
+__device__ __forceinline__ unsigned tr_key(float f) {
+    const unsigned u = __float_as_uint(f);
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float tr_val(unsigned k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
+__device__ __forceinline__ int tr_wave_sum(int v) {
+    v += rs_dpp_i<0xB1>(v); v += rs_dpp_i<0x4E>(v); v += rs_dpp_i<0x141>(v); v += rs_dpp_i<0x140>(v);
+    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
+}
+__device__ __forceinline__ double tr_readlane(double v, int l) {
+    const unsigned long long u = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
+    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double tr_wave_sum(double v) {
+    v = rs_row_sum(v);
+    return ((tr_readlane(v, 0) + tr_readlane(v, 16)) + tr_readlane(v, 32)) + tr_readlane(v, 48);
+}
+
+template <bool STAGE>
+__global__ void __launch_bounds__(RT) rollout_trunc_kernel(RollStepArgs a, RollTruncArgs q) {
+    XG_CHAIN_PRIO();
+    extern __shared__ float xs[];
+    __shared__ float red[RT / 64];
+    __shared__ int redi[RT / 64];
+    __shared__ double s_mass[2][TR_NC][RT / 64];
+    __shared__ int s_cnt[2][TR_NC][RT / 64];
+    __shared__ double wave_tot[RT / 64];
+    __shared__ int wave_cnt[RT / 64];
+    __shared__ int64_t s_tok;
+    __shared__ int s_owner;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = a.V;
+    const float* x = a.logits + (size_t)b * V;
+    // pass 1: the row into LDS, row max and argmax (ties -> lowest index), as rollout_step_kernel
+    float best = -INFINITY; int bi = 0x7fffffff;
+    constexpr int NLD = 24;
+    for (int v0 = tid; v0 < V; v0 += NLD * RT) {
+        float fl[NLD];
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) { const int v = v0 + j * RT; fl[j] = v < V ? x[v] : -INFINITY; }
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int v = v0 + j * RT;
+            if (v < V) {
+                const float f = fl[j];
+                if (STAGE) xs[v] = f;
+                if (f > best || (f == best && v < bi)) { best = f; bi = v; }
+            }
+        }
+    }
+    const float* xr = STAGE ? xs : x;                // valid after the barrier of the reduction below
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0) { red[wave] = best; redi[wave] = bi; }
+    __syncthreads();
+    best = red[0]; bi = redi[0];
+    for (int i = 1; i < RT / 64; ++i)
+        if (red[i] > best || (red[i] == best && redi[i] < bi)) { best = red[i]; bi = redi[i]; }
+    const float mx = best;
+    const float invt = 1.0f / a.temperature;
+    // log-sum-exp of the untempered, untruncated row: seq_logp is what every other rollout reports
+    float se = 0.f;
+    for (int v = tid; v < V; v += RT) se += __expf(xr[v] - mx);
+    se = block_sum(se, red);
+    const float lse = mx + logf(se);
+
+    // counts (by_mass false) or masses of {x >= thr[i]}.  The two slots alternate: a thread can be one pass ahead of another, never two.
+    // A search only narrows its key range (lo, hi], so a column at or above the value of hi + 1 is IN for every later candidate and
+    // one below the value of lo + 1 is OUT: a thread drops both from `act`, the bit set of its first 64 strided columns that are
+    // still open, and carries the IN ones as c_in / m_in.  After a few passes a thread visits a handful of its columns, not all.
+    int pass = 0;
+    const int ncol = tid < V ? (V - tid + RT - 1) / RT : 0;          // this thread's strided columns
+    const unsigned long long act_all = ncol >= 64 ? ~0ull : (1ull << ncol) - 1ull;
+    unsigned long long act = act_all; int c_in = 0; float m_in = 0.f;
+    auto probe = [&](const float (&thr)[TR_NC], bool by_mass, float in_thr, float out_thr, int (&cnt)[TR_NC], double (&mass)[TR_NC]) {
+        int c[TR_NC] = {0, 0, 0}; float m[TR_NC] = {0.f, 0.f, 0.f};
+        for (unsigned long long todo = act; todo; todo &= todo - 1ull) {
+            const int j = __ffsll((long long)todo) - 1;
+            const float f = xr[tid + j * RT];
+            if (f >= in_thr) {
+                act &= ~(1ull << j);
+                if (by_mass) m_in += __expf((f - mx) * invt); else ++c_in;
+            } else if (!(f >= out_thr)) {
+                act &= ~(1ull << j);
+            } else if (by_mass) {
+                if (f >= thr[0]) {                   // (thr[0] <= thr[1] <= thr[2])
+                    const float w = __expf((f - mx) * invt);
+#pragma unroll
+                    for (int i = 0; i < TR_NC; ++i) m[i] += f >= thr[i] ? w : 0.f;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < TR_NC; ++i) c[i] += f >= thr[i] ? 1 : 0;
+            }
+        }
+        for (int v = tid + 64 * RT; v < V; v += RT) {               // (V > 65536: the columns behind the bit set, every pass)
+            const float f = xr[v];
+            const float w = (by_mass && f >= thr[0]) ? __expf((f - mx) * invt) : 0.f;
+#pragma unroll
+            for (int i = 0; i < TR_NC; ++i) { c[i] += f >= thr[i] ? 1 : 0; m[i] += f >= thr[i] ? w : 0.f; }
+        }
+#pragma unroll
+        for (int i = 0; i < TR_NC; ++i) { c[i] += c_in; m[i] = m_in + m[i]; }
+        const int pb = pass & 1; ++pass;
+#pragma unroll
+        for (int i = 0; i < TR_NC; ++i) {
+            if (by_mass) { const double md = tr_wave_sum((double)m[i]); if (lane == 0) s_mass[pb][i][wave] = md; }
+            else { const int ci = tr_wave_sum(c[i]); if (lane == 0) s_cnt[pb][i][wave] = ci; }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < TR_NC; ++i) {
+            cnt[i] = 0; mass[i] = 0.0;
+            if (by_mass) for (int k = 0; k < RT / 64; ++k) mass[i] += s_mass[pb][i][k];
+            else for (int k = 0; k < RT / 64; ++k) cnt[i] += s_cnt[pb][i][k];
+        }
+    };
+    // the largest key in [lo, hi] whose set {x >= value of the key} holds at least top_k columns / at least `need` of mass; lo does.
+    auto search = [&](unsigned lo, unsigned hi, bool by_mass, double need) {
+        while (lo < hi) {
+            const unsigned step = max(1u, (hi - lo + 1) >> 2);
+            unsigned key[TR_NC]; float thr[TR_NC]; int cnt[TR_NC]; double mass[TR_NC]; bool ok[TR_NC];
+#pragma unroll
+            for (int i = 0; i < TR_NC; ++i) { key[i] = min(hi, lo + (unsigned)(i + 1) * step); thr[i] = tr_val(key[i]); }
+            probe(thr, by_mass, tr_val(hi + 1), tr_val(lo + 1), cnt, mass);
+#pragma unroll
+            for (int i = 0; i < TR_NC; ++i) ok[i] = by_mass ? mass[i] >= need : cnt[i] >= q.top_k;
+            if (ok[2]) lo = key[2];
+            else if (ok[1]) { lo = key[1]; hi = key[2] - 1; }
+            else if (ok[0]) { lo = key[0]; hi = key[1] - 1; }
+            else hi = key[0] - 1;
+        }
+        return lo;
+    };
+    // the threshold.  top_k = 1: the class of the maximum, whatever top_p (the nucleus lies inside it and holds the argmax): no search.
+    float thr = -INFINITY;
+    if (q.top_k == 1) {
+        thr = mx;
+    } else {
+        const unsigned khi = tr_key(mx);
+        unsigned kth = tr_key(-INFINITY);            // keeps everything
+        if (q.top_k > 1 && q.top_k < V) kth = search(kth, khi, false, 0.0);      // the k-th largest value
+        if (q.top_p < 1.0f) {                        // the nucleus inside that set: its threshold is never below the top-k one
+            const float t0 = tr_val(kth);
+            const float th[TR_NC] = {t0, t0, t0};
+            int cnt[TR_NC]; double mass[TR_NC];
+            act = act_all; c_in = 0; m_in = 0.f;
+            probe(th, true, tr_val(khi + 1), t0, cnt, mass);          // Z_k; the columns below the top-k threshold are OUT for good
+            kth = search(kth, khi, true, (double)q.top_p * mass[0]);
+        }
+        thr = tr_val(kth);
+    }
+
+    // the draw of rollout_step_kernel over the kept columns: chunk sums, block scan in double, the owner's walk; |K| rides along
+    const int per = (V + RT - 1) / RT;
+    const int v0 = tid * per, v1 = min(V, v0 + per);
+    float cs = 0.f; int kc = 0;
+    for (int v = v0; v < v1; ++v) {
+        const float f = xr[v];
+        if (f >= thr) { cs += __expf((f - mx) * invt); ++kc; }
+    }
+    double inc = (double)cs;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double up = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += up;
+    }
+    for (int o = 32; o > 0; o >>= 1) kc += __shfl_xor(kc, o, 64);
+    if (lane == 63) wave_tot[wave] = inc;
+    if (lane == 0) wave_cnt[wave] = kc;
+    if (tid == 0) s_owner = RT - 1;
+    __syncthreads();
+    double off = 0.0, tot = 0.0; int kept = 0;
+#pragma unroll
+    for (int i = 0; i < RT / 64; ++i) { const double wt = wave_tot[i]; if (i < wave) off += wt; tot += wt; kept += wave_cnt[i]; }
+    inc += off;
+    const double target = (double)a.uniforms[b] * tot;
+    if (inc > target) atomicMin(&s_owner, tid);      // first chunk whose running sum passes the target: it holds a kept column
+    __syncthreads();
+    if (tid == s_owner) {
+        const float tf = (float)target;
+        float run = (float)(inc - (double)cs); int pick = -1, last = -1;
+        for (int v = v0; v < v1; ++v) {
+            const float f = xr[v];
+            if (f >= thr) {
+                last = v;
+                run += __expf((f - mx) * invt);
+                if (run > tf) { pick = v; break; }
+            }
+        }
+        // (rounding at the end of the chunk: its last kept column; a chunk without one cannot own the draw, the argmax is always kept)
+        s_tok = pick >= 0 ? pick : (last >= 0 ? last : bi);
+    }
+    __syncthreads();
+    const int64_t tk = s_tok;
+    if (tid == 0) {
+        const bool live = a.t == 1 ? true : a.unf_prev[b] > 0.f;
+        const float xtk = xr[tk];
+        roll_bookkeep(a, b, XG_ROLLOUT_SAMPLE, tk, xtk - lse, lse, a.maxf);
+        const size_t at = (size_t)b * (a.T - 1) + (a.t - 1);
+        if (q.kept) q.kept[at] = live ? kept : 0;
+        // log(w_tok / Z_K); Z_K holds w_tok, so the clamp only takes the rounding of the exponential and the logarithm away
+        if (q.seq_logq) q.seq_logq[at] = live ? fminf(0.f, (xtk - mx) * invt - logf((float)tot)) : 0.f;
+    }
+    for (int e = tid; e < a.E; e += RT) a.xt[(size_t)b * a.E + e] = a.table[(size_t)tk * a.E + e];
+}
 // ------------------------------------------------------------------------------------------------
 // Rollout steps of at most 128 rows (round 3): the vocabulary product and the token choice as TWO light launches instead of a
 // (B, V) product that writes 10 MB of logits and a one-workgroup-per-row pass that reads them back three times.
@@ -1136,6 +1358,19 @@ int xgk_rollout_step(hipStream_t st, int B, const RollStepArgs& a) {
         hipLaunchKernelGGL((rollout_step_kernel<true>), dim3(B), dim3(RT), lds, st, a);
     } else {
         hipLaunchKernelGGL((rollout_step_kernel<false>), dim3(B), dim3(RT), 0, st, a);
+    }
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+int xgk_rollout_trunc(hipStream_t st, int B, const RollStepArgs& r, const RollTruncArgs& q) {
+    if (r.t < 1 || !r.logits || !r.uniforms || q.top_k < 0 || !(q.top_p > 0.f && q.top_p <= 1.0f) || !(r.temperature > 0.f)) return XG_EINVAL;
+    const size_t lds = (size_t)r.V * sizeof(float);
+    if (lds <= 150 * 1024) {
+        static std::atomic<unsigned> optin{0};
+        XG_TRY(xg_lds_optin(optin, reinterpret_cast<const void*>(&rollout_trunc_kernel<true>), 150 * 1024));
+        hipLaunchKernelGGL((rollout_trunc_kernel<true>), dim3(B), dim3(RT), lds, st, r, q);
+    } else {
+        hipLaunchKernelGGL((rollout_trunc_kernel<false>), dim3(B), dim3(RT), 0, st, r, q);
     }
     XG_CHECK_LAUNCH();
     return XG_OK;

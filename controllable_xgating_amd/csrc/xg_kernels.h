@@ -358,6 +358,9 @@ int xgk_vocab_part(hipStream_t st, int B, int R, int V, const float* H, int ldh,
                    int wr_rows, float* part, float temperature);
 RollSelectArgs xgk_roll_select_args(const RollStepArgs& r, const float* part);
 int xgk_roll_select(hipStream_t st, int B, const RollStepArgs& r, const float* part);
+// the choice of a step t >= 1 as a top-k / nucleus draw from the stored raw logits: threshold search, draw inside the kept set,
+// bookkeeping and embedding gather in one launch (xg_heads.hip: rollout_trunc_kernel).  Every row samples (r.split is not read).
+int xgk_rollout_trunc(hipStream_t st, int B, const RollStepArgs& r, const RollTruncArgs& q);
 // all steps in one launch: rows (steps, B) of logits / lse / tok, dslp (B, dstride)
 int xgk_rollout_dlogits_lse(hipStream_t st, float* logits, const float* lse, const int64_t* tok, const float* dslp,
                             int64_t dstride, int B, int V, int steps);

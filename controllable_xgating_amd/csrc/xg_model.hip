@@ -14,6 +14,7 @@
 #include "xg_kernels.h"
 #include "../../include/xgate_beam.h"
 #include "../../include/xgate_control.h"
+#include "../../include/xgate_truncate.h"
 #include "../../include/xgate_score.h"
 #include "../../include/xgate_beam_control.h"
 #include "../../include/xgate_beam_allow.h"
@@ -1746,6 +1747,9 @@ struct RolloutCall {
     // PairVideos under train-mode dropout (include/xgate_pair.h): rows [split, B) take every mask -- encoder and decoder -- from
     // seed_greedy, as rows 0 .. of a call of their own (rollout_open_pair_videos_two_seeds; StepIO.drop_split_rows)
     bool two_seeds = false; uint32_t seed_greedy = 0;
+    // truncated draws (include/xgate_truncate.h): every choice t >= 1 is rollout_trunc_kernel, a launch of its own on the logits the
+    // vocabulary product stored -- neither the step's own selection nor roll_select_kernel runs.  SAMPLE mode, split = d.B.
+    const RollTruncArgs* trunc = nullptr;
 };
 static RolloutCall pair_call(const float* uniforms, float temperature, int n_sample, float* logits_alt = nullptr) {
     RolloutCall c;
@@ -1807,6 +1811,7 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
     Streams es(st, run);
     const bool rows = c.form == RolloutForm::RowsPerVideo;
     if ((c.form != RolloutForm::Plain && (!c.d1 || !c.enc)) || rows != (c.rows_per_video > 0) || !step_scratch_ok(w, false, rows)) return XG_EINVAL;
+    if (c.trunc && (mode != XG_ROLLOUT_SAMPLE || split != B || c.logits_alt)) return XG_EINVAL;     // every row draws, from this workspace's logits
     float* const state0[4] = {w.H1, w.C1, w.H2, w.C2};
     const float* pos_rows = c.form == RolloutForm::PairVideos ? w.DPOSG : x->pos_feats;
     const float *Vsrc = rows ? c.enc->Venc : w.Venc, *vproj_src = rows ? c.enc->vproj : w.vproj;
@@ -1835,7 +1840,7 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
     // (its POS-gate tiles: xg_step.hip SEL, xg_select.h) instead of a launch of its own between the vocabulary product and the step
     // -- four dependent launches per step instead of five.  The last choice of a rollout (no step follows) keeps its launch.
     static const bool no_step_select = xg_diag_env("XG_NO_STEP_SELECT") != nullptr;
-    const bool step_select = fused_select && !no_step_select && step_packed(w, *d) && xg_cdiv(d->V, xgk_vocab_tile_width(d->V)) <= 256;
+    const bool step_select = !c.trunc && fused_select && !no_step_select && step_packed(w, *d) && xg_cdiv(d->V, xgk_vocab_tile_width(d->V)) <= 256;
     for (int t = 0; t < T; ++t) {
         int64_t* tok = w.TOK + (size_t)t * B;
         float* unf = w.UNF + (size_t)t * B;
@@ -1849,6 +1854,7 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
                               t >= 1 ? w.LSE + (size_t)(t - 1) * B : nullptr, seq, seq_logp, w.alive, xt, c.temperature, d->V, E, t, T, mode, split};
         RollSelectArgs sel{};
         if (in_step) sel = xgk_roll_select_args(ra, w.VPART);
+        else if (t >= 1 && c.trunc) XG_TRY(xgk_rollout_trunc(st, B, ra, *c.trunc));
         else if (t >= 1 && fused_select) XG_TRY(xgk_roll_select(st, B, ra, w.VPART));
         else XG_TRY(xgk_rollout_step(st, B, ra));
         StepIO s = step_io_at(w, *d, slot(t));
@@ -2225,12 +2231,10 @@ extern "C" size_t xgcc_workspace_bytes(const XgDims* d, int32_t S) {
     return cc_dims_ok(d, S) ? cc_carve(*d, S, nullptr).bytes : 0;
 }
 
-extern "C" int xgcc_rollout(void* stream, const XgDims* d, int32_t S, const XgParams* p, const XgBnState* bn, const XgBatch* x,
-                            const XgRun* run, int mode, const float* uniforms, float temperature, int64_t* seq, float* seq_logp,
-                            int32_t* n_steps, void* ws, size_t ws_bytes) {
-    XG_TRY(search_args(cc_dims_ok(d, S), p, bn, x, run, seq, seq_logp, n_steps, ws));
-    if (mode != XG_ROLLOUT_GREEDY && mode != XG_ROLLOUT_SAMPLE) return XG_EINVAL;
-    if (mode == XG_ROLLOUT_SAMPLE && (!uniforms || !(temperature > 0.f))) return XG_EINVAL;
+// what xgcc_rollout and xgtr_rollout share once their arguments are checked
+static int cc_rollout(void* stream, const XgDims* d, int32_t S, const XgParams* p, const XgBnState* bn, const XgBatch* x,
+                      const XgRun* run, int mode, const float* uniforms, float temperature, int64_t* seq, float* seq_logp,
+                      int32_t* n_steps, void* ws, size_t ws_bytes, const RollTruncArgs* trunc) {
     SearchWs w = cc_carve(*d, S, ws);
     if (ws_bytes < w.bytes) return XG_EWORKSPACE;
     const int M = d->B * S;
@@ -2239,9 +2243,32 @@ extern "C" int xgcc_rollout(void* stream, const XgDims* d, int32_t S, const XgPa
     attach_packed(w.enc, de, run);
     attach_packed(w.step, dm, run);
     RolloutCall c;
-    c.mode = mode; c.uniforms = uniforms; c.temperature = temperature; c.split = M;
+    c.mode = mode; c.uniforms = uniforms; c.temperature = temperature; c.split = M; c.trunc = trunc;
     c.form = RolloutForm::RowsPerVideo; c.d1 = &de; c.enc = &w.enc; c.rows_per_video = S;
     return rollout_impl((hipStream_t)stream, &dm, p, bn, x, run, w.step, seq, seq_logp, n_steps, c);
+}
+
+extern "C" int xgcc_rollout(void* stream, const XgDims* d, int32_t S, const XgParams* p, const XgBnState* bn, const XgBatch* x,
+                            const XgRun* run, int mode, const float* uniforms, float temperature, int64_t* seq, float* seq_logp,
+                            int32_t* n_steps, void* ws, size_t ws_bytes) {
+    XG_TRY(search_args(cc_dims_ok(d, S), p, bn, x, run, seq, seq_logp, n_steps, ws));
+    if (mode != XG_ROLLOUT_GREEDY && mode != XG_ROLLOUT_SAMPLE) return XG_EINVAL;
+    if (mode == XG_ROLLOUT_SAMPLE && (!uniforms || !(temperature > 0.f))) return XG_EINVAL;
+    return cc_rollout(stream, d, S, p, bn, x, run, mode, uniforms, temperature, seq, seq_logp, n_steps, ws, ws_bytes, nullptr);
+}
+
+// ---- truncated sampling (include/xgate_truncate.h): the rollout above with every choice t >= 1 a top-k / nucleus draw
+extern "C" int xgtr_version(void) { return XGTR_VERSION; }
+
+extern "C" size_t xgtr_workspace_bytes(const XgDims* d, int32_t S) { return xgcc_workspace_bytes(d, S); }
+
+extern "C" int xgtr_rollout(void* stream, const XgDims* d, int32_t S, const XgParams* p, const XgBnState* bn, const XgBatch* x,
+                            const XgRun* run, int32_t top_k, float top_p, const float* uniforms, float temperature, int64_t* seq,
+                            float* seq_logp, float* seq_logq, int32_t* kept, int32_t* n_steps, void* ws, size_t ws_bytes) {
+    XG_TRY(search_args(cc_dims_ok(d, S), p, bn, x, run, seq, seq_logp, n_steps, ws));
+    if (top_k < 0 || !(top_p > 0.f && top_p <= 1.0f) || !uniforms || !(temperature > 0.f)) return XG_EINVAL;
+    const RollTruncArgs q{top_k, top_p, kept, seq_logq};
+    return cc_rollout(stream, d, S, p, bn, x, run, XG_ROLLOUT_SAMPLE, uniforms, temperature, seq, seq_logp, n_steps, ws, ws_bytes, &q);
 }
 
 // ---- scoring given captions (include/xgate_score.h): Q caption rows per video, M = B Q rows, the videos once (videos_once) and

@@ -36,6 +36,14 @@ __host__ __device__ __forceinline__ int rs_per(int ntiles) { return (ntiles + 15
 __host__ __device__ __forceinline__ int rs_pitch(int ntiles) { return rs_per(ntiles) << 4; }
 __host__ __device__ __forceinline__ int rs_slot(int j, int per) { return (j % per) * 16 + j / per; }
 static_assert(sizeof(RollSelectArgs) <= 176, "RollSelectArgs rides in SkArgs (kernel-argument budget, xg_kernels.h)");
+// The truncated draw (rollout_trunc_kernel, xg_heads.hip; docs/CAPTION_TRUNCATED.md) takes these beside RollStepArgs: it is a launch
+// of its own, so nothing here rides in the step kernel's argument budget.
+struct RollTruncArgs {
+    int top_k;                // 0 (or >= V): off
+    float top_p;              // in (0, 1]; 1: off
+    int32_t* kept;            // (B,Tm1) size of the kept set, 0 after a row's end token; may be null
+    float* seq_logq;          // (B,Tm1) log-probability of the token under the truncated, tempered distribution; may be null
+};
 
 // the per-row bookkeeping of a rollout step once its token is chosen (one thread): unfinished &= it > 0 ; it *= unfinished ;
 // append (SAModel.py:200-210), the running "first step at which every row is finished" (:211-215)

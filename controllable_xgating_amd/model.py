@@ -592,6 +592,52 @@ class SAModel(FlatParams, nn.Module):
         n = int(n.item())
         return seq[:, :, :n], slp[:, :, :n]
 
+    def sample_truncated_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, top_k=0, top_p=1.0, temperature=1.0,
+                                   uniforms=None, generator=None, return_stats=False, trim=True):
+        """``sample_per_video`` in sampled mode with TOP-K and NUCLEUS truncation (include/xgate_truncate.h, docs/CAPTION_TRUNCATED.md):
+        every word is drawn from softmax(logits / temperature) restricted to the `top_k` largest logits (0: off) and, inside those,
+        to the smallest set of whole value classes whose mass reaches `top_p` (1: off); ties at either threshold are kept.
+        `pos_feats` is (B,S,R) -- (B,1,R) is the plain one-row-per-video case.  Returns (seq (B,S,n) int64, seqLogprobs (B,S,n)):
+        the log-probabilities are the UNTEMPERED, UNTRUNCATED ones, as ``sample`` gives them.  ``return_stats=True`` adds seq_logq
+        (B,S,n), the log-probability under the distribution actually drawn from (what an importance weight or a reranker needs),
+        and kept (B,S,n) int32, the size of the kept set; both are 0 behind a row's end token.
+
+        `uniforms` (L + 1, B*S) on the device; None: ``torch.rand(L + 1, B*S, device=..., generator=generator)``.  ``trim=False``:
+        no host sync -- full-width (B,S,L) tensors and the device-side n after them.  Eval mode, fp32 and device tensors only;
+        one enqueue, no host work per step.  Nothing returned carries an autograd graph."""
+        from . import _native_truncate as ntr
+        self._search_gate("sample_truncated_per_video")
+        top_k, top_p, temperature = int(top_k), float(top_p), float(temperature)
+        if top_k < 0:
+            raise ValueError("top_k >= 0 expected (0: off), got %d" % top_k)
+        if not (0.0 < top_p <= 1.0):
+            raise ValueError("top_p in (0, 1] expected (1: off), got %r" % top_p)
+        if not (0.0 < temperature < float("inf")):
+            raise ValueError("temperature must be finite and > 0, got %r" % temperature)
+        inputs = (feats_rgb, feats_opfl, feat_mask, pos_feats)
+        B, K, S, L, dev, d = self._search_open("sample_truncated_per_video", inputs, True)
+        M = B * S
+        if uniforms is None:
+            uniforms = torch.rand(L + 1, M, device=dev, dtype=torch.float32, generator=generator)
+        uniforms = uniforms.detach().contiguous().float()
+        if tuple(uniforms.shape) != (L + 1, M) or not uniforms.is_cuda:
+            raise ValueError("uniforms (L + 1 = %d, B*S = %d) on the device expected, got %s" % (L + 1, M, tuple(uniforms.shape)))
+        lib = ntr.lib()
+        args, wp, wn, keep = self._search_call("_control_ws", (B, K, L, S, str(dev)), lambda: lib.xgtr_workspace_bytes(C.byref(d), S),
+                                               "xgtr_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (B, S), inputs)
+        seq = torch.empty(B, S, L, dtype=torch.int64, device=dev)
+        slp = torch.empty(B, S, L, dtype=torch.float32, device=dev)
+        slq = torch.empty(B, S, L, dtype=torch.float32, device=dev) if return_stats else None
+        kept = torch.empty(B, S, L, dtype=torch.int32, device=dev) if return_stats else None
+        n = torch.empty(1, dtype=torch.int32, device=dev)
+        nv.check(lib.xgtr_rollout(_stream(), C.byref(d), S, *args, top_k, top_p, nv.ptr(uniforms), temperature, nv.ptr(seq), nv.ptr(slp),
+                                  nv.ptr(slq), nv.ptr(kept), nv.ptr(n), wp, wn), "xgtr_rollout")
+        out = (seq, slp, slq, kept) if return_stats else (seq, slp)
+        if not trim:
+            return out + (n,)
+        n = int(n.item())
+        return tuple(o[:, :, :n] for o in out)
+
     def beam_captions(self, feats_rgb, feats_opfl, feat_mask, pos_feats, beam_size=5, suppress_token=1, return_trace=False):
         """The W = beam_size captions the model finds most likely for each of the B videos (include/xgate_beam.h: the search of
         beam.py / the reference's sample_beam, SAModel.py:129-161, as ONE enqueue with no host work per step).  Returns (seq
