@@ -252,6 +252,70 @@ def template_adherence(seq, allow, word_cat):
     return (ok | ~counted).all(3)
 
 
+def length_scale_table(seq_length, alpha, kind="avg"):
+    """The (L,) float32 `length_scale` of ``SAModel.beam_captions_ruled`` (include/xgate_beam_rules.h): entry t scales the score of
+    a beam that finishes at step t, i.e. one of t + 1 tokens with its end token.  kind "avg": (t + 1) ** -alpha (alpha = 1: the
+    mean log-probability per token); kind "wu": ((5 + t + 1) / 6) ** -alpha (the GNMT length penalty).  Computed in float64 and
+    rounded once to fp32; every entry lies in (0, 1].  alpha >= 0; alpha = 0 gives all ones."""
+    L, alpha = int(seq_length), float(alpha)
+    if L < 1:
+        raise ValueError("seq_length >= 1 expected, got %d" % L)
+    if not (0.0 <= alpha < float("inf")):
+        raise ValueError("alpha must be finite and >= 0, got %r" % (alpha,))
+    n = np.arange(1, L + 1, dtype=np.float64)
+    if kind == "avg":
+        base = n
+    elif kind == "wu":
+        base = (5.0 + n) / 6.0
+    else:
+        raise ValueError("kind 'avg' or 'wu' expected, got %r" % (kind,))
+    return torch.from_numpy(np.power(base, -alpha).astype(np.float32))
+
+
+def repeated_ngrams(seq, n):
+    """(..) bool for captions seq (.., L): True where the caption's words -- its tokens before the first 0, all L when it has none
+    -- hold the same n-gram at two different positions.  Torch ops on `seq`'s device; nothing is read back."""
+    seq, n = torch.as_tensor(seq), int(n)
+    if n < 1:
+        raise ValueError("n >= 1 expected, got %d" % n)
+    if seq.dim() < 1 or seq.is_floating_point():
+        raise ValueError("seq (.., L) integer tokens expected")
+    L = seq.shape[-1]
+    if n >= L:                                       # at most one n-gram
+        return torch.zeros(seq.shape[:-1], dtype=torch.bool, device=seq.device)
+    words = (seq != 0).long().cumprod(-1).sum(-1)                                   # (..)
+    g = seq.unfold(-1, n, 1)                                                        # (.., L-n+1, n)
+    P = g.shape[-2]
+    valid = torch.arange(P, device=seq.device) + n <= words.unsqueeze(-1)           # (.., P): the n-gram lies inside the words
+    same = (g.unsqueeze(-2) == g.unsqueeze(-3)).all(-1)                             # (.., P, P)
+    later = torch.ones(P, P, dtype=torch.bool, device=seq.device).triu(1)
+    return (same & later & valid.unsqueeze(-1) & valid.unsqueeze(-2)).flatten(-2).any(-1)
+
+
+def beam_captions_ruled_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, word_cat=None,
+                                       constraints=None, built=False, **rules):
+    """``beam_captions_with_templates`` -- with `word_cat`, ``beam_captions_following_templates`` -- under decoding rules: (seq
+    (B,S,W,L) int64, seq_logp (B,S,W,L), score (B,S,W), key (B,S,W), template_score (B,S)).  The forced POS rollout
+    (``pos_model.sample_forced``) leaves `pos_feats` on the device and ``cap_model.beam_captions_ruled``
+    (include/xgate_beam_rules.h) takes the B videos once; `rules` are that method's keywords (beam_size, suppress_token,
+    no_repeat_ngram, min_length, bad_endings, length_scale).  `word_cat` (V,) uint8 on the device turns the hard template
+    constraint on: `constraints` and `built` as ``beam_captions_following_templates`` takes them, None: the templates themselves.
+    Inference only: both models run under ``torch.no_grad()``."""
+    if word_cat is None and constraints is not None:
+        raise ValueError("constraints need word_cat")
+    with torch.no_grad():
+        tag_logp, _, _, pos_feats = pos_model.sample_forced(feats_rgb, feats_opfl, feat_mask, templates, collect_states=False,
+                                                            trim=False)
+        B, S, L = tag_logp.shape
+        allow = None
+        if word_cat is not None:
+            allow = allow_masks(templates if constraints is None else constraints, L, built=built and constraints is not None)
+            allow = allow.to(pos_feats.device)
+        seq, seq_logp, score, key = cap_model.beam_captions_ruled(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(B, S, -1),
+                                                                  word_cat=word_cat, allow=allow, **rules)
+    return seq, seq_logp, score, key, tag_logp.sum(2)
+
+
 def score_captions_with_templates(pos_model, cap_model, feats_rgb, feats_opfl, feat_mask, templates, captions, cross=False):
     """Score GIVEN captions of each of the B videos under its S POS templates, on one captioner encoder pass: (tok_logp, score,
     count, template_score (B,S)).  The forced POS rollout (``pos_model.sample_forced``) leaves `pos_feats` (B*S,R) on the device and

@@ -9,6 +9,8 @@
 //                          list (the search over S templates per video, include/xgate_beam_control.h, has S times the rows).
 //   cap_beam_topw_allow_kernel  the threshold form over a row's ALLOWED words (include/xgate_beam_allow.h): the log-sum-exp runs over
 //                          them alone and every other word is lowered by 1000 like the suppressed one.
+//   cap_beam_topw_rules_kernel  either threshold form with 1000 more off the words a row's history bans (include/xgate_beam_rules.h):
+//                          the ban is applied to the <= L + 1 banned elements alone.
 //   cap_beam_merge_kernel  one workgroup per video: fills the candidate tables from topv / topi, runs steps 3-5 of the rule
 //                          (beam_merge, xg_beam_core.h), and every thread gathers h1, c1, h2, c2 of slot v from its parent out of
 //                          the step's OUTPUT buffer into its INPUT buffer.
@@ -16,6 +18,7 @@
 // row-repeats what was computed once per video (xgk_compact copies contiguous blocks: rows b W + slot of video b are not one).
 #include "xg_common.h"
 #include "xg_kernels.h"
+#include "../../include/xgate_beam_rules.h"
 
 namespace {
 
@@ -437,6 +440,217 @@ int launch_topw_allow(hipStream_t st, const float* logits, int64_t ld, int M, in
     return XG_OK;
 }
 
+// ---- the selection under RULES (include/xgate_beam_rules.h; only xgbr_beam_search launches it): cap_beam_topw_allow_kernel (ALLOW) or
+// cap_beam_topw_thr_kernel (no template constraint) with 1000 more off every word of the row's banned set.  The log-sum-exp is the
+// unbanned one, summed in the order of those kernels, so an empty set gives their bits.
+// Prologue: the row's t <= L history tokens go to LDS; thread i < t - n + 1 compares the n - 1 words from start i with the last n - 1
+// and names h[i+n-1] on a match, one more entry is word 0 (t < min_length, or wave 0 found h[t-1] in bad_end); an entry whose word an
+// earlier entry names is dropped, so a word is lowered ONCE.  The <= L + 1 entries (holes: -1) and their exact values
+// ((x - lse) - ..) - 1000 stand behind the row in dynamic LDS.
+// Staged, entry j's thread then overwrites element w of the row with a quiet NaN whose payload is j: the passes over the row test
+// x != x -- one compare per element, no list -- and only the <= L + 1 marked elements read their value from the list.  Unstaged (a row
+// beyond CB_STAGE_BYTES is never written), an index inside [lowest, highest banned word] walks the list.
+constexpr int RB_LMAX = XGBR_MAX_LENGTH;
+constexpr int RB_EXTRA_BYTES = 2 * (RB_LMAX + 1) * 4;
+static_assert(RB_LMAX + 1 <= TW_TPB, "one thread per entry of the ban list");
+static_assert(CB_STAGE_BYTES + RB_EXTRA_BYTES + 2048 <= 160 * 1024, "row, history and ban list, and the static tables, fit the CU's LDS");
+static_assert(RB_LMAX + 1 < (1 << 22), "an entry's index fits a quiet NaN's payload");
+
+template <int W, bool STAGE, bool ALLOW>
+__global__ void __launch_bounds__(TW_TPB) cap_beam_topw_rules_kernel(const float* __restrict__ logits, int64_t ld, int V, int suppress,
+                                                                     const uint8_t* __restrict__ word_cat,
+                                                                     const uint32_t* __restrict__ allow, int64_t astride, CapBeamBan ban,
+                                                                     int row_floats, float* __restrict__ topv, int32_t* __restrict__ topi) {
+    extern __shared__ float4 cb_lds4[];
+    __shared__ float red[TW_WAVES], cv[TW_WAVES * W], lv[TW_CAND], tau_s;
+    __shared__ int ci[TW_WAVES * W], li[TW_CAND], cnt_s, any_w[TW_WAVES], ban0_s, lo_s, hi_s;
+    const TopwRow<STAGE> r(logits, ld, V, cb_lds4);
+    const int tid = r.tid, lane = tid & 63, wave = tid >> 6;
+    int* bw = reinterpret_cast<int*>(cb_lds4) + row_floats;       // (L + 1) the banned words, -1: a hole
+    int* hs = bw + (ban.L + 1);                                   // (L) the history; dead once bw stands, then
+    float* bx = reinterpret_cast<float*>(hs);                     // (L + 1) the entries' values
+    const int t = ban.t, n = ban.ngram;
+    auto word = [&](int w) { return w < 0 ? 0 : (w >= V ? V - 1 : w); };
+    if (tid == 0) { cnt_s = 0; lo_s = 0x7fffffff; hi_s = -1; }    // (barriers below come before their first use)
+    // ---- the history, and the two conditions on word 0
+    const int32_t* h = ban.hist + (size_t)blockIdx.x * ban.L;
+    for (int i = tid; i < t; i += TW_TPB) hs[i] = word(h[i]);
+    if (wave == 0) {
+        bool hit = false;
+        if (t >= 1 && lane < ban.n_bad_end) hit = word(ban.bad_end[lane]) == word(h[t - 1]);
+        const unsigned long long hits = __ballot(hit);
+        if (lane == 0) ban0_s = (t < ban.min_length || hits != 0) ? 1 : 0;
+    }
+    __syncthreads();
+    // ---- the entries: one per start of an earlier n-gram, then word 0's
+    const int ng = (n >= 1 && t >= n) ? t - n + 1 : 0, nslots = ng + 1;
+    if (tid < ng) {
+        bool same = true;
+        for (int k = 0; k + 1 < n; ++k) same = same && hs[tid + k] == hs[t - n + 1 + k];
+        bw[tid] = same ? hs[tid + n - 1] : -1;
+    }
+    if (tid == ng) bw[ng] = ban0_s ? 0 : -1;
+    __syncthreads();
+    int mine = -1;                                                // entry tid's word, if no earlier entry names it
+    if (tid < nslots) {
+        mine = bw[tid];
+        for (int j = 0; j < tid && mine >= 0; ++j) mine = bw[j] == mine ? -1 : mine;
+    }
+    __syncthreads();
+    if (tid < nslots) {
+        bw[tid] = mine;
+        if (mine >= 0) { atomicMin(&lo_s, mine); atomicMax(&hi_s, mine); }
+    }
+    // ---- the row's one trip from memory (staged) and its log-sum-exp, as the kernel without rules forms it
+    TopwAllowed<STAGE> ok{word_cat, 0u, 0ull};
+    float lse;
+    if constexpr (ALLOW) {
+        ok.mask = allow[(size_t)(blockIdx.x / W) * astride];
+        bool any = false;
+        if constexpr (STAGE) {
+            for (int i = tid, k = 0; i < V; i += TW_TPB, ++k)
+                ok.bits |= (unsigned long long)((ok.mask >> (word_cat[i] & 31)) & 1u) << k;
+            any = ok.bits != 0;
+            if (tid < r.head) r.row[tid] = r.g[tid];
+            for (int j = tid; j < r.nvec; j += TW_TPB) *reinterpret_cast<float4*>(r.row + r.head + 4 * j) = r.g4[j];
+            if (r.tail0 + tid < V) r.row[r.tail0 + tid] = r.g[r.tail0 + tid];
+        } else {
+            for (int i = tid; i < V; i += TW_TPB) any = any || ok(i);
+        }
+        const unsigned long long some = __ballot(any);
+        if (lane == 0) any_w[wave] = some != 0 ? 1 : 0;
+        __syncthreads();
+        int found = 0;
+#pragma unroll
+        for (int k = 0; k < TW_WAVES; ++k) found |= any_w[k];
+        if (!found) { ok.mask = 0xFFFFFFFFu; ok.bits = ~0ull; }
+        float mx = -INFINITY;
+        r.each([&](float x, int i) { if (ok(i)) mx = fmaxf(mx, x); });
+        mx = wave_max(mx);
+        if (lane == 0) red[wave] = mx;
+        __syncthreads();
+        mx = red[0];
+#pragma unroll
+        for (int k = 1; k < TW_WAVES; ++k) mx = fmaxf(mx, red[k]);
+        __syncthreads();
+        float s = 0.f;
+        r.each([&](float x, int i) { if (ok(i)) s += __expf(x - mx); });
+        s = wave_sum(s);
+        if (lane == 0) red[wave] = s;
+        __syncthreads();
+        float tot = 0.f;
+#pragma unroll
+        for (int k = 0; k < TW_WAVES; ++k) tot += red[k];
+        lse = mx + logf(tot);
+    } else {
+        lse = r.stage_lse(red);
+    }
+    // ---- every entry's exact value; staged, its element of the row becomes the mark that leads to it
+    if (tid < nslots) {
+        float v = __uint_as_float(0x7FC00000u);
+        if (mine >= 0) {
+            float x;
+            if constexpr (STAGE) x = r.row[mine]; else x = r.g[mine];
+            v = x - lse;
+            if constexpr (ALLOW) { if (!((ok.mask >> (word_cat[mine] & 31)) & 1u)) v -= 1000.0f; }
+            if (mine == suppress) v -= 1000.0f;
+            v -= 1000.0f;
+        }
+        bx[tid] = v;
+        if constexpr (STAGE) { if (mine >= 0) r.row[mine] = __uint_as_float(0x7FC00000u | (unsigned)tid); }   // (distinct words: no two threads meet)
+    }
+    __syncthreads();
+    const int lo = lo_s, hi = hi_s;
+    auto val = [&](float x, int i) -> float {
+        if constexpr (STAGE) {
+            if (x != x) {
+                const unsigned j = __float_as_uint(x) & 0x3FFFFFu;
+                return j < (unsigned)nslots ? bx[j] : x;          // (a NaN of the row's own stays one: it ranks nowhere)
+            }
+        } else {
+            if (i >= lo && i <= hi) {
+                for (int j = 0; j < nslots; ++j) if (bw[j] == i) return bx[j];
+            }
+        }
+        float v = x - lse;
+        if constexpr (ALLOW) { if (!ok(i)) v -= 1000.0f; }
+        if (i == suppress) v -= 1000.0f;
+        return v;
+    };
+    // ---- the threshold selection of cap_beam_topw_thr_kernel over val
+    float tm = -INFINITY;
+    r.each([&](float x, int i) { tm = fmaxf(tm, val(x, i)); });
+#pragma unroll
+    for (int rd = 0; rd < W; ++rd) {
+        const float m = wave_max(tm);
+        const unsigned long long holders = __ballot(tm == m);
+        if (lane == 0) cv[wave * W + rd] = m;
+        if (holders != 0 && lane == __ffsll(holders) - 1) tm = -INFINITY;
+    }
+    __syncthreads();
+    if (tid < TW_WAVES * W) {
+        const float v = cv[tid];
+        int rank = 0;
+        for (int j = 0; j < TW_WAVES * W; ++j) {
+            const float ov = cv[j];
+            rank += (ov > v || (ov == v && j < tid)) ? 1 : 0;
+        }
+        if (rank == W - 1) tau_s = v;
+    }
+    __syncthreads();
+    const float tau = tau_s;
+    r.each([&](float x, int i) {
+        const float v = val(x, i);
+        if (v >= tau) {
+            const int at = atomicAdd(&cnt_s, 1);
+            if (at < TW_CAND) { lv[at] = v; li[at] = i; }
+        }
+    });
+    __syncthreads();
+    const int nc = cnt_s;
+    if (nc < W || nc > TW_CAND) {                                 // uniform over the workgroup
+        topw_by_insertion_of<W, STAGE>(r, val, cv, ci, topv, topi);
+        return;
+    }
+    if (tid < nc) {
+        const float v = lv[tid];
+        const int ix = li[tid];
+        int rank = 0;
+        for (int j = 0; j < nc; ++j) rank += beam_before(lv[j], li[j], v, ix) ? 1 : 0;
+        if (rank < W) {
+            topv[(size_t)blockIdx.x * W + rank] = v;
+            topi[(size_t)blockIdx.x * W + rank] = ix;             // (an index of `each`: inside [0, V))
+        }
+    }
+}
+
+template <int W, bool ALLOW>
+int launch_topw_rules(hipStream_t st, const float* logits, int64_t ld, int M, int V, int suppress, const uint8_t* word_cat,
+                      const uint32_t* allow, int64_t astride, const CapBeamBan& ban, float* topv, int32_t* topi) {
+    const size_t row = ((size_t)V + 8) * sizeof(float), extra = 2 * ((size_t)ban.L + 1) * sizeof(int);
+    if (row <= (size_t)CB_STAGE_BYTES) {                       // (the bound of the kernels without rules: the same form, the same sums)
+        if (row + extra > 64 * 1024) {
+            static std::atomic<unsigned> optin{0};
+            XG_TRY(xg_lds_optin(optin, reinterpret_cast<const void*>(cap_beam_topw_rules_kernel<W, true, ALLOW>),
+                                CB_STAGE_BYTES + RB_EXTRA_BYTES));
+        }
+        hipLaunchKernelGGL((cap_beam_topw_rules_kernel<W, true, ALLOW>), dim3(M), dim3(TW_TPB), row + extra, st, logits, ld, V, suppress,
+                           word_cat, allow, astride, ban, V + 8, topv, topi);
+    } else {
+        hipLaunchKernelGGL((cap_beam_topw_rules_kernel<W, false, ALLOW>), dim3(M), dim3(TW_TPB), extra, st, logits, ld, V, suppress,
+                           word_cat, allow, astride, ban, 0, topv, topi);
+    }
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+
+template <int W>
+int launch_topw_rules_any(hipStream_t st, const float* logits, int64_t ld, int M, int V, int suppress, const uint8_t* word_cat,
+                          const uint32_t* allow, int64_t astride, const CapBeamBan& ban, float* topv, int32_t* topi) {
+    return allow ? launch_topw_rules<W, true>(st, logits, ld, M, V, suppress, word_cat, allow, astride, ban, topv, topi)
+                 : launch_topw_rules<W, false>(st, logits, ld, M, V, suppress, word_cat, allow, astride, ban, topv, topi);
+}
+
 template <int W, bool THR>
 int launch_topw(hipStream_t st, const float* logits, int64_t ld, int M, int V, int suppress, float* topv, int32_t* topi) {
     using Kernel = void (*)(const float*, int64_t, int, int, float*, int32_t*);
@@ -504,6 +718,14 @@ __global__ void __launch_bounds__(CB_TPB) cap_beam_merge_kernel(CapBeamMergeArgs
             const int k = i / (W * R), rem = i - k * (W * R);
             const int v = rem / R, j = rem - v * R;
             a.dst[k][(row0 + v) * R + j] = a.src[k][(row0 + T.s_q[v]) * R + j];
+        }
+    }
+    // under rules slot v's history is its parent's t tokens and, appended, its own
+    if (a.hdst) {
+        const int t = a.book.t, L = a.book.L;
+        for (int i = tid; i < W * (t + 1); i += CB_TPB) {
+            const int v = i / (t + 1), j = i - v * (t + 1);
+            a.hdst[(row0 + v) * L + j] = j < t ? a.hsrc[(row0 + T.s_q[v]) * L + j] : T.s_tok[v];
         }
     }
 }
@@ -574,9 +796,30 @@ int xgk_cap_beam_topw_allow(hipStream_t st, const float* logits, int64_t ld, int
     }
 }
 
+int xgk_cap_beam_topw_rules(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, const uint8_t* word_cat,
+                            const uint32_t* allow, int64_t astride, const CapBeamBan& ban, float* topv, int32_t* topi) {
+    if (M <= 0 || V <= 0 || W < 1 || W > CB_MAX || W > V || ld < V || suppress >= V || !word_cat != !allow || astride < 1 || M % W)
+        return XG_EINVAL;
+    if (!ban.hist || ban.L < 1 || ban.L > RB_LMAX || ban.t < 0 || ban.t >= ban.L || ban.ngram < 0 || ban.min_length < 0 ||
+        ban.n_bad_end < 0 || ban.n_bad_end > XGBR_MAX_BAD_END || (ban.n_bad_end > 0 && !ban.bad_end))
+        return XG_EINVAL;
+    if (suppress < 0) suppress = -1;
+    switch (W) {
+        case 1: return launch_topw_rules_any<1>(st, logits, ld, M, V, suppress, word_cat, allow, astride, ban, topv, topi);
+        case 2: return launch_topw_rules_any<2>(st, logits, ld, M, V, suppress, word_cat, allow, astride, ban, topv, topi);
+        case 3: return launch_topw_rules_any<3>(st, logits, ld, M, V, suppress, word_cat, allow, astride, ban, topv, topi);
+        case 4: return launch_topw_rules_any<4>(st, logits, ld, M, V, suppress, word_cat, allow, astride, ban, topv, topi);
+        case 5: return launch_topw_rules_any<5>(st, logits, ld, M, V, suppress, word_cat, allow, astride, ban, topv, topi);
+        case 6: return launch_topw_rules_any<6>(st, logits, ld, M, V, suppress, word_cat, allow, astride, ban, topv, topi);
+        case 7: return launch_topw_rules_any<7>(st, logits, ld, M, V, suppress, word_cat, allow, astride, ban, topv, topi);
+        default: return launch_topw_rules_any<8>(st, logits, ld, M, V, suppress, word_cat, allow, astride, ban, topv, topi);
+    }
+}
+
 int xgk_cap_beam_merge(hipStream_t st, int B, CapBeamMergeArgs a) {
     const BeamBook<int64_t>& k = a.book;
     if (B <= 0 || k.W < 1 || k.W > CB_MAX || a.R <= 0 || k.L <= 0 || k.t < 0 || k.t >= k.L) return XG_EINVAL;
+    if ((a.hdst && !a.hsrc) || (k.scale && !k.done_key)) return XG_EINVAL;
     uintptr_t bits = 0;
     for (int k = 0; k < 4; ++k) bits |= reinterpret_cast<uintptr_t>(a.src[k]) | reinterpret_cast<uintptr_t>(a.dst[k]);
     a.vec = (a.R % 4 == 0 && bits % 16 == 0) ? 1 : 0;

@@ -10,6 +10,8 @@
 //      caller, whose threads gather slot v's state from parent s_q[v].
 //   5. still thread 0, for v = 0 .. W-1 in order: a token 0, or t = L-1, enters the video's best-W done list with score p, AFTER
 //      entries of equal score (so the list is the first W of a stable descending sort of every completion), and sum[v] = -1000.
+//      With a `scale` table in the book (include/xgate_beam_rules.h) the list is ordered by KEY instead: key = p * scale[t] (one
+//      fp32 multiply) for a live p > -500, else p; done_key holds the keys beside done_score.  scale == null: the rule above.
 // beam_backtrace_row then follows a done entry's parents back through trace.
 // Plain stores from one lane, no atomics, one fixed order for every sum.
 #pragma once
@@ -34,6 +36,8 @@ struct BeamBook {
     int32_t* done_at;            // (B,W,2) their (step, slot)
     int32_t* done_n;             // (B) how many (not read at t = 0)
     int L, W, t;
+    const float* scale;          // (L) the done list's length scale, or null: the list is ordered by score
+    float* done_key;             // (B,W) the keys of the done list; only with `scale`
 };
 
 // the book's regions out of a workspace, in their one order; trace_out and t are the call's.  Carver: take<T>(n)
@@ -56,6 +60,8 @@ struct BeamTables {
     int s_q[XG_BEAM_MAX], s_tok[XG_BEAM_MAX];
 };
 static_assert(sizeof(BeamTables) == 896, "the fixed part of XGPB_LDS_BYTES (1024) accounts for 896 bytes of tables");
+
+constexpr float XG_BEAM_LIVE = -500.0f;      // the dead-slot rule: a sum at or below this carries a -1000
 
 // the order of the search: is (v, i) before (ov, oi)?  Larger value first, lower index first on exact ties.  Total on non-NaN
 // values; a NaN is before nothing and nothing is before it, so it ranks nowhere and is never kept.
@@ -92,6 +98,7 @@ __device__ __forceinline__ void beam_merge(BeamTables& T, const BeamBook<Tok>& k
     __syncthreads();
     if (tid != 0) return;
     float* ds = k.done_score + row0;
+    float* dk = k.scale ? k.done_key + row0 : ds;             // what the list is ordered by
     int32_t* da = k.done_at + row0 * 2;
     int n = t == 0 ? 0 : k.done_n[b];
     n = n < 0 ? 0 : (n > W ? W : n);
@@ -104,12 +111,18 @@ __device__ __forceinline__ void beam_merge(BeamTables& T, const BeamBook<Tok>& k
         k.tok[row0 + v] = T.s_tok[v];
         float sm = T.s_p[v];
         if (T.s_tok[v] == 0 || t == L - 1) {
+            float key = sm;
+            if (k.scale && sm > XG_BEAM_LIVE) key = __fmul_rn(sm, k.scale[t]);
             int pos = n;
-            while (pos > 0 && ds[pos - 1] < sm) --pos;         // after entries of equal score
+            while (pos > 0 && dk[pos - 1] < key) --pos;        // after entries of equal score (key)
             if (pos < W) {
                 const int last = n < W ? n : W - 1;
-                for (int i = last; i > pos; --i) { ds[i] = ds[i - 1]; da[2 * i] = da[2 * i - 2]; da[2 * i + 1] = da[2 * i - 1]; }
+                for (int i = last; i > pos; --i) {
+                    ds[i] = ds[i - 1]; da[2 * i] = da[2 * i - 2]; da[2 * i + 1] = da[2 * i - 1];
+                    if (k.scale) dk[i] = dk[i - 1];
+                }
                 ds[pos] = sm; da[2 * pos] = t; da[2 * pos + 1] = v;
+                if (k.scale) dk[pos] = key;
                 if (n < W) ++n;
             }
             sm = -1000.0f;
@@ -152,8 +165,6 @@ __device__ __forceinline__ void beam_backtrace_row(const BeamBook<Tok>& k, size_
 //      pair go to G.par (pair slot indices) for the caller's state gather, the caller's trace is (pairs,L,N,2) with pair slot
 //      parents, and the group's live new tokens join the penalty list.  Ends with a barrier: the next group may start at once.
 // n_j(v) = 0 or lambda = 0 leave lp as it is (lp - 0), so Gd = 1 is beam_merge bit for bit.
-constexpr float XG_BEAM_LIVE = -500.0f;      // the dead-slot rule: a sum at or below this carries a -1000
-
 struct BeamGroupTables {
     BeamTables T;
     float c_r[XG_BEAM_MAX * XG_BEAM_MAX];    // the unpenalised lp of candidate entry [q * XG_BEAM_MAX + k]

@@ -394,7 +394,16 @@ struct CapBeamMergeArgs {
     BeamBook<int64_t> book;
     const float* src[4]; float* dst[4];       // h1, c1, h2, c2 (M,R): what the step wrote -> what the next step reads
     int R, V, vec;                // (vec: set by the launcher)
+    const int32_t* hsrc; int32_t* hdst;       // per-row histories (M,L) under rules (include/xgate_beam_rules.h), or null: slot v's
+                                              // becomes its parent's first t tokens with the new token appended
 };
+// the selection under rules (include/xgate_beam_rules.h): the threshold form over lp less 1000 at every word of the row's banned set
+// -- built from its history hist[m * L .. + t) (tokens clamped into [0, V)): the no-repeat n-gram words, word 0 while t < min_length,
+// word 0 behind a bad_end word -- after the 1000 of a word that is not allowed and of `suppress`.  word_cat / allow / astride as in
+// xgk_cap_beam_topw_allow, or both null: the plain log-softmax.  L <= XGBR_MAX_LENGTH.
+struct CapBeamBan { const int32_t* hist; int L, t, ngram, min_length; const int32_t* bad_end; int n_bad_end; };
+int xgk_cap_beam_topw_rules(hipStream_t st, const float* logits, int64_t ld, int M, int V, int W, int suppress, const uint8_t* word_cat,
+                            const uint32_t* allow, int64_t astride, const CapBeamBan& ban, float* topv, int32_t* topi);
 int xgk_cap_beam_merge(hipStream_t st, int B, CapBeamMergeArgs a);
 // the diverse form (include/xgate_beam_diverse.h): a.book carved as (pairs Gd, Wg, L), topv / topi (pairs Gd Wg, Gd Wg) from the
 // selection at W = Gd Wg; the groups of a pair merged in series under lambda times the earlier groups' live new words

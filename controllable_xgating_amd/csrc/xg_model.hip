@@ -18,6 +18,7 @@
 #include "../../include/xgate_score.h"
 #include "../../include/xgate_beam_control.h"
 #include "../../include/xgate_beam_allow.h"
+#include "../../include/xgate_beam_rules.h"
 #include "../../include/xgate_beam_diverse.h"
 #include "../../include/xgate_pair.h"
 
@@ -2103,16 +2104,54 @@ int search_args(bool dims, const XgParams* p, const XgBnState* bn, const XgBatch
 // (include/xgate_beam_allow.h) step t's selection is the allowed form over column t of the (G,L) masks.  Without one the launches,
 // their order and their arguments are what they were.  Under `dv` (include/xgate_beam_diverse.h) W = Gd Wg: the selection is the
 // threshold form at W = N, unchanged, the book is carved as (G Gd, Wg, L) and the merge is the diverse one; without it likewise.
+// Under rules `br` (include/xgate_beam_rules.h; S >= 1, never with `dv`): the workspace grows by two blocks of per-row histories and
+// the done list's keys (rules_carve), the merge appends to the histories and orders its done list by key when a scale is given, and,
+// when a ban can fire at all (n >= 1, min_length >= 1 or a bad_end list), every step's selection is the rules form over the block
+// the merge before it wrote.  Rules that can ban nothing leave the selection launches what they are without `br`.
 struct BeamAllow { const uint8_t* word_cat; const uint32_t* allow; };
 struct BeamDiverse { int Gd, Wg; float lambda; };
+struct BeamRules { const XgBeamRules* rules; const uint8_t* word_cat; const uint32_t* allow; float* key; };
+struct RulesWs : BeamWs { int32_t* hist[2]; float* done_key; };
+RulesWs rules_carve(const XgDims& d, int S, int W, void* base) {
+    RulesWs w{};
+    static_cast<BeamWs&>(w) = beam_carve(d, S, W, base);
+    const size_t M = (size_t)d.B * S * W, L = d.T - 1;
+    Carver c{static_cast<char*>(base), w.bytes};
+    w.hist[0] = c.take<int32_t>(M * L); w.hist[1] = c.take<int32_t>(M * L);
+    w.done_key = c.take<float>(M);
+    w.bytes = (c.off + 255) & ~(size_t)255;
+    return w;
+}
+bool rules_dims_ok(const XgDims* d, int S, int W, int suppress) { return S >= 1 && beam_dims_ok(d, S, W, suppress) && d->T - 1 <= XGBR_MAX_LENGTH; }
+
 int beam_search_impl(void* stream, const XgDims* d, int S, int W, int32_t suppress_token, const XgParams* p, const XgBnState* bn,
                      const XgBatch* x, const XgRun* run, int64_t* seq, float* seq_logp, float* score, int32_t* trace, void* ws,
-                     size_t ws_bytes, const BeamAllow* al = nullptr, const BeamDiverse* dv = nullptr) {
+                     size_t ws_bytes, const BeamAllow* al = nullptr, const BeamDiverse* dv = nullptr, const BeamRules* br = nullptr) {
     XG_TRY(search_args(beam_dims_ok(d, S, W, suppress_token), p, bn, x, run, seq, seq_logp, score, ws));
     if (al && (!al->word_cat || !al->allow)) return XG_EINVAL;
     // (W = Gd Wg is the entry point's; the merge launcher refuses a negative, infinite or NaN lambda, but only once work is enqueued)
     if (dv && (al || !(dv->lambda >= 0.0f) || dv->lambda == INFINITY)) return XG_EINVAL;
-    BeamWs w = beam_carve(*d, S, W, ws, dv ? dv->Gd : 1);
+    BeamWs w;
+    int32_t* hist[2] = {nullptr, nullptr};
+    bool bans = false;
+    BeamAllow al_br{};
+    if (br) {
+        const XgBeamRules* r = br->rules;
+        const int L = d->T - 1;
+        if (dv || al || S < 1 || L > XGBR_MAX_LENGTH || !r) return XG_EINVAL;
+        if (r->no_repeat_ngram < 0 || r->no_repeat_ngram > L || r->min_length < 0 || r->min_length > L) return XG_EINVAL;
+        if (r->n_bad_end < 0 || r->n_bad_end > XGBR_MAX_BAD_END || (r->n_bad_end > 0 && !r->bad_end)) return XG_EINVAL;
+        if (!br->word_cat != !br->allow) return XG_EINVAL;
+        RulesWs rw = rules_carve(*d, S, W, ws);
+        w = rw;
+        w.book.scale = r->length_scale;
+        w.book.done_key = rw.done_key;
+        hist[0] = rw.hist[0]; hist[1] = rw.hist[1];
+        bans = r->no_repeat_ngram >= 1 || r->min_length >= 1 || r->n_bad_end >= 1;
+        if (br->allow) { al_br = BeamAllow{br->word_cat, br->allow}; al = &al_br; }
+    } else {
+        w = beam_carve(*d, S, W, ws, dv ? dv->Gd : 1);
+    }
     if (ws_bytes < w.bytes) return XG_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const bool shared = S > 0;
@@ -2152,13 +2191,24 @@ int beam_search_impl(void* stream, const XgDims* d, int S, int W, int32_t suppre
         s.rows_per_video = shared ? S * W : 0;
         XG_TRY(core_step(st, dm, *p, *run, w.step, Venc, vproj, s));
         XG_TRY(xgk_linear(st, 0, M, V, R, s.h2o, R, p->logit_w, p->logit_b, w.step.LOGITS, V));
-        if (al) XG_TRY(xgk_cap_beam_topw_allow(st, w.step.LOGITS, V, M, V, W, suppress_token, al->word_cat, al->allow + t, L, w.topv, w.topi));
+        if (bans) {
+            const XgBeamRules* r = br->rules;
+            const CapBeamBan ban{hist[t & 1], L, t, r->no_repeat_ngram, r->min_length, r->bad_end, r->n_bad_end};
+            XG_TRY(xgk_cap_beam_topw_rules(st, w.step.LOGITS, V, M, V, W, suppress_token, al ? al->word_cat : nullptr,
+                                           al ? al->allow + t : nullptr, L, ban, w.topv, w.topi));
+        } else if (al) XG_TRY(xgk_cap_beam_topw_allow(st, w.step.LOGITS, V, M, V, W, suppress_token, al->word_cat, al->allow + t, L, w.topv, w.topi));
         else XG_TRY((shared ? xgk_cap_beam_topw_thr : xgk_cap_beam_topw)(st, w.step.LOGITS, V, M, V, W, suppress_token, w.topv, w.topi));
         ma.book.t = t;
+        if (bans) { ma.hsrc = hist[t & 1]; ma.hdst = hist[(t + 1) & 1]; }
         if (dv) XG_TRY(xgk_cap_beam_merge_diverse(st, G, ma, dv->Gd, dv->lambda));
         else XG_TRY(xgk_cap_beam_merge(st, G, ma));
     }
-    return xgk_cap_beam_backtrace(st, dv ? G * dv->Gd : G, w.book, seq, seq_logp, score);
+    XG_TRY(xgk_cap_beam_backtrace(st, dv ? G * dv->Gd : G, w.book, seq, seq_logp, score));
+    if (br && br->key) {                                  // (the done list's keys lie in its order; without a scale key == score)
+        const float* src = w.book.scale ? w.book.done_key : score;
+        if (hipMemcpyAsync(br->key, src, sizeof(float) * (size_t)M, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+    }
+    return XG_OK;
 }
 
 }  // namespace
@@ -2201,6 +2251,23 @@ extern "C" int xgba_beam_search(void* stream, const XgDims* d, int32_t S, int32_
     if (S < 1) return XG_EINVAL;
     const BeamAllow al{word_cat, allow};
     return beam_search_impl(stream, d, S, W, suppress_token, p, bn, x, run, seq, seq_logp, score, trace, ws, ws_bytes, &al);
+}
+
+// ---- that search, with or without the words held to a template, under decoding rules (include/xgate_beam_rules.h): no repeated
+// n-gram, a minimum length, no end behind a listed word, a length-scaled final ranking
+extern "C" int xgbr_version(void) { return XGBR_VERSION; }
+
+extern "C" size_t xgbr_workspace_bytes(const XgDims* d, int32_t S, int32_t W) {
+    return rules_dims_ok(d, S, W, -1) ? rules_carve(*d, S, W, nullptr).bytes : 0;
+}
+
+extern "C" int xgbr_beam_search(void* stream, const XgDims* d, int32_t S, int32_t W, int32_t suppress_token, const XgBeamRules* rules,
+                                const uint8_t* word_cat, const uint32_t* allow, const XgParams* p, const XgBnState* bn, const XgBatch* x,
+                                const XgRun* run, int64_t* seq, float* seq_logp, float* score, float* key, int32_t* trace, void* ws,
+                                size_t ws_bytes) {
+    if (S < 1) return XG_EINVAL;
+    const BeamRules br{rules, word_cat, allow, key};
+    return beam_search_impl(stream, d, S, W, suppress_token, p, bn, x, run, seq, seq_logp, score, trace, ws, ws_bytes, nullptr, nullptr, &br);
 }
 
 // ---- diverse beam search (include/xgate_beam_diverse.h): the rows-per-video search at W = Gd Wg slots per pair, merged group by group

@@ -124,6 +124,20 @@ def word_category_table(category, wtoi, V):
     return table
 
 
+# words a caption should not end on (articles, prepositions, copulas), the usual list of caption decoders of this family
+BAD_ENDINGS = ("a", "an", "the", "in", "for", "at", "of", "with", "before", "after", "on", "upon", "near", "to", "is", "are", "am")
+
+
+def bad_ending_ids(wtoi, words=BAD_ENDINGS):
+    """The indices of `words` in the vocabulary ``wtoi`` {word: index}, in the order of `words` and each once: the `bad_endings`
+    of ``SAModel.beam_captions_ruled`` (include/xgate_beam_rules.h: bad_end).  Words missing from the vocabulary are skipped."""
+    out = []
+    for wd in words:
+        if wd in wtoi and int(wtoi[wd]) not in out:
+            out.append(int(wtoi[wd]))
+    return out
+
+
 def vocab_size(worddict):
     """data_io.get_nwords (:122-123): the pickled dictionary starts at index 2; 0 = <EOS> / BOS / pad, 1 = unknown."""
     return len(worddict) + 2

@@ -732,6 +732,93 @@ class SAModel(FlatParams, nn.Module):
         out = (seq, seq_logp, score)
         return out + (trace,) if return_trace else out
 
+    def beam_captions_ruled(self, feats_rgb, feats_opfl, feat_mask, pos_feats, beam_size=5, suppress_token=1, no_repeat_ngram=0,
+                            min_length=0, bad_endings=None, length_scale=None, word_cat=None, allow=None, return_trace=False):
+        """``beam_captions_per_video`` -- with `word_cat` and `allow`, ``beam_captions_allowed`` -- under decoding rules
+        (include/xgate_beam_rules.h, docs/CAPTION_RULES.md).  `no_repeat_ngram` = n >= 1: the word that would complete an n-gram a
+        beam already holds is lowered by 1000 like the suppressed word, so no beam with a score above -500 holds an n-gram twice
+        (0: off).  `min_length`: the end token 0 is lowered likewise at steps t < min_length.  `bad_endings`: up to 32 words (a
+        sequence or tensor of indices, ``data.bad_ending_ids``) behind which the end token is lowered likewise.  `length_scale`
+        (L,) in (0, 1] (``control.length_scale_table``): a (video, template) pair's finished beams are ranked by key = score *
+        length_scale[step of the finish] instead of by score.  The log-sum-exp of a step is never changed by a ban: seq_logp stays
+        the model's log-probability.  Returns (seq (B,S,W,L) int64, seq_logp (B,S,W,L), score (B,S,W), key (B,S,W)[, trace
+        (B,S,L,W,2) int32]), a pair's beams in descending key; with every rule off seq, seq_logp, score and trace are those of the
+        search without rules bit for bit and key == score.  One enqueue, no host work per step.
+
+        Raises as ``beam_captions_per_video`` / ``beam_captions_allowed`` do, plus ValueError for n or `min_length` outside [0, L],
+        L above 512, `bad_endings` outside [0, V) or more than 32 of them, a `length_scale` that is not (L,), not finite or outside
+        (0, 1], and exactly one of `word_cat` / `allow` given.  `bad_endings` and `length_scale` are checked on the host: hand them
+        over as host data (a device tensor is read back).  Eval mode, fp32 and device tensors only."""
+        from . import _native_beam_rules as nbr
+        name = "beam_captions_ruled"
+        inputs, W, sup = (feats_rgb, feats_opfl, feat_mask, pos_feats), int(beam_size), int(suppress_token)
+        self._search_gate(name)
+        Ls, V = self.seq_length, self.vocab_size
+        n, mn = int(no_repeat_ngram), int(min_length)
+        # (the rules' own checks hold on any device: they come before the device gate of _search_open, behind the mode's)
+        if Ls > nbr.XGBR_MAX_LENGTH:
+            raise ValueError("seq_length <= %d expected, got %d" % (nbr.XGBR_MAX_LENGTH, Ls))
+        if not 0 <= n <= Ls:
+            raise ValueError("0 <= no_repeat_ngram <= seq_length = %d expected, got %d" % (Ls, n))
+        if not 0 <= mn <= Ls:
+            raise ValueError("0 <= min_length <= seq_length = %d expected, got %d" % (Ls, mn))
+        bad = None
+        if bad_endings is not None:
+            bad = torch.as_tensor(bad_endings).detach().cpu()
+            if bad.is_floating_point() or bad.is_complex() or bad.dtype == torch.bool or bad.dim() != 1:
+                raise ValueError("bad_endings: a flat sequence of word indices expected")
+            if bad.numel() > nbr.XGBR_MAX_BAD_END:
+                raise ValueError("at most %d bad_endings expected, got %d" % (nbr.XGBR_MAX_BAD_END, bad.numel()))
+            if bad.numel() and (int(bad.min()) < 0 or int(bad.max()) >= V):
+                raise ValueError("bad_endings must lie in [0, vocab_size = %d)" % V)
+            bad = bad.to(torch.int32).contiguous() if bad.numel() else None
+        scale = None
+        if length_scale is not None:
+            scale = torch.as_tensor(length_scale).detach().cpu()
+            if not scale.is_floating_point() or tuple(scale.shape) != (Ls,):
+                raise ValueError("length_scale (L = %d,) floats expected, got %s" % (Ls, tuple(scale.shape)))
+            scale = scale.to(torch.float32).contiguous()
+            if not bool(torch.isfinite(scale).all()) or not bool(((scale > 0) & (scale <= 1)).all()):
+                raise ValueError("every length_scale entry must be finite and lie in (0, 1]")
+        if (word_cat is None) != (allow is None):
+            raise ValueError("word_cat and allow come together: both or neither")
+        if word_cat is not None:
+            if not torch.is_tensor(word_cat) or word_cat.dtype != torch.uint8 or tuple(word_cat.shape) != (V,):
+                raise ValueError("word_cat (V = %d,) uint8 expected, got %s" % (
+                    V, (tuple(word_cat.shape), word_cat.dtype) if torch.is_tensor(word_cat) else type(word_cat)))
+            if not torch.is_tensor(allow) or allow.is_floating_point() or allow.is_complex() or allow.dtype == torch.bool:
+                raise ValueError("allow holds integer masks")
+            if pos_feats.dim() == 3 and tuple(allow.shape) != tuple(pos_feats.shape[:2]) + (Ls,):
+                raise ValueError("allow (B = %d, S = %d, L = %d) expected, got %s" % (pos_feats.shape[0], pos_feats.shape[1], Ls,
+                                                                                      tuple(allow.shape)))
+        B, K, S, L, dev, d = self._search_open(name, inputs, True, beam=(W, sup))
+        a = wc = None
+        if word_cat is not None:
+            self._search_gate(name, word_cat, allow)
+            with torch.no_grad():                    # the uint32 bit patterns in int32 storage
+                a = allow.detach().long() & 0xFFFFFFFF
+                a = torch.where(a >= 1 << 31, a - (1 << 32), a).to(torch.int32).contiguous()
+                wc = word_cat.detach().contiguous()
+        # the two small tables on the device, kept from the last call with the same values (no copy per call)
+        tkey = (None if bad is None else tuple(bad.tolist()), None if scale is None else scale.numpy().tobytes(), str(dev))
+        if getattr(self, "_beam_rules_tables", (None,))[0] != tkey:
+            self._beam_rules_tables = (tkey, None if bad is None else bad.to(dev), None if scale is None else scale.to(dev))
+        _, bad, scale = self._beam_rules_tables
+        rules = nbr.XgBeamRules(n, mn, nv.ptr(bad), 0 if bad is None else bad.numel(), nv.ptr(scale))
+        lib = nbr.lib()
+        args, wp, wn, keep = self._search_call("_beam_rules_ws", (B, K, L, S, W, str(dev)),
+                                               lambda: lib.xgbr_workspace_bytes(C.byref(d), S, W),
+                                               "xgbr_workspace_bytes: invalid dims or too many rows (B %d, S %d, W %d)" % (B, S, W), inputs)
+        seq = torch.empty(B, S, W, L, dtype=torch.int64, device=dev)
+        seq_logp = torch.empty(B, S, W, L, dtype=torch.float32, device=dev)
+        score = torch.empty(B, S, W, dtype=torch.float32, device=dev)
+        key = torch.empty(B, S, W, dtype=torch.float32, device=dev)
+        trace = torch.empty(B, S, L, W, 2, dtype=torch.int32, device=dev) if return_trace else None
+        nv.check(lib.xgbr_beam_search(_stream(), C.byref(d), S, W, sup, C.byref(rules), nv.ptr(wc), nv.ptr(a), *args, nv.ptr(seq),
+                                      nv.ptr(seq_logp), nv.ptr(score), nv.ptr(key), nv.ptr(trace), wp, wn), "xgbr_beam_search")
+        out = (seq, seq_logp, score, key)
+        return out + (trace,) if return_trace else out
+
     def beam_captions_diverse(self, feats_rgb, feats_opfl, feat_mask, pos_feats, groups, group_size, diversity=0.5, suppress_token=1,
                               return_trace=False):
         """Diverse beam search (include/xgate_beam_diverse.h) for S `pos_feats` rows per video on ONE encoder pass: per (video,
