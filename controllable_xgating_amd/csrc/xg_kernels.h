@@ -324,6 +324,20 @@ int xgk_attn_post_dV(hipStream_t st, const float* P, const float* vproj, const f
                      const float* ALPHA, const float* DAF, int lddaf, int64_t daf_tstride, float* dV, int T, int B, int K, int A, int R);
 int xgk_attn_dV(hipStream_t st, const float* ALPHA /*(T,B,K)*/, const float* DAF /*(T,B,ldaf)*/, int lddaf,
                 int64_t daf_tstride, float* dV, int T, int B, int K, int R, bool accumulate);
+// ---- the attention backward with Q rows per video (xg_train_video.hip; include/xgate_train_video.h): daf, p, alpha, de, dp per row,
+// row b Q + q; vproj (B,K,A) and V (B,K,R) per VIDEO
+constexpr int XGK_ATTN_BWD_GROUP = 4;            // rows of one video per workgroup of the fast form
+int xgk_attn_bwd_group(hipStream_t st, const float* daf, int lddaf, const float* p, const float* vproj, const float* V, const float* w,
+                       const float* alpha, float* de, float* dp, int B, int Q, int K, int R, int A);
+int xgk_attn_bwd_group_form(const float* daf, int lddaf, const float* p, const float* vproj, const float* V, const float* w,
+                            const float* dp, int K, int R, int A);      // 1: the group form takes these operands, 0: the rows form
+// after the time loop, over the M = B Q rows: dvproj[b][k][a] = w_a sum_t sum_q de (1 - th^2), dw[a] += sum de th (dw null: skipped),
+// dV[b][k][r] = sum_t sum_q alpha daf -- plain stores, one writer per element, the Q T terms in (t, q) order
+int xgk_attn_post_dV_group(hipStream_t st, const float* P /*(T,M,A)*/, const float* vproj, const float* w, const float* DE /*(T,M,K)*/,
+                           float* dvproj, float* dw, const float* ALPHA /*(T,M,K)*/, const float* DAF, int lddaf, int64_t daf_tstride,
+                           float* dV, int T, int B, int Q, int K, int A, int R);
+// out[b][r] = sum_q in[b Q + q][r], in q order
+int xgk_rows_sum_group(hipStream_t st, const float* in, float* out, int B, int Q, int R);
 
 // ---- xg_heads.hip
 // out[orow(i)] = log_softmax(in[i]) ; orow = (i % inner) * outer + i / inner when permute (time-major -> batch-major)

@@ -21,6 +21,7 @@
 #include "../../include/xgate_beam_rules.h"
 #include "../../include/xgate_beam_diverse.h"
 #include "../../include/xgate_pair.h"
+#include "../../include/xgate_train_video.h"
 
 #include <new>
 #include <cstdlib>
@@ -878,13 +879,16 @@ int decoder_tokens_xe(hipStream_t sx, const XgDims& d, const XgParams& p, const 
 // already under way there.
 // early_loss (fused loss path): the cross-entropy rows of those steps follow their logits on the auxiliary stream, under
 // the remaining steps (w.sums must have been zeroed on the main stream before).
+// rows_per_video > 0 (include/xgate_train_video.h): d.B counts ROWS, V and v2a(V) hold one block per VIDEO in `enc`, and the caller
+// has left the initial state in block 0 of w.H1 / C1 / H2 / C2 (videos_once).
 int decoder_fwd_xe(Streams& ss, const XgDims& d, const XgParams& p, const XgBatch& x, const XgRun& run, Ws& w,
-                   int* logit_rows_done, bool early_loss = false) {
+                   int* logit_rows_done, bool early_loss = false, int rows_per_video = 0, const Ws* enc = nullptr) {
     hipStream_t st = ss.main;
     const int B = d.B, R = d.R, T = d.T;
     const size_t BR = (size_t)B * R;
-    if (!step_scratch_ok(w, false, false)) return XG_EINVAL;
-    XG_TRY(init_and_vproj(ss, d, p, x.feat_mask, w));
+    if (!step_scratch_ok(w, false, rows_per_video > 0) || (rows_per_video > 0) != (enc != nullptr)) return XG_EINVAL;
+    const Ws& vw = enc ? *enc : w;                // where V and v2a(V) live
+    if (!enc) XG_TRY(init_and_vproj(ss, d, p, x.feat_mask, w));
     XG_TRY(zero_dsync(st, w));
     XG_TRY(ss.join());                                                                              // token-side products
     const int th = (ss.overlap() && T >= 4) ? T / 2 : 0;          // the early product starts behind step T / 2 (split points swept in rounds 3-5: flat)
@@ -910,7 +914,8 @@ int decoder_fwd_xe(Streams& ss, const XgDims& d, const XgParams& p, const XgBatc
     for (int t = 0; t < T; ++t) {
         StepIO s = step_io_at(w, d, t);
         s.pre1 = w.PRE1 + (size_t)t * B * 4 * R; s.mask = x.seq_mask + t; s.ldm = T; s.half_attn = fwd_bg;
-        XG_TRY(core_step(st, d, p, run, w, w.Venc, w.vproj, s));
+        s.rows_per_video = rows_per_video;
+        XG_TRY(core_step(st, d, p, run, w, vw.Venc, vw.vproj, s));
         const int n = t + 1;                                           // steps finished
         bool cut;
         if (!chunked) cut = th > 0 && n == th;
@@ -957,9 +962,14 @@ int heads_fwd_logits(Streams& ss, const XgDims& d, const XgParams& p, const XgRu
 // mask: element (b,t) at mask[b*ldm + t*tstride].  tokens likewise for the embedding scatter.
 int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgParams& g, const XgBatch& x,
                      const XgRun& run, Ws& w, const float* mask, int ldm, int mask_tstride, const int64_t* tok,
-                     int tok_bstride, int tok_tstride) {
+                     int tok_bstride, int tok_tstride, int rows_per_video = 0, Ws* enc = nullptr) {
     hipStream_t st = ss.main;
-    const int B = d.B, K = d.K, R = d.R, A = d.A, E = d.E, T = d.T, TB = T * B, N = B * K;
+    // rows_per_video = Q > 0 (include/xgate_train_video.h): d.B counts ROWS, row b Q + q; what belongs to a VIDEO -- V, v2a(V), vbar
+    // and their gradients -- lives in `enc`, one block per video, and the three places below that touch it take their group forms
+    if ((rows_per_video > 0) != (enc != nullptr) || (rows_per_video > 0 && d.B % rows_per_video != 0)) return XG_EINVAL;
+    Ws& vw = enc ? *enc : w;
+    const int B = d.B, K = d.K, R = d.R, A = d.A, E = d.E, T = d.T, TB = T * B;
+    const int Bv = rows_per_video > 0 ? B / rows_per_video : B, N = Bv * K;      // videos; their frames
     const size_t BR = (size_t)B * R;
     // The reverse-time recurrence splits into two chains.  Chain 2 (cell 2 + attention: dh2, dc2) never reads anything
     // chain 1 (cell 1: dh1, dc1) produces, and only chain 2's products (dAF, dE) feed the encoder backward: it runs on
@@ -1098,8 +1108,12 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
             allow_split(sk, 0, w); allow_split(sk, 1, w);
             XG_TRY(xgk_skinny(st, sk, sk_mode(w)));
         }
-        XG_TRY(xgk_attn_bwd(st, daf, R, w.P + (size_t)t * B * A, w.vproj, w.Venc, p.a2w_w, w.ALPHA + (size_t)t * B * K,
-                            w.DE + (size_t)t * B * K, dp, B, K, R, A));
+        if (rows_per_video > 0)
+            XG_TRY(xgk_attn_bwd_group(st, daf, R, w.P + (size_t)t * B * A, vw.vproj, vw.Venc, p.a2w_w, w.ALPHA + (size_t)t * B * K,
+                                      w.DE + (size_t)t * B * K, dp, Bv, rows_per_video, K, R, A));
+        else
+            XG_TRY(xgk_attn_bwd(st, daf, R, w.P + (size_t)t * B * A, w.vproj, w.Venc, p.a2w_w, w.ALPHA + (size_t)t * B * K,
+                                w.DE + (size_t)t * B * K, dp, B, K, R, A));
         {   // into step t-1: dh2 += dp Wh2a[:, R:]  (+ cell 2's backward at t-1 on the completed dh2)
             SkArgs sk{};
             sk.njobs = 1;
@@ -1137,9 +1151,13 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
     // ---- after the loop.  Main chain (the encoder backward waits for it): dVproj -> dV.  Everything else is a
     // parameter gradient and goes to the auxiliary stream, under the encoder's recurrent backward.
     // (dV first, as a plain store: accumulating on top of the product below it would read every element back)
-    XG_TRY(xgk_attn_post_dV(st, w.P, w.vproj, p.a2w_w, w.DE, w.DVPROJ, g.a2w_w, w.ALPHA, w.DAF, R, (int64_t)BR, w.DV, T, B, K, A, R));
-    XG_TRY(cvt16(st, w, w.DVPROJ, (size_t)N * A));
-    XG_TRY(nn16(st, w.gm, N, R, A, w.DVPROJ, m16(w, w.DVPROJ), A, p.v2a_w, w16(w, W16_V2A), R, w.DV, R, true));
+    if (rows_per_video > 0)
+        XG_TRY(xgk_attn_post_dV_group(st, w.P, vw.vproj, p.a2w_w, w.DE, vw.DVPROJ, g.a2w_w, w.ALPHA, w.DAF, R, (int64_t)BR, vw.DV, T, Bv,
+                                      rows_per_video, K, A, R));
+    else
+        XG_TRY(xgk_attn_post_dV(st, w.P, w.vproj, p.a2w_w, w.DE, w.DVPROJ, g.a2w_w, w.ALPHA, w.DAF, R, (int64_t)BR, w.DV, T, B, K, A, R));
+    XG_TRY(cvt16(st, vw, vw.DVPROJ, (size_t)N * A));
+    XG_TRY(nn16(st, w.gm, N, R, A, vw.DVPROJ, m16(vw, vw.DVPROJ), A, p.v2a_w, w16(w, W16_V2A), R, vw.DV, R, true));
     // gradients wrt the initial state -> img_embed_* (init_hidden; vbar is detached: SAModel.py:59-62)
     {
         float* gst[4] = {w.dst[cur1][0], w.dst[cur1][1], w.dst[cur][2], w.dst[cur][3]};
@@ -1147,7 +1165,11 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
         float* gb[4] = {g.ih1_b, g.ic1_b, g.ih2_b, g.ic2_b};
         for (int j = 0; j < 4; ++j) {
             hipStream_t sj = j < 2 ? s1 : sx;     // h1 / c1 come out of chain 1
-            XG_TRY(gemm_tn_cs(sj, w.gm, B, R, R, gst[j], R, w.vbar, R, gw[j], R, gb[j]));
+            if (rows_per_video > 0) {             // the Q rows of a video share its initial state: their gradients add, in row order
+                XG_TRY(xgk_rows_sum_group(sj, gst[j], vw.dst[1][j], Bv, rows_per_video, R));
+                gst[j] = vw.dst[1][j];
+            }
+            XG_TRY(gemm_tn_cs(sj, w.gm, Bv, R, R, gst[j], R, vw.vbar, R, gw[j], R, gb[j]));
         }
     }
     // batched weight gradients over the steps the loop has not handed out yet
@@ -1165,10 +1187,10 @@ int decoder_bwd_core(Streams& ss, const XgDims& d, const XgParams& p, const XgPa
         // v2a.bias: the column sums of dVproj cancel almost completely (every video's softmax gradients sum to zero across its
         // frames), so what is left of a sum over bf16-ROUNDED elements is mostly rounding (cosine 0.91 against the fp32 oracle at
         // the full configs[4] size): this one bias gradient keeps its own pass over the fp32 values
-        XG_TRY(tn16(sx, w.gm, N, A, R, w.DVPROJ, m16(w, w.DVPROJ), A, w.Venc, m16(w, w.Venc), R, g.v2a_w, R));
-        XG_TRY(xgk_colsum3(sx, w.DVPROJ, A, N, A, g.v2a_b, nullptr, nullptr));
+        XG_TRY(tn16(sx, w.gm, N, A, R, vw.DVPROJ, m16(vw, vw.DVPROJ), A, vw.Venc, m16(vw, vw.Venc), R, g.v2a_w, R));
+        XG_TRY(xgk_colsum3(sx, vw.DVPROJ, A, N, A, g.v2a_b, nullptr, nullptr));
     } else {
-        XG_TRY(tn16(sx, w.gm, N, A, R, w.DVPROJ, m16(w, w.DVPROJ), A, w.Venc, m16(w, w.Venc), R, g.v2a_w, R, g.v2a_b));
+        XG_TRY(tn16(sx, w.gm, N, A, R, vw.DVPROJ, m16(vw, vw.DVPROJ), A, vw.Venc, m16(vw, vw.Venc), R, g.v2a_w, R, g.v2a_b));
     }
     XG_TRY(ss.chain2_into_aux());             // aux now also covers the second side chain
     // everything but two_spatial_encoder.* is final once the auxiliary stream gets here (it has waited for main above)
@@ -2464,4 +2486,143 @@ extern "C" int xg_rollout_bwd(void* stream, const XgDims* d, const XgParams* p, 
     XgDims dT = *d;
     dT.T = T - 1;
     return backward_tail(ss, *d, dT, *p, *g, *x, *run, w, false, nullptr, w.UNF, 1, B, w.TOK, 1, B);
+}
+
+// ---- teacher-forced training on Q captions per video (include/xgate_train_video.h): the fused loss of xg_xe_loss_fwd / _bwd over
+// M = B Q rows with the videos once.  The workspace is the per-video part (`enc`: a whole workspace of the B videos at T = 1, as the
+// searches have it: encoder, v2a(V), vbar and the gradients that belong to a video) followed by the row part (`row`): everything
+// carve() gives the decoder, the heads and the reverse-time pass at d.B = M, and nothing of the encoder.  Of the row part only ALPHA
+// and DE are (rows, K) blocks.  The forward is videos_once, the hoisted token side, T core_steps in their rows-per-video form and
+// the heads on M rows; the backward is heads_bwd and decoder_bwd_core on M rows (rows_per_video = Q), then encoder_bwd on the videos.
+namespace {
+
+struct TrainVideoWs { Ws enc, row; size_t bytes; };
+
+TrainVideoWs tv_carve(const XgDims& d, int Q, void* base) {
+    TrainVideoWs w{};
+    w.enc = carve(beam_dims(d, d.B), base);
+    w.enc.sh16 = nullptr; w.enc.bytes = w.enc.core_bytes;          // fp32 only: no bf16 mirror region
+    Carver c{static_cast<char*>(base), w.enc.core_bytes};
+    const size_t M = (size_t)d.B * Q, K = d.K, R = d.R, A = d.A, E = d.E, V = d.V, C = d.C, H = d.H, T = d.T, TM = T * M;
+    Ws& s = w.row;
+    carve_step_scratch(c, s, M, R, false);
+    s.Xe = c.take<float>(TM * E); s.GP = c.take<float>(TM * R); s.POSG = c.take<float>(TM * R); s.PRE1 = c.take<float>(TM * 4 * R);
+    s.H1 = c.take<float>((T + 1) * M * R); s.C1 = c.take<float>((T + 1) * M * R);
+    s.H2 = c.take<float>((T + 1) * M * R); s.C2 = c.take<float>((T + 1) * M * R);
+    s.G1 = c.take<float>(TM * 4 * R); s.G2 = c.take<float>(TM * 4 * R);
+    s.P = c.take<float>(TM * A); s.ALPHA = c.take<float>(TM * K); s.AF = c.take<float>(TM * R);
+    s.LOGITS = c.take<float>(TM * V); s.HC = c.take<float>(TM * H); s.CL = c.take<float>(TM * C);
+    s.LSE = c.take<float>(TM); s.LSEC = c.take<float>(TM); s.sums = c.take<float>(8);
+    s.DH2OUT = c.take<float>(TM * R); s.DHC = c.take<float>(TM * H); s.DCL = c.take<float>(TM * C);
+    s.DS1 = c.take<float>(TM * 4 * R); s.DS2 = c.take<float>(TM * 4 * R); s.DP = c.take<float>(TM * A); s.DE = c.take<float>(TM * K);
+    for (int j = 0; j < 4; ++j) s.dst[1][j] = c.take<float>(M * R);
+    s.DPOSG = c.take<float>(TM * R); s.DH1X = c.take<float>(TM * R); s.DGP = c.take<float>(TM * R); s.DXe = c.take<float>(TM * E);
+    {   // the zero block of the reverse-time pass (zero_backward_block)
+        c.off = (c.off + 255) & ~(size_t)255;
+        const size_t z0 = c.off;
+        s.zblock = c.base ? c.base + z0 : nullptr;
+        s.DAF = c.take<float>(TM * R);
+        for (int j = 0; j < 4; ++j) s.dst[0][j] = c.take<float>(M * R);
+        s.tickets = c.take<int32_t>((size_t)SK_MAX_JOBS * SKPART_INTS);
+        s.zbytes = c.off - z0;
+    }
+    w.bytes = (c.off + 255) & ~(size_t)255;
+    s.bytes = s.core_bytes = w.bytes;
+    s.base_f = reinterpret_cast<const float*>(c.base);
+    s.end_f = c.base ? reinterpret_cast<const float*>(c.base + w.bytes) : nullptr;
+    s.sh16 = nullptr;
+    return w;
+}
+
+// The gates of the three entry points, in the order of include/xgate_train_video.h; on XG_OK `w` is carved and knows the call's
+// packed weights, de / dm are the dims of the videos and of the rows.
+int tv_open(const XgDims* d, int Q, const XgParams* p, const XgRun* run, void* ws, size_t ws_bytes, TrainVideoWs* w, XgDims* de,
+            XgDims* dm) {
+    if (!cc_dims_ok(d, Q) || !ws) return XG_EINVAL;
+    *w = tv_carve(*d, Q, ws);
+    if (ws_bytes < w->bytes) return XG_EWORKSPACE;
+    if ((uintptr_t)ws % 256 != 0 || !p) return XG_EINVAL;
+    *de = beam_dims(*d, d->B);
+    *dm = *d; dm->B = d->B * Q;
+    if (run) {
+        if (run->gemm_mode != 0) return XG_EINVAL;
+        attach_packed(w->enc, *de, run);
+        attach_packed(w->row, *dm, run);
+    }
+    return XG_OK;
+}
+bool tv_batch_ok(const XgBatch* x) {
+    return x && x->feats_rgb && x->feats_opfl && x->feat_mask && x->pos_feats && x->seq && x->seq_mask;
+}
+
+}  // namespace
+
+extern "C" int xgtv_version(void) { return XGTV_VERSION; }
+
+extern "C" size_t xgtv_workspace_bytes(const XgDims* d, int32_t Q) {
+    return cc_dims_ok(d, Q) ? tv_carve(*d, Q, nullptr).bytes : 0;
+}
+
+extern "C" int xgtv_xe_loss_fwd(void* stream, const XgDims* d, int32_t Q, const XgParams* p, const XgBnState* bn, const XgBatch* x,
+                                const int64_t* cap_classes, const float* class_mask, float weight_class, const XgRun* run, void* ws,
+                                size_t ws_bytes, float* losses) {
+    TrainVideoWs w; XgDims de, dm;
+    XG_TRY(tv_open(d, Q, p, run, ws, ws_bytes, &w, &de, &dm));
+    if (!run || !tv_batch_ok(x) || !losses) return XG_EINVAL;
+    if (!run->train && (!bn || !bn->rgb_mean || !bn->rgb_var || !bn->opfl_mean || !bn->opfl_var)) return XG_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int M = dm.B, T = d->T;
+    Ws& r = w.row;
+    Streams ss(st, run);
+    int rows_done = 0;
+    ZERO(st, r.sums, 2);                       // both halves of the cross-entropy add into it
+    const bool cls = cap_classes != nullptr;   // (without class targets nobody reads the classifier head: xg_xe_loss_fwd)
+    XG_TRY(ss.fork());
+    XG_TRY(decoder_tokens_xe(ss.aux, dm, *p, *x, *run, r));
+    float* const state0[4] = {r.H1, r.C1, r.H2, r.C2};
+    XG_TRY(videos_once(ss, de, *p, bn, *x, *run, w.enc, CapBeamRepeatArgs{}, state0, Q));
+    XG_TRY(decoder_fwd_xe(ss, dm, *p, *x, *run, r, &rows_done, true, Q, &w.enc));
+    XG_TRY(heads_fwd_logits(ss, dm, *p, *run, r, T * M, rows_done, cls));
+    XG_TRY(xgk_xent_fwd(st, r.LOGITS, d->V, x->seq, x->seq_mask, nullptr, M, T, d->V, 1, r.LSE, r.sums, rows_done, -1, false));
+    if (cap_classes) {
+        XG_TRY(xgk_xent_fwd(st, r.CL, d->C, cap_classes, x->seq_mask, class_mask, M, T, d->C, 0, r.LSEC, r.sums + 2));
+    } else {
+        ZERO(st, r.sums + 2, 2);
+    }
+    hipLaunchKernelGGL(losses_kernel, dim3(1), dim3(1), 0, st, r.sums, cap_classes ? weight_class : 0.f, losses);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+
+extern "C" int xgtv_xe_loss_bwd(void* stream, const XgDims* d, int32_t Q, const XgParams* p, const XgParams* g, const XgBatch* x,
+                                const int64_t* cap_classes, const float* class_mask, float weight_class, const float* dloss_dev,
+                                const XgRun* run, void* ws, size_t ws_bytes) {
+    TrainVideoWs w; XgDims de, dm;
+    XG_TRY(tv_open(d, Q, p, run, ws, ws_bytes, &w, &de, &dm));
+    if (!run || !g || !tv_batch_ok(x) || !dloss_dev) return XG_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int M = dm.B, T = d->T;
+    Ws& r = w.row;
+    const XentBwd xent{x->seq, x->seq_mask, dloss_dev};
+    const bool cls = cap_classes != nullptr && weight_class != 0.f;
+    if (cls) {
+        COPY(st, r.DCL, r.CL, (size_t)T * M * d->C);
+        XG_TRY(xgk_xent_bwd(st, r.DCL, d->C, cap_classes, x->seq_mask, class_mask, M, T, d->C, 0, r.LSEC, r.sums + 2, dloss_dev,
+                            weight_class));
+    }
+    Streams ss(st, run);
+    XG_TRY(heads_bwd(ss, dm, *p, *g, *run, r, T * M, cls, &xent));
+    XG_TRY(decoder_bwd_core(ss, dm, *p, *g, *x, *run, r, x->seq_mask, T, 1, x->seq, T, 1, Q, &w.enc));
+    XG_TRY(encoder_bwd(ss, de, *p, *g, *x, *run, w.enc, w.enc.DV));
+    return ss.join();
+}
+
+extern "C" int xgtv_video_grads(void* stream, const XgDims* d, int32_t Q, const XgParams* p, void* ws, size_t ws_bytes, float* dvproj,
+                                float* dV) {
+    TrainVideoWs w; XgDims de, dm;
+    XG_TRY(tv_open(d, Q, p, nullptr, ws, ws_bytes, &w, &de, &dm));
+    if (!dvproj || !dV) return XG_EINVAL;
+    const Ws& r = w.row;
+    return xgk_attn_post_dV_group((hipStream_t)stream, r.P, w.enc.vproj, p->a2w_w, r.DE, dvproj, nullptr, r.ALPHA, r.DAF, d->R,
+                                  (int64_t)dm.B * d->R, dV, d->T, d->B, Q, d->K, d->A, d->R);
 }

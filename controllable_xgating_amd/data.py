@@ -58,6 +58,43 @@ def collate(items):
     return caps, caps_mask, cap_classes, class_masks, feats1, feats2, feat_mask, pos_feat
 
 
+def collate_per_video(items, Q):
+    """``collate`` for Q caption items per video (SAModel.xe_loss_per_video): `items` holds B * Q dicts as ``collate`` takes them,
+    the Q captions of one video next to each other (items b Q .. b Q + Q - 1; their feat1 / feat2 / feat_mask are the video's and
+    are taken from the first).  Nothing is sorted: a video's rows stay together.  Returns the eight tensors in ``collate``'s
+    order with the caption fields per (video, caption) -- caps (B,Q,L+1) int64 with column 0 = BOS = 0, caps_mask, cap_classes,
+    class_masks (B,Q,L+1), pos_feat (B,Q,R) -- and the video's features ONCE: feats1 (B,K,F1), feats2 (B,K,F2), feat_mask (B,K).
+    L is the longest caption of the batch."""
+    if Q < 1 or len(items) == 0 or len(items) % Q != 0:
+        raise ValueError("%d items are no whole number of videos with Q = %d captions each" % (len(items), Q))
+    B = len(items) // Q
+    for b in range(B):
+        ids = {it["id"] for it in items[b * Q:(b + 1) * Q] if "id" in it}
+        if len(ids) > 1:
+            raise ValueError("items %d .. %d belong to different videos: %s" % (b * Q, (b + 1) * Q - 1, sorted(ids)))
+    max_len = max(len(it["cap"]) for it in items)
+    caps = torch.zeros(B * Q, max_len + 1, dtype=torch.int64)
+    caps_mask = torch.zeros(B * Q, max_len + 1)
+    cap_classes = torch.zeros(B * Q, max_len + 1, dtype=torch.int64)
+    class_masks = torch.zeros(B * Q, max_len + 1)
+    for i, it in enumerate(items):                       # the row fields as collate fills them
+        n = len(it["cap"])
+        caps[i, 1:n + 1] = torch.as_tensor(it["cap"], dtype=torch.int64)
+        caps_mask[i, :n + 1] = 1
+        nc = len(it["cap_class"])
+        cap_classes[i, :nc] = torch.as_tensor(it["cap_class"], dtype=torch.int64)
+        ncm = len(it["class_mask"])
+        class_masks[i, :ncm] = torch.as_tensor(it["class_mask"], dtype=torch.float32)
+        class_masks[i, ncm] = 1
+    first = items[::Q]
+    feats1 = torch.stack([it["feat1"] for it in first], 0)
+    feats2 = torch.stack([it["feat2"] for it in first], 0)
+    feat_mask = torch.cat([it["feat_mask"] for it in first], 0)
+    pos_feat = torch.stack([it["pos_feat"] for it in items], 0).reshape(B, Q, -1)
+    per = lambda t: t.reshape(B, Q, max_len + 1)          # noqa: E731
+    return per(caps), per(caps_mask), per(cap_classes), per(class_masks), feats1, feats2, feat_mask, pos_feat
+
+
 # ---------------------------------------------------------------------------------------------------- on-disk side
 def load_pkl(path):
     """data_io.py:19-25."""

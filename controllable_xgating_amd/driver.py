@@ -212,13 +212,19 @@ class Trainer:
         self.sc_flag = sc_flag_for_epoch(self.opt, epoch)
 
     def train_batch(self, b):
-        """starttrain.py:123-137.  b: dict with feat1, feat2, feat_mask, pos_feat, cap, cap_mask, cap_classes, class_mask."""
+        """starttrain.py:123-137.  b: dict with feat1, feat2, feat_mask, pos_feat, cap, cap_mask, cap_classes, class_mask.
+        A three-dimensional b["cap"] (B,Q,T) is a batch of Q captions per video (data.collate_per_video)."""
         model, opt = self.model, self.opt
         self.optimizer.zero_grad()                                                           # :123
         info = {}
         if not self.sc_flag:
             wc = getattr(opt, "weight_class", 0.0)
-            if self.fused:
+            if b["cap"].dim() == 3:
+                # Q captions per video (data.collate_per_video): cap (B,Q,T), the video's features once -- the fused loss in its
+                # per-video form; the optimizer arming and the gradient event below are the same
+                loss = model.xe_loss_per_video(b["feat1"], b["feat2"], b["feat_mask"], b["pos_feat"], b["cap"], b["cap_mask"],
+                                               b.get("cap_classes"), b.get("class_mask"), wc)
+            elif self.fused:
                 loss = model.xe_loss(b["feat1"], b["feat2"], b["feat_mask"], b["pos_feat"], b["cap"], b["cap_mask"],
                                      b.get("cap_classes"), b.get("class_mask"), wc)
             else:

@@ -371,6 +371,66 @@ class SAModel(FlatParams, nn.Module):
         return _XELossFunction.apply(self, save, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes,
                                      class_mask, float(weight_class), *params)
 
+    def xe_loss_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes=None,
+                          class_mask=None, weight_class=0.0):
+        """``xe_loss`` for Q captions per video on ONE encoder pass (include/xgate_train_video.h): the B videos are handed over
+        once -- feats_rgb (B,K,F1), feats_opfl (B,K,F2), feat_mask (B,K) -- with pos_feats (B,Q,R), seq (B,Q,T) int64, seq_mask
+        (B,Q,T) and, optionally, cap_classes (B,Q,T) and class_mask (B,Q,T) per caption; row b Q + q is caption q of video b.
+        Returns the scalar loss over the B Q rows with a graph; ``backward()`` fills every parameter gradient and ``last_losses``
+        holds (total, language, classifier) as after ``xe_loss``.
+
+        The encoder, init_hidden and v2a(V) run once per video, forward and backward, and every attention step reads a video's V
+        and v2a(V) once per group of its rows.  At drop_prob_lm = 0 the loss and the gradients are those of ``xe_loss`` on the
+        batch with every video repeated Q times (up to summation order); the BatchNorm running statistics receive the update of
+        the B videos.  Under dropout the encoder's masks are those of a B-video call, the decoder's those of a B Q-row call.
+
+        fp32, device tensors, no scheduled sampling (ss_prob = 0); train and eval mode."""
+        from . import _native_train_video  # noqa: F401  (the binding is declared when the call is made)
+        if self.precision != "fp32":
+            raise NotImplementedError("xe_loss_per_video is fp32 only (precision = %r)" % (self.precision,))
+        if self.training and self.ss_prob > 0.0:
+            raise NotImplementedError("xe_loss_per_video has no scheduled sampling: ss_prob must be 0")
+        for name, t, nd in (("feats_rgb", feats_rgb, 3), ("feats_opfl", feats_opfl, 3), ("feat_mask", feat_mask, 2),
+                            ("pos_feats", pos_feats, 3), ("seq", seq, 3), ("seq_mask", seq_mask, 3)):
+            if not torch.is_tensor(t) or t.dim() != nd:
+                raise ValueError("%s: a %d-dimensional tensor expected" % (name, nd))
+        B, K = feats_rgb.shape[:2]
+        Q, T = int(seq.shape[1]), int(seq.shape[2])
+        if B < 1 or K < 1 or Q < 1 or T < 2:
+            raise ValueError("B, K, Q >= 1 and T >= 2 expected, got B %d, K %d, Q %d, T %d" % (B, K, Q, T))
+        want = (("feats_rgb", feats_rgb, (B, K, self.feat_size)), ("feats_opfl", feats_opfl, (B, K, self.feat_size2)),
+                ("feat_mask", feat_mask, (B, K)), ("pos_feats", pos_feats, (B, Q, self.rnn_size)), ("seq", seq, (B, Q, T)),
+                ("seq_mask", seq_mask, (B, Q, T)), ("cap_classes", cap_classes, (B, Q, T)), ("class_mask", class_mask, (B, Q, T)))
+        for name, t, shape in want:
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shape):
+                raise ValueError("%s %s expected, got %s" % (name, shape, tuple(t.shape) if torch.is_tensor(t) else type(t)))
+        if seq.is_floating_point() or (cap_classes is not None and cap_classes.is_floating_point()):
+            raise ValueError("seq and cap_classes are integer tensors")
+        for t in (feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes, class_mask):
+            if t is not None and not t.is_cuda:
+                raise NotImplementedError("xe_loss_per_video needs device tensors: there is no CPU path")
+        params = self._param_list()
+        save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        return _XELossVideoFunction.apply(self, save, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes,
+                                          class_mask, float(weight_class), *params)
+
+    def _video_workspace(self, d, Q, dev, save):
+        """(key, tensor) of a workspace of xe_loss_per_video (xgtv_workspace_bytes): the forward's own until its backward has run
+        when it saves activations, else one shared scratch per shape; not zero-filled (the calls do not read what it held)."""
+        from . import _native_train_video as ntv
+        key = (tuple(getattr(d, f[0]) for f in d._fields_), Q, str(dev))
+        pool = self.__dict__.setdefault("_video_pool", {})
+        lst = pool.setdefault((key, save), [])
+        if lst:
+            return key, (lst.pop() if save else lst[0])
+        n = ntv.lib().xgtv_workspace_bytes(C.byref(d), Q)
+        if n == 0:
+            raise nv.XgError("xgtv_workspace_bytes: invalid dims or too many rows (B %d, Q %d)" % (d.B, Q))
+        ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+        if not save:
+            lst.append(ws)
+        return key, ws
+
     def sample_pair(self, feats_rgb, feats_opfl, feat_mask, pos_feats, opt={}):
         """The two rollouts of one SCST iteration in ONE batched pass: ``sample(..., {'sample_max': 0})``
         (starttrain.py:131) and the greedy baseline ``sample(..., {'sample_max': 1})`` (myutils.py:45-48).
@@ -1024,6 +1084,59 @@ class _XELossFunction(torch.autograd.Function):
         nv.check(nv.lib().xg_xe_loss_bwd(_stream(), C.byref(d), C.byref(ps), C.byref(gs), C.byref(b), nv.ptr(ctx.cc),
                                          nv.ptr(ctx.cm), ctx.wc, nv.ptr(dl), C.byref(run), wp, wn), "xg_xe_loss_bwd")
         return _close_backward(ctx, g, 11)
+
+
+class _XELossVideoFunction(torch.autograd.Function):
+    """_XELossFunction with the B videos once and Q caption rows each (include/xgate_train_video.h)."""
+
+    @staticmethod
+    def forward(ctx, model, save, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes, class_mask,
+                weight_class, *params):
+        from . import _native_train_video as ntv
+        B, K, _ = feats_rgb.shape
+        Q, T = seq.shape[1], seq.shape[2]
+        dev = feats_rgb.device
+        d = model._dims(B, K, T)
+        key, ws = model._video_workspace(d, Q, dev, save)
+        wp, wn = _ws_ptr(ws)
+        rows = (pos_feats.reshape(B * Q, -1), seq.reshape(B * Q, T), seq_mask.reshape(B * Q, T))
+        b, keep = model._batch(feats_rgb, feats_opfl, feat_mask, *rows)
+        cc = None if cap_classes is None else cap_classes.detach().reshape(B * Q, T).contiguous().long()
+        cm = None if class_mask is None else class_mask.detach().reshape(B * Q, T).contiguous().float()
+        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        ps, bn, run = model._params_struct(), model._bn_struct(), model._run(save)
+        model._bump_bn()                           # (in FRONT of the forward, as _XELossFunction has it)
+        try:
+            nv.check(ntv.lib().xgtv_xe_loss_fwd(_stream(), C.byref(d), Q, C.byref(ps), C.byref(bn), C.byref(b), nv.ptr(cc), nv.ptr(cm),
+                                                weight_class, C.byref(run), wp, wn, nv.ptr(losses)), "xgtv_xe_loss_fwd")
+        except Exception:
+            model._bump_bn(-1)                     # the call was refused: num_batches_tracked stays where it was
+            if save:
+                model._video_pool[(key, True)].append(ws)
+            raise
+        ctx.model, ctx.d, ctx.Q, ctx.ws, ctx.key, ctx.keep, ctx.run, ctx.saved_ws = model, d, Q, ws, key, keep, run, save
+        ctx.cc, ctx.cm, ctx.wc = cc, cm, weight_class
+        model.last_losses = losses.detach()        # READ-ONLY for callers: it shares storage with the returned loss (no copy kernel)
+        return losses[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        from . import _native_train_video as ntv
+        if not ctx.saved_ws:
+            raise nv.XgError("backward without saved activations")
+        model = ctx.model
+        g, gs = model._grads_struct()
+        b, keep = model._batch(*ctx.keep)
+        wp, wn = _ws_ptr(ctx.ws)
+        run = _with_grad_event(model, ctx.run)
+        dl = dloss.detach().contiguous().float().to(keep[0].device)
+        nv.check(ntv.lib().xgtv_xe_loss_bwd(_stream(), C.byref(ctx.d), ctx.Q, C.byref(model._params_struct()), C.byref(gs), C.byref(b),
+                                            nv.ptr(ctx.cc), nv.ptr(ctx.cm), ctx.wc, nv.ptr(dl), C.byref(run), wp, wn),
+                 "xgtv_xe_loss_bwd")
+        model._video_pool[(ctx.key, True)].append(ctx.ws)
+        model._last_video_ws = (ctx.d, ctx.Q, ctx.ws)      # tests / tools: what xgtv_video_grads reads (valid until the next call reuses it)
+        ctx.ws = None
+        return (None,) * 11 + tuple(model._grad_views(g))
 
 
 class _RolloutFunction(torch.autograd.Function):
