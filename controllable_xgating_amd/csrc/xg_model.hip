@@ -22,6 +22,7 @@
 #include "../../include/xgate_beam_diverse.h"
 #include "../../include/xgate_pair.h"
 #include "../../include/xgate_train_video.h"
+#include "../../include/xgate_scst_video.h"
 
 #include <new>
 #include <cstdlib>
@@ -1752,7 +1753,8 @@ static int videos_once(Streams& es, const XgDims& de, const XgParams& p, const X
 // w.H1 / C1 / H2 / C2.  Plain: `x` holds the d.B rows, everything runs in `w` (encode_and_init).  PairVideos: rollout_open_pair_videos.
 // RowsPerVideo (xgcc_rollout; videos_once): `x` holds the d1->B = d.B / rows_per_video videos once and pos_feats per row.  Only the
 // initial state is repeated, every step's attention reads enc's V and v2a(V) at row / S.  `w` is the row part of cc_carve: every
-// per-step tensor is ONE block that each step overwrites (slot() below), the state alternates between two blocks.
+// per-step tensor is ONE block that each step overwrites (slot() below), the state alternates between two blocks.  With
+// RolloutCall.keep (xgsv_rollout) `w` is the row part of sv_carve instead and the steps write time-major slots, as the Plain form does.
 enum class RolloutForm { Plain, PairVideos, RowsPerVideo };
 struct RolloutCall {
     int mode = XG_ROLLOUT_GREEDY;
@@ -1767,6 +1769,9 @@ struct RolloutCall {
     RolloutForm form = RolloutForm::Plain;
     const XgDims* d1 = nullptr; Ws* enc = nullptr;      // PairVideos, RowsPerVideo: the videos' dims and the workspace their encoder runs in
     int rows_per_video = 0;                             // RowsPerVideo
+    // RowsPerVideo with everything a backward reads KEPT (xgsv_rollout, include/xgate_scst_video.h): `w` is the row part of sv_carve,
+    // every saved tensor and the state are time-major blocks (step_io_at), the gates are saved and the (T, B, E) embedding copy is made
+    bool keep = false;
     // PairVideos under train-mode dropout (include/xgate_pair.h): rows [split, B) take every mask -- encoder and decoder -- from
     // seed_greedy, as rows 0 .. of a call of their own (rollout_open_pair_videos_two_seeds; StepIO.drop_split_rows)
     bool two_seeds = false; uint32_t seed_greedy = 0;
@@ -1833,12 +1838,13 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
     const int B = d->B, R = d->R, E = d->E, T = d->T, mode = c.mode, split = c.split;
     Streams es(st, run);
     const bool rows = c.form == RolloutForm::RowsPerVideo;
-    if ((c.form != RolloutForm::Plain && (!c.d1 || !c.enc)) || rows != (c.rows_per_video > 0) || !step_scratch_ok(w, false, rows)) return XG_EINVAL;
+    if ((c.form != RolloutForm::Plain && (!c.d1 || !c.enc)) || rows != (c.rows_per_video > 0) || (c.keep && !rows) || !step_scratch_ok(w, false, rows)) return XG_EINVAL;
     if (c.trunc && (mode != XG_ROLLOUT_SAMPLE || split != B || c.logits_alt)) return XG_EINVAL;     // every row draws, from this workspace's logits
     float* const state0[4] = {w.H1, w.C1, w.H2, w.C2};
     const float* pos_rows = c.form == RolloutForm::PairVideos ? w.DPOSG : x->pos_feats;
     const float *Vsrc = rows ? c.enc->Venc : w.Venc, *vproj_src = rows ? c.enc->vproj : w.vproj;
-    auto slot = [&](int t) { return rows ? 0 : t; };
+    const bool one_block = rows && !c.keep;             // cc_carve's row part: one overwritten block per per-step tensor
+    auto slot = [&](int t) { return one_block ? 0 : t; };
     switch (c.form) {
     case RolloutForm::Plain: XG_TRY(encode_and_init(es, *d, *p, bn, *x, *run, w)); break;
     case RolloutForm::PairVideos:
@@ -1882,11 +1888,12 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
         else XG_TRY(xgk_rollout_step(st, B, ra));
         StepIO s = step_io_at(w, *d, slot(t));
         s.pos = pos_rows; s.gp = w.GP + (size_t)slot(t) * B * R; s.mask = unf; s.ldm = 1;
-        if (rows) {                               // state block t & 1 -> the other one; no saved gates
+        if (rows) s.rows_per_video = c.rows_per_video;
+        if (one_block) {                          // state block t & 1 -> the other one; no saved gates
             const size_t in = (size_t)(t & 1) * B * R, out = (size_t)((t + 1) & 1) * B * R;
             s.h1 = w.H1 + in; s.c1 = w.C1 + in; s.h2 = w.H2 + in; s.c2 = w.C2 + in;
             s.h1o = w.H1 + out; s.c1o = w.C1 + out; s.h2o = w.H2 + out; s.c2o = w.C2 + out;
-            s.g1 = nullptr; s.g2 = nullptr; s.t = t; s.rows_per_video = c.rows_per_video;
+            s.g1 = nullptr; s.g2 = nullptr; s.t = t;
         }
         if (in_step) { s.sel = &sel; s.xt = nullptr; s.tok = tok; }
         if (c.two_seeds) { s.drop_split_rows = split; s.drop_seed_hi = c.seed_greedy; }
@@ -1904,7 +1911,7 @@ static int rollout_impl(hipStream_t st, const XgDims* d, const XgParams* p, cons
     }
     // the steps that chose their own tokens gathered their embedding rows inside the products: the (T, B, E) copy the backward (and a
     // compaction) reads is made here for all of them at once, off the token's path
-    if (step_select && T >= 3 && !rows)
+    if (step_select && T >= 3 && !one_block)
         XG_TRY(xgk_embed_gather(st, p->embed_w, E, w.TOK + B, (T - 2) * B, 1, 0, (T - 2) * B, d->V, w.Xe + (size_t)B * E, E));
     XG_TRY(record_prof(run->prof_event1, st));
     return xgk_rollout_finalize(st, w.alive, n_steps, T - 1, split < B ? 2 : 1);
@@ -2625,4 +2632,106 @@ extern "C" int xgtv_video_grads(void* stream, const XgDims* d, int32_t Q, const 
     const Ws& r = w.row;
     return xgk_attn_post_dV_group((hipStream_t)stream, r.P, w.enc.vproj, p->a2w_w, r.DE, dvproj, nullptr, r.ALPHA, r.DAF, d->R,
                                   (int64_t)dm.B * d->R, dV, d->T, d->B, Q, d->K, d->A, d->R);
+}
+
+// ---- self-critical training on S rollouts per video (include/xgate_scst_video.h): the sampled rollout of rollout_impl in its
+// rows-per-video form with everything the backward reads kept, and xg_rollout_bwd over M = B S rows with the videos once.  The
+// workspace is the per-video part (`enc`, as tv_carve has it) followed by the row part: the step scratch, the per-step tensors of the
+// decoder and of the reverse-time pass in time-major blocks, the raw logits of the T - 1 steps that ran, and the rollout's own
+// buffers.  No classifier tensors and no hoisted token side; of the row part only ALPHA and DE are (rows, K) blocks.
+namespace {
+
+TrainVideoWs sv_carve(const XgDims& d, int S, void* base) {
+    TrainVideoWs w{};
+    w.enc = carve(beam_dims(d, d.B), base);
+    w.enc.sh16 = nullptr; w.enc.bytes = w.enc.core_bytes;          // fp32 only: no bf16 mirror region
+    Carver c{static_cast<char*>(base), w.enc.core_bytes};
+    const size_t M = (size_t)d.B * S, K = d.K, R = d.R, A = d.A, E = d.E, V = d.V, T = d.T, TM = T * M;
+    Ws& s = w.row;
+    carve_step_scratch(c, s, M, R, false);
+    s.Xe = c.take<float>(TM * E); s.GP = c.take<float>(TM * R); s.POSG = c.take<float>(TM * R);
+    s.H1 = c.take<float>((T + 1) * M * R); s.C1 = c.take<float>((T + 1) * M * R);
+    s.H2 = c.take<float>((T + 1) * M * R); s.C2 = c.take<float>((T + 1) * M * R);
+    s.G1 = c.take<float>(TM * 4 * R); s.G2 = c.take<float>(TM * 4 * R);
+    s.P = c.take<float>(TM * A); s.ALPHA = c.take<float>(TM * K); s.AF = c.take<float>(TM * R);
+    s.LOGITS = c.take<float>((T - 1) * M * V);                     // the dead last step leaves none
+    s.LSE = c.take<float>(TM);
+    s.DH2OUT = c.take<float>(TM * R);
+    s.DS1 = c.take<float>(TM * 4 * R); s.DS2 = c.take<float>(TM * 4 * R); s.DP = c.take<float>(TM * A); s.DE = c.take<float>(TM * K);
+    for (int j = 0; j < 4; ++j) s.dst[1][j] = c.take<float>(M * R);
+    s.DPOSG = c.take<float>(TM * R); s.DH1X = c.take<float>(TM * R); s.DGP = c.take<float>(TM * R); s.DXe = c.take<float>(TM * E);
+    s.TOK = c.take<int64_t>(TM); s.TOKLP = c.take<float>(TM); s.UNF = c.take<float>(TM);
+    s.alive = c.take<int32_t>(4);
+    s.VPART = c.take<float>(M * ((V + 31) / 32 + 16) * 4);         // per-tile row statistics (row pitch: xg_select.h rs_pitch)
+    {   // the zero block of the reverse-time pass (zero_backward_block)
+        c.off = (c.off + 255) & ~(size_t)255;
+        const size_t z0 = c.off;
+        s.zblock = c.base ? c.base + z0 : nullptr;
+        s.DAF = c.take<float>(TM * R);
+        for (int j = 0; j < 4; ++j) s.dst[0][j] = c.take<float>(M * R);
+        s.tickets = c.take<int32_t>((size_t)SK_MAX_JOBS * SKPART_INTS);
+        s.zbytes = c.off - z0;
+    }
+    w.bytes = (c.off + 255) & ~(size_t)255;
+    s.bytes = s.core_bytes = w.bytes;
+    s.base_f = reinterpret_cast<const float*>(c.base);
+    s.end_f = c.base ? reinterpret_cast<const float*>(c.base + w.bytes) : nullptr;
+    s.sh16 = nullptr;
+    return w;
+}
+
+// The gates of the two entry points, in the order of include/xgate_scst_video.h (tv_open's)
+int sv_open(const XgDims* d, int S, const XgParams* p, const XgRun* run, void* ws, size_t ws_bytes, TrainVideoWs* w, XgDims* de,
+            XgDims* dm) {
+    if (!cc_dims_ok(d, S) || !ws) return XG_EINVAL;
+    *w = sv_carve(*d, S, ws);
+    if (ws_bytes < w->bytes) return XG_EWORKSPACE;
+    if ((uintptr_t)ws % 256 != 0 || !p || !run || run->gemm_mode != 0) return XG_EINVAL;
+    *de = beam_dims(*d, d->B);
+    *dm = *d; dm->B = d->B * S;
+    attach_packed(w->enc, *de, run);
+    attach_packed(w->row, *dm, run);
+    return XG_OK;
+}
+bool sv_batch_ok(const XgBatch* x) { return x && x->feats_rgb && x->feats_opfl && x->feat_mask && x->pos_feats; }
+
+}  // namespace
+
+extern "C" int xgsv_version(void) { return XGSV_VERSION; }
+
+extern "C" size_t xgsv_workspace_bytes(const XgDims* d, int32_t S) {
+    return cc_dims_ok(d, S) ? sv_carve(*d, S, nullptr).bytes : 0;
+}
+
+extern "C" int xgsv_rollout(void* stream, const XgDims* d, int32_t S, const XgParams* p, const XgBnState* bn, const XgBatch* x,
+                            const XgRun* run, const float* uniforms, float temperature, int64_t* seq, float* seq_logp,
+                            int32_t* n_steps, void* ws, size_t ws_bytes) {
+    TrainVideoWs w; XgDims de, dm;
+    XG_TRY(sv_open(d, S, p, run, ws, ws_bytes, &w, &de, &dm));
+    if (!sv_batch_ok(x) || !uniforms || !seq || !seq_logp || !n_steps || !(temperature > 0.f)) return XG_EINVAL;
+    if (!run->train && (!bn || !bn->rgb_mean || !bn->rgb_var || !bn->opfl_mean || !bn->opfl_var)) return XG_EINVAL;
+    RolloutCall c;
+    c.mode = XG_ROLLOUT_SAMPLE; c.uniforms = uniforms; c.temperature = temperature; c.split = dm.B;
+    c.form = RolloutForm::RowsPerVideo; c.d1 = &de; c.enc = &w.enc; c.rows_per_video = S; c.keep = true;
+    return rollout_impl((hipStream_t)stream, &dm, p, bn, x, run, w.row, seq, seq_logp, n_steps, c);
+}
+
+extern "C" int xgsv_rollout_bwd(void* stream, const XgDims* d, int32_t S, const XgParams* p, const XgParams* g, const XgBatch* x,
+                                const XgRun* run, const float* dseq_logp, void* ws, size_t ws_bytes) {
+    TrainVideoWs w; XgDims de, dm;
+    XG_TRY(sv_open(d, S, p, run, ws, ws_bytes, &w, &de, &dm));
+    if (!g || !sv_batch_ok(x) || !dseq_logp) return XG_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int M = dm.B, T = d->T;
+    Ws& r = w.row;
+    // dlogits of step t - 1's output from the token drawn at step t: LOGITS holds raw logits, LSE their log-sum-exp (xg_rollout_bwd)
+    XG_TRY(xgk_rollout_dlogits_lse(st, r.LOGITS, r.LSE, r.TOK + M, dseq_logp, T - 1, M, d->V, T - 1));
+    Streams ss(st, run);
+    // the rollout ran T - 1 core steps: the first T - 1 blocks of every time-major tensor are the (T - 1)-step problem
+    XgDims dT = dm;
+    dT.T = T - 1;
+    XG_TRY(heads_bwd(ss, dT, *p, *g, *run, r, dT.T * M, false, nullptr));
+    XG_TRY(decoder_bwd_core(ss, dT, *p, *g, *x, *run, r, r.UNF, 1, M, r.TOK, 1, M, S, &w.enc));
+    XG_TRY(encoder_bwd(ss, de, *p, *g, *x, *run, w.enc, w.enc.DV));
+    return ss.join();
 }

@@ -181,6 +181,34 @@ def scst_rollouts(model, feat1, feat2, feat_mask, pos_feat, overlap=True, mode=N
     return s_seq[:, :n_s], s_slp[:, :n_s], g_seq[:, :n_g]
 
 
+def scst_rollouts_per_video(model, feat1, feat2, feat_mask, pos_feat, rows_per_video=None, baseline="mean_others", temperature=1.0,
+                            uniforms=None):
+    """The rollouts of one self-critical iteration with S sampled rollouts per video on ONE encoder pass (SAModel.rollout_per_video,
+    docs/CAPTION_SCST_PER_VIDEO.md).  pos_feat (B,S,R), or (B,R) with rows_per_video = S: the video's feature for each of its S rows.
+    baseline "mean_others": no greedy rollout at all (a row's baseline is the mean score of the video's other rows); "greedy": the
+    existing ``sample`` in greedy mode on the B videos under no_grad, (B,R) pos_feat only.
+    Returns (gen (B,S,L), seqLogprobs (B,S,L) with a graph, n (1,) device int32, greedy (B,n') or None) -- no host sync for
+    "mean_others", the greedy rollout's own for "greedy"."""
+    if baseline not in ("mean_others", "greedy"):
+        raise ValueError('baseline "mean_others" or "greedy" expected, got %r' % (baseline,))
+    if pos_feat.dim() == 3:
+        if baseline == "greedy":
+            raise NotImplementedError('baseline "greedy" needs one pos_feat per video (B,R): which of the S rows would the greedy rollout take?')
+        if rows_per_video is not None and int(rows_per_video) != pos_feat.shape[1]:
+            raise ValueError("pos_feat (B, S = %d, R) against rows_per_video = %d" % (pos_feat.shape[1], rows_per_video))
+        pos_rows = pos_feat
+    else:
+        if rows_per_video is None or int(rows_per_video) < 1:
+            raise ValueError("a (B,R) pos_feat needs rows_per_video >= 1")
+        pos_rows = pos_feat.unsqueeze(1).expand(-1, int(rows_per_video), -1)
+    greedy = None
+    if baseline == "greedy":
+        with torch.no_grad():
+            greedy, _ = model.sample(feat1, feat2, feat_mask, pos_feat, {"sample_max": 1})
+    gen, slp, n = model.rollout_per_video(feat1, feat2, feat_mask, pos_rows, temperature=temperature, uniforms=uniforms)
+    return gen, slp, n, greedy
+
+
 class Trainer:
     """One object = the body of ``train(opt)`` (starttrain.py:19-242) without the data loader."""
 
@@ -233,6 +261,37 @@ class Trainer:
                 loss_classify = self.classify_crit(category, b["cap_classes"], b["cap_mask"], b["class_mask"])       # :127
                 loss = loss_language + wc * loss_classify                                    # :129
                 info.update(loss_language=loss_language, loss_classify=loss_classify)
+        elif (getattr(opt, "scst_rows_per_video", None) or 0) >= 2 or b["pos_feat"].dim() == 3:
+            # S sampled rollouts per video on one encoder pass; the advantage is formed on the device from one score per row.  The
+            # only host copy of the iteration is the scorer's copy of the tokens.
+            S = getattr(opt, "scst_rows_per_video", None)
+            baseline = getattr(opt, "scst_baseline", "mean_others")
+            gen_f, slp_f, n, greedy = scst_rollouts_per_video(model, b["feat1"], b["feat2"], b["feat_mask"], b["pos_feat"],
+                                                              rows_per_video=S, baseline=baseline)
+            B, S, L = gen_f.shape
+            if greedy is None:
+                tok = torch.cat([gen_f.reshape(B * S, L), n.to(torch.int64).expand(1, L)]).cpu()       # (one copy, one sync)
+                n_s = int(tok[-1, 0])
+                scores = np.asarray(self.scorer(tok[:B * S, :n_s].numpy(), None), dtype=np.float32)
+                base = "mean_others"
+            else:
+                g = torch.zeros(B, L, dtype=torch.int64, device=gen_f.device)
+                g[:, :greedy.shape[1]] = greedy
+                tok = torch.cat([gen_f.reshape(B * S, L), g, n.to(torch.int64).expand(1, L)]).cpu()    # (one copy, one sync)
+                n_s = int(tok[-1, 0])
+                scores = np.asarray(self.scorer(tok[:B * S, :n_s].numpy(), tok[B * S:B * S + B, :greedy.shape[1]].numpy()),
+                                    dtype=np.float32)
+                base = torch.from_numpy(np.ascontiguousarray(scores[B * S:])).to(slp_f.device)
+            if getattr(self, "rl_crit_video", None) is None:
+                from .model import PerVideoRewardCriterion
+                self.rl_crit_video = PerVideoRewardCriterion()
+            score = torch.from_numpy(np.ascontiguousarray(scores[:B * S])).reshape(B, S).to(slp_f.device)
+            loss = self.rl_crit_video(slp_f, gen_f, score, n=n, baseline=base)
+            self.last_advantage = self.rl_crit_video.last_advantage          # (B,S) on the device: nothing is copied back for it
+            # the mean advantage over a greedy baseline, as in the paths below; under "mean_others" that mean is zero by
+            # construction, so the mean score of the rollouts is reported
+            rows = scores[:B * S].reshape(B, S)
+            info["avg_reward"] = float(np.mean(rows - scores[B * S:, None]) if greedy is not None else np.mean(rows))
         else:
             mode = getattr(opt, "scst_rollout_mode", None)
             if mode in (None, "batched") and model.training:

@@ -431,6 +431,67 @@ class SAModel(FlatParams, nn.Module):
             lst.append(ws)
         return key, ws
 
+    def rollout_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, temperature=1.0, uniforms=None, trim=False):
+        """The sampled rollout of ``sample`` for S `pos_feats` rows per video on ONE encoder pass, WITH a graph (include/
+        xgate_scst_video.h): the B videos are handed over once -- feats_rgb (B,K,F1), feats_opfl (B,K,F2), feat_mask (B,K) -- with
+        pos_feats (B,S,R); row b S + s is rollout s of video b.  Returns seq (B,S,L) int64, seqLogprobs (B,S,L) and n (1,) int32 on
+        the device (the early-exit width: no host sync); with trim=True the two tensors cut to n (the call's only host sync).
+        ``seqLogprobs.backward(...)`` / a criterion on it (PerVideoRewardCriterion) fills every parameter gradient.
+
+        Row by row this is ``sample(..., {'sample_max': 0})`` on the batch with every video repeated S times, uniforms (L + 1, B*S)
+        and the untempered log-probability gathered.  The encoder, init_hidden and v2a(V) run once per video, forward and backward;
+        the BatchNorm running statistics receive ONE update from the B videos; under dropout the encoder's masks are those of a
+        B-video call, the decoder's those of a B S-row call (docs/CAPTION_SCST_PER_VIDEO.md).  Without grad it still runs: train-
+        or eval-mode sampling with nothing kept.  fp32 and device tensors only."""
+        from . import _native_scst_video  # noqa: F401  (the binding is declared when the call is made)
+        if self.precision != "fp32":
+            raise NotImplementedError("rollout_per_video is fp32 only (precision = %r)" % (self.precision,))
+        for name, t, nd in (("feats_rgb", feats_rgb, 3), ("feats_opfl", feats_opfl, 3), ("feat_mask", feat_mask, 2),
+                            ("pos_feats", pos_feats, 3)):
+            if not torch.is_tensor(t) or t.dim() != nd:
+                raise ValueError("%s: a %d-dimensional tensor expected" % (name, nd))
+        B, K = feats_rgb.shape[:2]
+        S, L = int(pos_feats.shape[1]), self.seq_length
+        if B < 1 or K < 1 or S < 1:
+            raise ValueError("B, K, S >= 1 expected, got B %d, K %d, S %d" % (B, K, S))
+        for name, t, shape in (("feats_rgb", feats_rgb, (B, K, self.feat_size)), ("feats_opfl", feats_opfl, (B, K, self.feat_size2)),
+                               ("feat_mask", feat_mask, (B, K)), ("pos_feats", pos_feats, (B, S, self.rnn_size))):
+            if tuple(t.shape) != shape:
+                raise ValueError("%s %s expected, got %s" % (name, shape, tuple(t.shape)))
+        if not (float(temperature) > 0.0):
+            raise ValueError("temperature > 0 expected, got %r" % (temperature,))
+        if uniforms is not None and (not torch.is_tensor(uniforms) or tuple(uniforms.shape) != (L + 1, B * S)):
+            raise ValueError("uniforms (L + 1 = %d, B*S = %d) expected, got %s"
+                             % (L + 1, B * S, tuple(uniforms.shape) if torch.is_tensor(uniforms) else type(uniforms)))
+        for t in (feats_rgb, feats_opfl, feat_mask, pos_feats, uniforms):
+            if t is not None and not t.is_cuda:
+                raise NotImplementedError("rollout_per_video needs device tensors: there is no CPU path")
+        params = self._param_list()
+        save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        seq, slp, n = _RolloutVideoFunction.apply(self, save, feats_rgb, feats_opfl, feat_mask, pos_feats, uniforms,
+                                                  float(temperature), *params)
+        if trim:
+            k = int(n.item())
+            return seq[:, :, :k], slp[:, :, :k], n
+        return seq, slp, n
+
+    def _scst_video_workspace(self, d, S, dev, save):
+        """(key, tensor) of a workspace of rollout_per_video (xgsv_workspace_bytes), pooled as _video_workspace pools its own: the
+        forward's until its backward has run when it saves activations, else one shared scratch per shape; not zero-filled."""
+        from . import _native_scst_video as nsv
+        key = (tuple(getattr(d, f[0]) for f in d._fields_), S, str(dev))
+        pool = self.__dict__.setdefault("_scst_video_pool", {})
+        lst = pool.setdefault((key, save), [])
+        if lst:
+            return key, (lst.pop() if save else lst[0])
+        n = nsv.lib().xgsv_workspace_bytes(C.byref(d), S)
+        if n == 0:
+            raise nv.XgError("xgsv_workspace_bytes: invalid dims or too many rows (B %d, S %d)" % (d.B, S))
+        ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+        if not save:
+            lst.append(ws)
+        return key, ws
+
     def sample_pair(self, feats_rgb, feats_opfl, feat_mask, pos_feats, opt={}):
         """The two rollouts of one SCST iteration in ONE batched pass: ``sample(..., {'sample_max': 0})``
         (starttrain.py:131) and the greedy baseline ``sample(..., {'sample_max': 1})`` (myutils.py:45-48).
@@ -1139,6 +1200,66 @@ class _XELossVideoFunction(torch.autograd.Function):
         return (None,) * 11 + tuple(model._grad_views(g))
 
 
+class _RolloutVideoFunction(torch.autograd.Function):
+    """The sampled rollout with the B videos once and S rollout rows each (include/xgate_scst_video.h), modelled on
+    _XELossVideoFunction: a workspace of its own pool, given back after the backward and when the call is refused."""
+
+    @staticmethod
+    def forward(ctx, model, save, feats_rgb, feats_opfl, feat_mask, pos_feats, uniforms, temperature, *params):
+        from . import _native_scst_video as nsv
+        B, K, _ = feats_rgb.shape
+        S, L = pos_feats.shape[1], model.seq_length
+        dev = feats_rgb.device
+        d = model._dims(B, K, L + 1)
+        key, ws = model._scst_video_workspace(d, S, dev, save)
+        wp, wn = _ws_ptr(ws)
+        b, keep = model._batch(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(B * S, -1))
+        if uniforms is None:
+            uniforms = torch.rand(L + 1, B * S, device=dev, dtype=torch.float32)
+        uniforms = uniforms.detach().contiguous().float()
+        seq = torch.empty(B, S, L, dtype=torch.int64, device=dev)
+        slp = torch.empty(B, S, L, dtype=torch.float32, device=dev)
+        n = torch.empty(1, dtype=torch.int32, device=dev)
+        ps, bn, run = model._params_struct(), model._bn_struct(), model._run(save)
+        model._bump_bn()                           # (in FRONT of the forward, as _XELossFunction has it)
+        try:
+            nv.check(nsv.lib().xgsv_rollout(_stream(), C.byref(d), S, C.byref(ps), C.byref(bn), C.byref(b), C.byref(run),
+                                            nv.ptr(uniforms), temperature, nv.ptr(seq), nv.ptr(slp), nv.ptr(n), wp, wn),
+                     "xgsv_rollout")
+        except Exception:
+            model._bump_bn(-1)                     # the call was refused: num_batches_tracked stays where it was
+            if save:
+                model._scst_video_pool[(key, True)].append(ws)
+            raise
+        ctx.model, ctx.d, ctx.S, ctx.ws, ctx.key, ctx.keep, ctx.run, ctx.saved_ws = model, d, S, ws, key, keep, run, save
+        ctx.mark_non_differentiable(seq, n)
+        return seq, slp, n
+
+    @staticmethod
+    def backward(ctx, dseq, dslp, dn):
+        from . import _native_scst_video as nsv
+        if not ctx.saved_ws:
+            raise nv.XgError("backward without saved activations")
+        model, d, S = ctx.model, ctx.d, ctx.S
+        g, gs = model._grads_struct()
+        b, keep = model._batch(*ctx.keep)
+        wp, wn = _ws_ptr(ctx.ws)
+        run = _with_grad_event(model, ctx.run)
+        L = d.T - 1
+        full = dslp.detach().reshape(d.B * S, -1).float()
+        if full.shape[1] != L:                     # (a gradient of trimmed log-probs: the columns behind n carry none)
+            wide = torch.zeros(d.B * S, L, dtype=torch.float32, device=keep[0].device)
+            wide[:, :full.shape[1]] = full
+            full = wide
+        full = full.contiguous()
+        nv.check(nsv.lib().xgsv_rollout_bwd(_stream(), C.byref(d), S, C.byref(model._params_struct()), C.byref(gs), C.byref(b),
+                                            C.byref(run), nv.ptr(full), wp, wn), "xgsv_rollout_bwd")
+        model._scst_video_pool[(ctx.key, True)].append(ctx.ws)
+        model._last_scst_video_ws = (d, S, ctx.ws)         # tests / tools (valid until the next call reuses it)
+        ctx.ws = None
+        return (None,) * 8 + tuple(model._grad_views(g))
+
+
 class _RolloutFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, feats_rgb, feats_opfl, feat_mask, pos_feats, mode, uniforms, forced, temperature,
@@ -1339,3 +1460,77 @@ class RewardCriterion(nn.Module):
     def forward(self, input, seq, reward, n=None):
         reward = torch.as_tensor(reward, dtype=torch.float32, device=input.device)
         return _RewardFunction.apply(input, seq, reward, n)
+
+
+class _PerVideoRewardFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, slp, seq, score, base, baseline, n):
+        from . import _native_scst_video as nsv
+        B, S, L = slp.shape
+        dev = slp.device
+        slp_c = slp.detach().contiguous().float()
+        seq = seq.detach().contiguous().long()
+        score = score.detach().contiguous().float()
+        base = None if base is None else base.detach().contiguous().float()
+        nd = None if n is None else n.detach().reshape(-1)[:1].to(torch.int32)
+        adv = torch.empty(B, S, dtype=torch.float32, device=dev)
+        partial = torch.empty(B, 2, dtype=torch.float32, device=dev)
+        sums = torch.empty(2, dtype=torch.float32, device=dev)
+        nv.check(nsv.lib().xgsv_reward_fwd(_stream(), nv.ptr(slp_c), nv.ptr(seq), nv.ptr(score), nv.ptr(base), baseline, nv.ptr(nd),
+                                           B, S, L, nv.ptr(adv), nv.ptr(partial), nv.ptr(sums)), "xgsv_reward_fwd")
+        ctx.meta = (B, S, L, seq, adv, nd, sums)
+        ctx.mark_non_differentiable(adv)
+        return sums[0] / sums[1], adv
+
+    @staticmethod
+    def backward(ctx, dloss, dadv):
+        from . import _native_scst_video as nsv
+        B, S, L, seq, adv, nd, sums = ctx.meta
+        dslp = torch.empty(B, S, L, dtype=torch.float32, device=sums.device)
+        dl = dloss.detach().reshape(1).contiguous().float().to(sums.device)      # device scalar: no sync
+        nv.check(nsv.lib().xgsv_reward_bwd(_stream(), nv.ptr(seq), nv.ptr(adv), nv.ptr(nd), B, S, L, nv.ptr(sums), nv.ptr(dl),
+                                           nv.ptr(dslp)), "xgsv_reward_bwd")
+        return dslp, None, None, None, None, None
+
+
+class PerVideoRewardCriterion(nn.Module):
+    """RewardCriterion over B videos x S rollouts with ONE score per row and the advantage formed on the device (include/
+    xgate_scst_video.h): ``crit(seqLogprobs (B,S,L), seq (B,S,L), score (B,S), n=None, baseline="mean_others")`` returns
+    -sum(seqLogprobs * adv * mask) / sum(mask), mask as in RewardCriterion (`n`: the rollout's device-side width).  baseline:
+    "mean_others" (adv = score minus the mean of the video's other S - 1 scores; S >= 2), None (adv = score) or a (B,) tensor (adv =
+    score - baseline[b]; S = 1 with the greedy rollout's score is the reference's self-critical reward).  ``last_advantage`` holds
+    the (B,S) advantages of the last call.  The sums take no float atomics: two identical calls give identical bits."""
+
+    def __init__(self):
+        super().__init__()
+        self.last_advantage = None
+
+    def forward(self, input, seq, score, n=None, baseline="mean_others"):
+        from ._native_scst_video import XGSV_BASE_GIVEN, XGSV_BASE_MEAN_OTHERS, XGSV_BASE_NONE
+        if not torch.is_tensor(input) or input.dim() != 3:
+            raise ValueError("seqLogprobs (B,S,L) expected")
+        B, S, L = input.shape
+        if not torch.is_tensor(seq) or tuple(seq.shape) != (B, S, L):
+            raise ValueError("seq %s expected, got %s" % ((B, S, L), tuple(seq.shape) if torch.is_tensor(seq) else type(seq)))
+        score = torch.as_tensor(score, dtype=torch.float32, device=input.device)
+        if tuple(score.shape) != (B, S):
+            raise ValueError("score %s expected, got %s" % ((B, S), tuple(score.shape)))
+        base = None
+        if baseline is None:
+            mode = XGSV_BASE_NONE
+        elif isinstance(baseline, str):
+            if baseline != "mean_others":
+                raise ValueError('baseline: "mean_others", None or a (B,) tensor expected, got %r' % (baseline,))
+            if S < 2:
+                raise ValueError('baseline "mean_others" needs S >= 2 rollouts per video, got %d' % S)
+            mode = XGSV_BASE_MEAN_OTHERS
+        else:
+            base = torch.as_tensor(baseline, dtype=torch.float32, device=input.device)
+            if tuple(base.shape) != (B,):
+                raise ValueError("baseline (%d,) expected, got %s" % (B, tuple(base.shape)))
+            mode = XGSV_BASE_GIVEN
+        if not input.is_cuda or not seq.is_cuda:
+            raise NotImplementedError("PerVideoRewardCriterion needs device tensors: there is no CPU path")
+        loss, adv = _PerVideoRewardFunction.apply(input, seq, score, base, mode, n)
+        self.last_advantage = adv
+        return loss
