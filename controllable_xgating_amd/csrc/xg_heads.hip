@@ -1264,6 +1264,173 @@ __global__ void ss_select_kernel(const int64_t* seq, int T, int t, int B, const 
     tok[b] = take ? sampled[b] : seq[(size_t)b * T + t];
 }
 
+// ------------------------------------------------------------------------------------------------
+// The token choice of scheduled sampling inside the fused loss (include/xgate_ss.h; SAModel.py:89-99): row m of step t is fed a
+// token drawn from step t - 1's distribution iff u_sel[m] < ss_prob (strict, as ss_select_kernel has it), else seq[m, t].  The draw
+// is the inverse CDF at temperature 1 over w_v = exp(logit_v - max): the first column whose running sum passes u_tok[m] times the
+// total.  One launch writes the fed token (twice: the workspace's copy the backward reads and the caller's) and gathers its
+// embedding row into the step's xt.  a.logits == null: nothing is drawn (t = 0, eval mode, ss_prob = 0).
+//
+// ss_choice_tiles_kernel  over the per-tile row statistics of xgk_vocab_part, on roll_select_rows16's scheme (xg_select.h): 16 lanes
+//                         (one DPP row) per token row, four rows per wave.  Stage 1 requests the row's statistics, its two uniforms
+//                         and seq[m, t] together; the draw -- scan of the lanes' tile sums in double, walk to the tile, that tile's
+//                         stored logits, scan and walk inside it -- runs only in waves where some row's coin says so.
+// ss_choice_row_kernel    every other shape: one workgroup per row over the stored (M, V) raw logits, rollout_step_kernel's draw
+//                         (chunk sums, block scan in double in a fixed order, the owner walks its chunk).
+__device__ __forceinline__ int ss_clamp_tok(int64_t t, int V) { return t < 0 ? 0 : (t >= V ? V - 1 : (int)t); }
+
+constexpr int SSC_T = 256;                // 16 token rows per workgroup
+__global__ void __launch_bounds__(SSC_T) ss_choice_tiles_kernel(SsChoiceArgs a) {
+    XG_CHAIN_PRIO();
+    const int lane = threadIdx.x & 63, l = lane & 15;
+    const int b = (int)((blockIdx.x * SSC_T + threadIdx.x) >> 4);
+    const bool here = b < a.M;
+    const int br = here ? b : 0;
+    const int nt = a.ntiles, per = rs_per(nt);
+    // ---- stage 1: the row's statistics, its two uniforms and its ground-truth token requested together
+    const v_f32x4* pr = reinterpret_cast<const v_f32x4*>(a.part) + (size_t)br * (per << 4) + l;
+    v_f32x4 pv[RSW_PER];
+#pragma unroll
+    for (int i = 0; i < RSW_PER; ++i) {
+        const int j = l * per + i;
+        const v_f32x4 z = {-INFINITY, 0.f, 0.f, 0.f};
+        pv[i] = (i < per && j < nt) ? pr[i << 4] : z;           // slot (i, l): rs_slot(j, per)
+    }
+    const float usel = a.u_sel[br], uni = a.u_tok[br];
+    int tk = ss_clamp_tok(a.seq[(size_t)br * a.T + a.t], a.V);
+    const bool smp = here && usel < a.ss_prob;                  // sample_mask = sample_prob < ss_prob (:91)
+    if (__any(smp)) {
+        // ---- stage 2: the row maximum, the tiles' weights against it, the draw's tile
+        float best = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < RSW_PER; ++i) best = fmaxf(best, pv[i][0]);
+        const float mx = rs_row_max(best);
+        double ct = 0.0;
+#pragma unroll
+        for (int i = 0; i < RSW_PER; ++i) {
+            const float wt = pv[i][1] * __expf(pv[i][0] - mx);  // (absent tiles: exp(-inf) = 0 times a zero sum)
+            pv[i][2] = wt;
+            ct += (double)wt;
+        }
+        const double inc = rs_row_scan(ct);
+        const double tot = rs_row_sum(ct);
+        const double target = (double)uni * tot;
+        unsigned long long pass = __ballot(inc > target);
+        unsigned mine = (unsigned)(pass >> (lane & 48)) & 0xFFFFu;
+        int owner = mine ? __ffs((int)mine) - 1 : 15;
+        double run = inc - ct;
+        int jt = min(nt, l * per + per) - 1;                    // (rounding: the last tile of the share if nothing passes)
+        if (jt < l * per) jt = nt - 1;
+        bool found = false;
+#pragma unroll
+        for (int i = 0; i < RSW_PER; ++i) {
+            if (!found && i < per && l * per + i < nt) {
+                if (run + (double)pv[i][2] > target) { jt = l * per + i; found = true; }
+                else run += (double)pv[i][2];
+            }
+        }
+        bool own = l == owner;
+        jt = rs_row_max(own ? jt : -1);
+        const float base = (float)rs_row_sum(own ? run : 0.0), tf = (float)target;
+        const int v0 = jt * a.tw;
+        // ---- stage 3: the drawn tile's stored logits (tw <= 128: 8 per lane, column order)
+        constexpr int XP = 8;
+        float x[XP], e[XP], es = 0.f;
+        const int nvalid = min(a.tw, a.V - v0);
+        const int xper = (a.tw + 15) >> 4;                      // 5 for 80-column tiles, 2 for 32
+        const float* xrow = a.logits + (size_t)br * a.V + v0;
+#pragma unroll
+        for (int k = 0; k < XP; ++k) { const int c = l * xper + k; x[k] = (smp && k < xper && c < nvalid) ? xrow[c] : -INFINITY; }
+        // ---- stage 4: the draw inside its tile
+#pragma unroll
+        for (int k = 0; k < XP; ++k) { e[k] = (smp && k < xper && l * xper + k < nvalid) ? __expf(x[k] - mx) : 0.f; es += e[k]; }
+        const float incf = rs_row_scan(es);
+        pass = __ballot(smp && base + incf > tf);
+        mine = (unsigned)(pass >> (lane & 48)) & 0xFFFFu;
+        // (nothing passes -- rounding at the very end of the distribution --: the tile's last valid column)
+        owner = mine ? __ffs((int)mine) - 1 : min(15, (nvalid - 1) / xper);
+        float runf = base + (incf - es);
+        int pk = min(xper, nvalid - l * xper) - 1; if (pk < 0) pk = 0;
+        found = false;
+#pragma unroll
+        for (int k = 0; k < XP; ++k) {
+            if (!found && k < xper && l * xper + k < nvalid) {
+                runf += e[k];
+                if (runf > tf) { pk = k; found = true; }
+            }
+        }
+        own = smp && l == owner;
+        const int tks = rs_row_max(own ? v0 + l * xper + pk : -1);
+        if (smp) tk = tks;
+    }
+    if (!here) return;
+    if (l == 0) { a.tok[b] = (int64_t)tk; a.tok_out[b] = (int64_t)tk; }       // the lane that owns the row
+    const float* src = a.table + (size_t)tk * a.E;
+    float* dst = a.xt + (size_t)b * a.E;
+    if (a.E % 4 == 0 && (((uintptr_t)a.table | (uintptr_t)a.xt) & 15) == 0) {
+        for (int c = l * 4; c < a.E; c += 64) *reinterpret_cast<float4*>(dst + c) = *reinterpret_cast<const float4*>(src + c);
+    } else {
+        for (int c = l; c < a.E; c += 16) dst[c] = src[c];
+    }
+}
+
+constexpr int SSR_T = 1024;
+__global__ void __launch_bounds__(SSR_T) ss_choice_row_kernel(SsChoiceArgs a) {
+    XG_CHAIN_PRIO();
+    __shared__ float red[SSR_T / 64];
+    __shared__ double wave_tot[SSR_T / 64];
+    __shared__ int s_owner, s_tok;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int tk = ss_clamp_tok(a.seq[(size_t)b * a.T + a.t], a.V);
+    const bool smp = a.logits != nullptr && a.u_sel[b] < a.ss_prob;          // (the same in every thread of the workgroup)
+    if (smp) {
+        const float* x = a.logits + (size_t)b * a.V;
+        float best = -INFINITY;
+        for (int v = tid; v < a.V; v += SSR_T) best = fmaxf(best, x[v]);
+        for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
+        if (lane == 0) red[wave] = best;
+        if (tid == 0) s_owner = SSR_T - 1;
+        __syncthreads();
+        float mx = red[0];
+        for (int i = 1; i < SSR_T / 64; ++i) mx = fmaxf(mx, red[i]);
+        // each thread owns a contiguous chunk of columns; chunk sums -> block scan in double -> the owner walks its chunk
+        const int per = (a.V + SSR_T - 1) / SSR_T;
+        const int v0 = min(a.V, tid * per), v1 = min(a.V, v0 + per);
+        float cs = 0.f;
+        for (int v = v0; v < v1; ++v) cs += __expf(x[v] - mx);
+        double inc = (double)cs;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const double up = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += up;
+        }
+        if (lane == 63) wave_tot[wave] = inc;
+        __syncthreads();
+        double off = 0.0, tot = 0.0;
+#pragma unroll
+        for (int i = 0; i < SSR_T / 64; ++i) { const double wt = wave_tot[i]; if (i < wave) off += wt; tot += wt; }
+        inc += off;
+        const double target = (double)a.u_tok[b] * tot;
+        if (inc > target) atomicMin(&s_owner, tid);             // first chunk whose running sum passes the target
+        __syncthreads();
+        if (tid == s_owner) {
+            float run = (float)(inc - (double)cs);
+            const float tf = (float)target;
+            int pick = v1 - 1;                                  // (rounding at the very end of the distribution: the last column)
+            if (pick < v0) pick = a.V - 1;
+            for (int v = v0; v < v1; ++v) {
+                run += __expf(x[v] - mx);
+                if (run > tf) { pick = v; break; }
+            }
+            s_tok = pick;
+        }
+        __syncthreads();
+        tk = s_tok;
+    }
+    if (tid == 0) { a.tok[b] = (int64_t)tk; a.tok_out[b] = (int64_t)tk; }
+    for (int e = tid; e < a.E; e += SSR_T) a.xt[(size_t)b * a.E + e] = a.table[(size_t)tk * a.E + e];
+}
+
 }  // namespace
 
 int xgk_log_softmax(hipStream_t st, const float* in, int ldin, float* out, int ldout, int rows, int V, int inner,
@@ -1427,6 +1594,19 @@ int xgk_rollout_dlogits_lse(hipStream_t st, float* logits, const float* lse, con
 int xgk_ss_select(hipStream_t st, const int64_t* seq, int T, int t, int B, const float* u_sel, float ss_prob,
                   const int64_t* sampled, int64_t* tok) {
     hipLaunchKernelGGL(ss_select_kernel, dim3(xg_cdiv(B, 256)), dim3(256), 0, st, seq, T, t, B, u_sel, ss_prob, sampled, tok);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+// 1: the choice reads the tile statistics xgk_vocab_part left (a.part), 0: the stored rows themselves
+int xgk_ss_choice_form(const SsChoiceArgs& a) {
+    return (a.logits && a.part && a.ntiles >= 1 && a.ntiles <= 16 * RSW_PER && a.tw >= 1 && a.tw <= 128 && (uintptr_t)a.part % 16 == 0) ? 1 : 0;
+}
+int xgk_ss_choice(hipStream_t st, const SsChoiceArgs& a) {
+    if (a.M < 1 || a.V < 2 || a.E < 1 || a.T < 1 || a.t < 0 || a.t >= a.T || !a.seq || !a.table || !a.tok || !a.tok_out || !a.xt ||
+        (a.logits && (!a.u_sel || !a.u_tok)))
+        return XG_EINVAL;
+    if (xgk_ss_choice_form(a)) hipLaunchKernelGGL(ss_choice_tiles_kernel, dim3(xg_cdiv(a.M, SSC_T / 16)), dim3(SSC_T), 0, st, a);
+    else hipLaunchKernelGGL(ss_choice_row_kernel, dim3(a.M), dim3(SSR_T), 0, st, a);
     XG_CHECK_LAUNCH();
     return XG_OK;
 }

@@ -386,6 +386,23 @@ int xgk_compact(hipStream_t st, CompactArgs& a);
 // scheduled sampling (SAModel.py:89-99): tok[b] = u_sel[b] < ss_prob ? sampled[b] : seq[b*T + t]
 int xgk_ss_select(hipStream_t st, const int64_t* seq, int T, int t, int B, const float* u_sel, float ss_prob,
                   const int64_t* sampled, int64_t* tok);
+// the token choice of scheduled sampling inside the fused loss (include/xgate_ss.h), one launch per step: the fed token of every
+// row -- drawn from step t - 1's raw logits where u_sel < ss_prob, else seq[m, t] -- and its embedding row into xt
+struct SsChoiceArgs {
+    const float* logits;      // (M,V) raw logits of step t - 1 as the vocabulary product stored them; null: nothing is drawn
+    const float* part;        // their tile statistics (xgk_vocab_part), or null: the full-row form
+    const float* u_sel;       // (M) step-t slices of the two uniforms (read when logits != null)
+    const float* u_tok;
+    const int64_t* seq;       // (M,T)
+    const float* table;       // embedding (V,E)
+    int64_t* tok;             // (M) step-t slices: the workspace's copy and the caller's
+    int64_t* tok_out;
+    float* xt;                // (M,E) out
+    float ss_prob;
+    int M, V, E, T, t, ntiles, tw;
+};
+int xgk_ss_choice_form(const SsChoiceArgs& a);   // 1: tile statistics, 0: full rows
+int xgk_ss_choice(hipStream_t st, const SsChoiceArgs& a);
 
 // ---- xg_beam.hip: the captioner's beam search (include/xgate_beam.h)
 // dst row b W + slot = src row b (rows of n floats), every entry in one launch

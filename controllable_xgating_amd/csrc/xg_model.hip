@@ -23,6 +23,7 @@
 #include "../../include/xgate_pair.h"
 #include "../../include/xgate_train_video.h"
 #include "../../include/xgate_scst_video.h"
+#include "../../include/xgate_ss.h"
 
 #include <new>
 #include <cstdlib>
@@ -2733,5 +2734,158 @@ extern "C" int xgsv_rollout_bwd(void* stream, const XgDims* d, int32_t S, const 
     XG_TRY(heads_bwd(ss, dT, *p, *g, *run, r, dT.T * M, false, nullptr));
     XG_TRY(decoder_bwd_core(ss, dT, *p, *g, *x, *run, r, r.UNF, 1, M, r.TOK, 1, M, S, &w.enc));
     XG_TRY(encoder_bwd(ss, de, *p, *g, *x, *run, w.enc, w.enc.DV));
+    return ss.join();
+}
+
+// ---- the fused teacher-forced loss under scheduled sampling (include/xgate_ss.h): xg_xe_loss_fwd / xgtv_xe_loss_fwd with the step's
+// token CHOSEN in front of the step (xg_heads.hip: ss_choice_*_kernel) from the logits the step before stored, so the token side is
+// not hoisted: the step runs in its token-fed form (the rollout's), the vocabulary product follows every step and leaves the tile
+// statistics the next choice reads.  Five dependent launches per step.  Behind the loop: the cross-entropy over the stored raw
+// logits, the classifier head batched over T, the losses.  The backward is that of the teacher-forced loss with w.TOK for seq.
+// Q == 0 runs in a standard workspace (carve); Q >= 1 in tv_carve's two parts plus the fed tokens and the tile statistics.
+namespace {
+
+TrainVideoWs ssv_carve(const XgDims& d, int Q, void* base) {
+    TrainVideoWs w = tv_carve(d, Q, base);
+    Carver c{static_cast<char*>(base), w.bytes};
+    const size_t M = (size_t)d.B * Q, V = d.V, T = d.T;
+    Ws& s = w.row;
+    s.TOK = c.take<int64_t>(T * M);
+    s.VPART = c.take<float>(M * ((V + 31) / 32 + 16) * 4);         // per-tile row statistics (row pitch: xg_select.h rs_pitch)
+    w.bytes = (c.off + 255) & ~(size_t)255;
+    s.bytes = s.core_bytes = w.bytes;
+    s.end_f = c.base ? reinterpret_cast<const float*>(c.base + w.bytes) : nullptr;
+    return w;
+}
+
+bool ss_dims_ok(const XgDims* d, int Q) { return Q == 0 ? (dims_ok(d) && d->B <= (1 << 20)) : cc_dims_ok(d, Q); }
+
+// What both entry points work in: `row` holds the M decoder rows, `enc` the videos (Q == 0: the same workspace)
+struct SsWs { TrainVideoWs v; Ws plain; Ws* row; Ws* enc; XgDims de, dm; };
+
+// The gates of the two entry points, in the order of include/xgate_ss.h (tv_open's)
+int ss_open(const XgDims* d, int Q, const XgParams* p, const XgRun* run, void* ws, size_t ws_bytes, SsWs* o) {
+    if (Q < 0 || !ss_dims_ok(d, Q) || !ws) return XG_EINVAL;
+    if (Q == 0) {
+        o->plain = carve(*d, ws);
+        if (ws_bytes < o->plain.core_bytes) return XG_EWORKSPACE;
+        if (ws_bytes < o->plain.bytes) { o->plain.sh16 = nullptr; o->plain.bytes = o->plain.core_bytes; }
+        o->row = o->enc = &o->plain;
+        o->de = o->dm = *d;
+    } else {
+        o->v = ssv_carve(*d, Q, ws);
+        if (ws_bytes < o->v.bytes) return XG_EWORKSPACE;
+        o->row = &o->v.row; o->enc = &o->v.enc;
+        o->de = beam_dims(*d, d->B);
+        o->dm = *d; o->dm.B = d->B * Q;
+    }
+    if ((uintptr_t)ws % 256 != 0 || !p || !run || run->gemm_mode != 0) return XG_EINVAL;
+    attach_packed(*o->enc, o->de, run);
+    if (Q > 0) attach_packed(*o->row, o->dm, run);
+    return XG_OK;
+}
+
+// The decoder loop of both forms over d.B = M rows.  rows_per_video > 0: V and v2a(V) live in `enc`, one block per video.  The caller
+// has left the initial state in block 0 of w.H1 / C1 / H2 / C2.  Every step writes its time-major slots, gates included.
+int ss_decoder_loop(Streams& ss, const XgDims& d, const XgParams& p, const XgBatch& x, const XgRun& run, Ws& w, int rows_per_video,
+                    const Ws* enc, float ss_prob, const float* u_sel, const float* u_tok, int64_t* tok_out) {
+    hipStream_t st = ss.main;
+    const int M = d.B, R = d.R, E = d.E, T = d.T, V = d.V;
+    if (!step_scratch_ok(w, false, rows_per_video > 0) || (rows_per_video > 0) != (enc != nullptr) || !w.TOK || !w.VPART) return XG_EINVAL;
+    const Ws& vw = enc ? *enc : w;
+    const bool draw = run.train && ss_prob > 0.f;
+    // the vocabulary product with tile statistics (<= 128 rows, R % 32 == 0, V >= 32: xgk_vocab_select_ok), every row's logits stored
+    const bool tiles = w.gm == 0 && xgk_vocab_select_ok(M, R, V, w.H2, R, p.logit_w);
+    const int tw = xgk_vocab_tile_width(V);
+    XG_TRY(zero_dsync(st, w));
+    XG_TRY(record_prof(run.prof_event0, st));
+    for (int t = 0; t < T; ++t) {
+        const bool dr = draw && t >= 1;
+        const size_t tm = (size_t)t * M;
+        SsChoiceArgs ca{};
+        ca.logits = dr ? w.LOGITS + (tm - M) * V : nullptr;
+        ca.part = (dr && tiles) ? w.VPART : nullptr;
+        ca.u_sel = dr ? u_sel + tm : nullptr; ca.u_tok = dr ? u_tok + tm : nullptr;
+        ca.seq = x.seq; ca.table = p.embed_w; ca.tok = w.TOK + tm; ca.tok_out = tok_out + tm; ca.xt = w.Xe + tm * E;
+        ca.ss_prob = ss_prob; ca.M = M; ca.V = V; ca.E = E; ca.T = T; ca.t = t; ca.ntiles = xg_cdiv(V, tw); ca.tw = tw;
+        XG_TRY(xgk_ss_choice(st, ca));
+        StepIO s = step_io_at(w, d, t);
+        s.pos = x.pos_feats; s.gp = w.GP + tm * R; s.mask = x.seq_mask + t; s.ldm = T; s.rows_per_video = rows_per_video;
+        XG_TRY(core_step(st, d, p, run, w, vw.Venc, vw.vproj, s));
+        float* lg = w.LOGITS + tm * V;
+        if (tiles) XG_TRY(xgk_vocab_part(st, M, R, V, s.h2o, R, p.logit_w, p.logit_b, lg, M, w.VPART, 1.0f));
+        else XG_TRY(xgk_linear(st, w.gm, M, V, R, s.h2o, R, p.logit_w, p.logit_b, lg, V));
+    }
+    return record_prof(run.prof_event1, st);
+}
+
+bool ss_bn_ok(const XgRun* run, const XgBnState* bn) {
+    return run->train || (bn && bn->rgb_mean && bn->rgb_var && bn->opfl_mean && bn->opfl_var);
+}
+
+}  // namespace
+
+extern "C" int xgss_version(void) { return XGSS_VERSION; }
+
+extern "C" size_t xgss_workspace_bytes(const XgDims* d, int32_t Q) {
+    if (Q < 0 || !ss_dims_ok(d, Q)) return 0;
+    return Q == 0 ? carve(*d, nullptr).core_bytes : ssv_carve(*d, Q, nullptr).bytes;
+}
+
+extern "C" int xgss_xe_loss_fwd(void* stream, const XgDims* d, int32_t Q, const XgParams* p, const XgBnState* bn, const XgBatch* x,
+                                const int64_t* cap_classes, const float* class_mask, float weight_class, float ss_prob,
+                                const float* u_sel, const float* u_tok, const XgRun* run, void* ws, size_t ws_bytes, float* losses,
+                                int64_t* tok_out) {
+    SsWs o;
+    XG_TRY(ss_open(d, Q, p, run, ws, ws_bytes, &o));
+    if (!tv_batch_ok(x) || !losses || !tok_out || !ss_bn_ok(run, bn)) return XG_EINVAL;
+    if (!(ss_prob >= 0.f && ss_prob <= 1.f) || (run->train && ss_prob > 0.f && (!u_sel || !u_tok))) return XG_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int M = o.dm.B, T = d->T;
+    Ws& r = *o.row;
+    Streams ss(st, run);
+    if (Q == 0) {
+        XG_TRY(encode_and_init(ss, o.de, *p, bn, *x, *run, r));
+    } else {
+        float* const state0[4] = {r.H1, r.C1, r.H2, r.C2};
+        XG_TRY(videos_once(ss, o.de, *p, bn, *x, *run, *o.enc, CapBeamRepeatArgs{}, state0, Q));
+    }
+    XG_TRY(ss_decoder_loop(ss, o.dm, *p, *x, *run, r, Q, Q > 0 ? o.enc : nullptr, ss_prob, u_sel, u_tok, tok_out));
+    XG_TRY(ss.join());
+    XG_TRY(xgk_xent_fwd(st, r.LOGITS, d->V, x->seq, x->seq_mask, nullptr, M, T, d->V, 1, r.LSE, r.sums, 0, -1, true));
+    if (cap_classes) {                         // (without class targets nobody reads the classifier head: xg_xe_loss_fwd)
+        XG_TRY(classifier_fwd(st, o.dm, *p, *run, r, T * M));
+        XG_TRY(xgk_xent_fwd(st, r.CL, d->C, cap_classes, x->seq_mask, class_mask, M, T, d->C, 0, r.LSEC, r.sums + 2));
+    } else {
+        ZERO(st, r.sums + 2, 2);
+    }
+    hipLaunchKernelGGL(losses_kernel, dim3(1), dim3(1), 0, st, r.sums, cap_classes ? weight_class : 0.f, losses);
+    XG_CHECK_LAUNCH();
+    return XG_OK;
+}
+
+extern "C" int xgss_xe_loss_bwd(void* stream, const XgDims* d, int32_t Q, const XgParams* p, const XgParams* g, const XgBatch* x,
+                                const int64_t* cap_classes, const float* class_mask, float weight_class, const float* dloss_dev,
+                                const XgRun* run, void* ws, size_t ws_bytes) {
+    SsWs o;
+    XG_TRY(ss_open(d, Q, p, run, ws, ws_bytes, &o));
+    if (!g || !tv_batch_ok(x) || !dloss_dev) return XG_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int M = o.dm.B, T = d->T;
+    Ws& r = *o.row;
+    const XentBwd xent{x->seq, x->seq_mask, dloss_dev};
+    const bool cls = cap_classes != nullptr && weight_class != 0.f;
+    if (cls) {
+        COPY(st, r.DCL, r.CL, (size_t)T * M * d->C);
+        XG_TRY(xgk_xent_bwd(st, r.DCL, d->C, cap_classes, x->seq_mask, class_mask, M, T, d->C, 0, r.LSEC, r.sums + 2, dloss_dev,
+                            weight_class));
+    }
+    Streams ss(st, run);
+    // the fed tokens (time-major, w.TOK) take seq's place on the token side and in the embedding scatter: no gradient flows through
+    // the choice (SAModel.py:96 detaches it)
+    if (Q == 0) return backward_tail(ss, *d, *d, *p, *g, *x, *run, r, cls, &xent, x->seq_mask, T, 1, r.TOK, 1, M);
+    XG_TRY(heads_bwd(ss, o.dm, *p, *g, *run, r, T * M, cls, &xent));
+    XG_TRY(decoder_bwd_core(ss, o.dm, *p, *g, *x, *run, r, x->seq_mask, T, 1, r.TOK, 1, M, Q, o.enc));
+    XG_TRY(encoder_bwd(ss, o.de, *p, *g, *x, *run, *o.enc, o.enc->DV));
     return ss.join();
 }

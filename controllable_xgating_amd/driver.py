@@ -247,12 +247,26 @@ class Trainer:
         info = {}
         if not self.sc_flag:
             wc = getattr(opt, "weight_class", 0.0)
-            if b["cap"].dim() == 3:
+            # scheduled sampling (model.ss_prob > 0 in train mode, start_epoch): the fused loss draws inside its decoder loop
+            # (model.xe_loss_ss / xe_loss_ss_per_video); opt.fused_ss_loss = False, or another precision, gives the reference's
+            # call sequence, which honours ss_prob as well but has no per-video form
+            ss = bool(model.training and model.ss_prob > 0.0)
+            ss_fused = ss and getattr(opt, "fused_ss_loss", True) and getattr(model, "precision", "fp32") == "fp32"
+            if ss and b["cap"].dim() == 3:
+                if not ss_fused:
+                    raise NotImplementedError("Q captions per video under scheduled sampling need the fused fp32 loss "
+                                              "(fused_ss_loss, precision fp32): there is no un-fused per-video path")
+                loss = model.xe_loss_ss_per_video(b["feat1"], b["feat2"], b["feat_mask"], b["pos_feat"], b["cap"], b["cap_mask"],
+                                                  b.get("cap_classes"), b.get("class_mask"), wc)
+            elif ss_fused and self.fused:
+                loss = model.xe_loss_ss(b["feat1"], b["feat2"], b["feat_mask"], b["pos_feat"], b["cap"], b["cap_mask"],
+                                        b.get("cap_classes"), b.get("class_mask"), wc)
+            elif b["cap"].dim() == 3:
                 # Q captions per video (data.collate_per_video): cap (B,Q,T), the video's features once -- the fused loss in its
                 # per-video form; the optimizer arming and the gradient event below are the same
                 loss = model.xe_loss_per_video(b["feat1"], b["feat2"], b["feat_mask"], b["pos_feat"], b["cap"], b["cap_mask"],
                                                b.get("cap_classes"), b.get("class_mask"), wc)
-            elif self.fused:
+            elif self.fused and not ss:
                 loss = model.xe_loss(b["feat1"], b["feat2"], b["feat_mask"], b["pos_feat"], b["cap"], b["cap_mask"],
                                      b.get("cap_classes"), b.get("class_mask"), wc)
             else:

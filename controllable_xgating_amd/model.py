@@ -365,11 +365,112 @@ class SAModel(FlatParams, nn.Module):
                 class_mask=None, weight_class=0.0):
         """Fused fast path: forward + LanguageModelCriterion (+ weight_class * ClassiferCriterion)
         without materialising the (m,T,V) log-prob tensor or its gradient
-        (starttrain.py:125-129).  Returns the scalar loss tensor; .backward() works."""
+        (starttrain.py:125-129).  Returns the scalar loss tensor; .backward() works.
+
+        It teacher-forces whatever ``ss_prob`` is: scheduled sampling on the fused path is ``xe_loss_ss``."""
         params = self._param_list()
         save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
         return _XELossFunction.apply(self, save, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes,
                                      class_mask, float(weight_class), *params)
+
+    def _ss_uniforms(self, T, M, dev):
+        """(u_sel, u_tok), each (T, M) float32 on `dev`: the test hook ``self.ss_uniforms`` or two fresh draws."""
+        u = getattr(self, "ss_uniforms", None)
+        if u is None:
+            u = (torch.rand(T, M, device=dev), torch.rand(T, M, device=dev))
+        u = tuple(t.detach().to(dev).contiguous().float() for t in u)
+        for t in u:
+            if tuple(t.shape) != (T, M):
+                raise ValueError("ss_uniforms: two (%d, %d) tensors expected, got %s" % (T, M, tuple(t.shape)))
+        return u
+
+    def xe_loss_ss(self, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes=None, class_mask=None,
+                   weight_class=0.0):
+        """``xe_loss`` under scheduled sampling (include/xgate_ss.h; SAModel.py:89-99): in train mode with ``ss_prob`` > 0, row m of
+        step t >= 1 is fed a token drawn from step t - 1's distribution iff u_sel[t, m] < ss_prob, else seq[m, t]; the loss is
+        ``xe_loss``'s over the logits that token stream produces and no gradient flows through the choice.  The draw happens
+        inside the decoder loop on the device: no (m,T,V) log-prob tensor and no gradient of one.  The uniforms come from the test
+        hook ``self.ss_uniforms = (u_sel, u_tok)``, each (T, m), else from two ``torch.rand``.  Returns the scalar loss with a
+        graph, sets ``last_losses`` and leaves the fed tokens in ``last_ss_tokens`` (T, m) int64.
+
+        Eval mode or ``ss_prob`` == 0: this is ``xe_loss`` (``last_ss_tokens`` is then seq, time-major).  fp32, device tensors."""
+        if not (self.training and self.ss_prob > 0.0):
+            loss = self.xe_loss(feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes, class_mask, weight_class)
+            self.last_ss_tokens = seq.detach().long().t().contiguous()
+            return loss
+        if self.precision != "fp32":
+            raise NotImplementedError("xe_loss_ss is fp32 only (precision = %r)" % (self.precision,))
+        for name, t, nd in (("feats_rgb", feats_rgb, 3), ("feats_opfl", feats_opfl, 3), ("feat_mask", feat_mask, 2),
+                            ("pos_feats", pos_feats, 2), ("seq", seq, 2), ("seq_mask", seq_mask, 2)):
+            if not torch.is_tensor(t) or t.dim() != nd:
+                raise ValueError("%s: a %d-dimensional tensor expected" % (name, nd))
+        for t in (feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes, class_mask):
+            if t is not None and not t.is_cuda:
+                raise NotImplementedError("xe_loss_ss needs device tensors: there is no CPU path")
+        if not 0.0 <= float(self.ss_prob) <= 1.0:
+            raise ValueError("ss_prob in [0, 1] expected, got %r" % (self.ss_prob,))
+        params = self._param_list()
+        save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        u = self._ss_uniforms(int(seq.shape[1]), int(seq.shape[0]), seq.device)
+        return _XELossSSFunction.apply(self, save, 0, float(self.ss_prob), u, feats_rgb, feats_opfl, feat_mask, pos_feats, seq,
+                                       seq_mask, cap_classes, class_mask, float(weight_class), *params)
+
+    def xe_loss_ss_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes=None, class_mask=None,
+                             weight_class=0.0):
+        """``xe_loss_per_video`` under scheduled sampling (include/xgate_ss.h): the shapes of ``xe_loss_per_video`` -- the B videos
+        once, pos_feats (B,Q,R), seq / seq_mask (B,Q,T) --, the rule of ``xe_loss_ss`` on the M = B Q rows, row b Q + q.  The
+        uniforms of the test hook ``self.ss_uniforms`` are (T, M) each; ``last_ss_tokens`` is (T, M) int64.
+
+        Eval mode or ``ss_prob`` == 0: this is ``xe_loss_per_video``.  fp32, device tensors."""
+        if not (self.training and self.ss_prob > 0.0):
+            loss = self.xe_loss_per_video(feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes, class_mask,
+                                          weight_class)
+            self.last_ss_tokens = seq.detach().long().reshape(-1, seq.shape[-1]).t().contiguous()
+            return loss
+        if self.precision != "fp32":
+            raise NotImplementedError("xe_loss_ss_per_video is fp32 only (precision = %r)" % (self.precision,))
+        if not 0.0 <= float(self.ss_prob) <= 1.0:
+            raise ValueError("ss_prob in [0, 1] expected, got %r" % (self.ss_prob,))
+        for name, t, nd in (("feats_rgb", feats_rgb, 3), ("feats_opfl", feats_opfl, 3), ("feat_mask", feat_mask, 2),
+                            ("pos_feats", pos_feats, 3), ("seq", seq, 3), ("seq_mask", seq_mask, 3)):
+            if not torch.is_tensor(t) or t.dim() != nd:
+                raise ValueError("%s: a %d-dimensional tensor expected" % (name, nd))
+        B, K = feats_rgb.shape[:2]
+        Q, T = int(seq.shape[1]), int(seq.shape[2])
+        if B < 1 or K < 1 or Q < 1 or T < 2:
+            raise ValueError("B, K, Q >= 1 and T >= 2 expected, got B %d, K %d, Q %d, T %d" % (B, K, Q, T))
+        want = (("feats_rgb", feats_rgb, (B, K, self.feat_size)), ("feats_opfl", feats_opfl, (B, K, self.feat_size2)),
+                ("feat_mask", feat_mask, (B, K)), ("pos_feats", pos_feats, (B, Q, self.rnn_size)), ("seq", seq, (B, Q, T)),
+                ("seq_mask", seq_mask, (B, Q, T)), ("cap_classes", cap_classes, (B, Q, T)), ("class_mask", class_mask, (B, Q, T)))
+        for name, t, shape in want:
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shape):
+                raise ValueError("%s %s expected, got %s" % (name, shape, tuple(t.shape) if torch.is_tensor(t) else type(t)))
+        if seq.is_floating_point() or (cap_classes is not None and cap_classes.is_floating_point()):
+            raise ValueError("seq and cap_classes are integer tensors")
+        for t in (feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes, class_mask):
+            if t is not None and not t.is_cuda:
+                raise NotImplementedError("xe_loss_ss_per_video needs device tensors: there is no CPU path")
+        params = self._param_list()
+        save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        u = self._ss_uniforms(T, B * Q, seq.device)
+        return _XELossSSFunction.apply(self, save, Q, float(self.ss_prob), u, feats_rgb, feats_opfl, feat_mask, pos_feats, seq,
+                                       seq_mask, cap_classes, class_mask, float(weight_class), *params)
+
+    def _ss_video_workspace(self, d, Q, dev, save):
+        """(key, tensor) of a workspace of xe_loss_ss_per_video (xgss_workspace_bytes): pooled as _video_workspace pools its own."""
+        from . import _native_ss as nss
+        key = (tuple(getattr(d, f[0]) for f in d._fields_), Q, str(dev))
+        pool = self.__dict__.setdefault("_ss_video_pool", {})
+        lst = pool.setdefault((key, save), [])
+        if lst:
+            return key, (lst.pop() if save else lst[0])
+        n = nss.lib().xgss_workspace_bytes(C.byref(d), Q)
+        if n == 0:
+            raise nv.XgError("xgss_workspace_bytes: invalid dims or too many rows (B %d, Q %d)" % (d.B, Q))
+        ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+        if not save:
+            lst.append(ws)
+        return key, ws
 
     def xe_loss_per_video(self, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes=None,
                           class_mask=None, weight_class=0.0):
@@ -1198,6 +1299,77 @@ class _XELossVideoFunction(torch.autograd.Function):
         model._last_video_ws = (ctx.d, ctx.Q, ctx.ws)      # tests / tools: what xgtv_video_grads reads (valid until the next call reuses it)
         ctx.ws = None
         return (None,) * 11 + tuple(model._grad_views(g))
+
+
+class _XELossSSFunction(torch.autograd.Function):
+    """The fused loss under scheduled sampling (include/xgate_ss.h).  Q == 0: _XELossFunction's shapes and workspace pool;
+    Q >= 1: _XELossVideoFunction's shapes, a pool of its own sizes.  The fed tokens go to model.last_ss_tokens."""
+
+    @staticmethod
+    def forward(ctx, model, save, Q, ss_prob, u, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes, class_mask,
+                weight_class, *params):
+        from . import _native_ss as nss
+        B, K, _ = feats_rgb.shape
+        T = seq.shape[-1]
+        M = B * max(Q, 1)
+        dev = feats_rgb.device
+        d = model._dims(B, K, T)
+        if Q == 0:
+            key = None
+            ws, wp, wn = _take_workspace(model, d, dev, save)
+        else:
+            key, ws = model._ss_video_workspace(d, Q, dev, save)
+            wp, wn = _ws_ptr(ws)
+        b, keep = model._batch(feats_rgb, feats_opfl, feat_mask, pos_feats.reshape(M, -1), seq.reshape(M, T), seq_mask.reshape(M, T))
+        cc = None if cap_classes is None else cap_classes.detach().reshape(M, T).contiguous().long()
+        cm = None if class_mask is None else class_mask.detach().reshape(M, T).contiguous().float()
+        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        tok = torch.empty(T, M, dtype=torch.int64, device=dev)
+        ps, bn, run = model._params_struct(), model._bn_struct(), model._run(save)
+
+        def give_back():
+            if Q == 0:
+                if save:
+                    model._pool.give(d, dev, ws)
+            elif save:
+                model._ss_video_pool[(key, True)].append(ws)
+
+        model._bump_bn()                           # (in FRONT of the forward, as _XELossFunction has it)
+        try:
+            nv.check(nss.lib().xgss_xe_loss_fwd(_stream(), C.byref(d), Q, C.byref(ps), C.byref(bn), C.byref(b), nv.ptr(cc), nv.ptr(cm),
+                                                weight_class, ss_prob, nv.ptr(u[0]), nv.ptr(u[1]), C.byref(run), wp, wn,
+                                                nv.ptr(losses), nv.ptr(tok)), "xgss_xe_loss_fwd")
+        except Exception:
+            model._bump_bn(-1)                     # the call was refused: num_batches_tracked stays where it was
+            give_back()
+            raise
+        ctx.model, ctx.d, ctx.Q, ctx.ws, ctx.key, ctx.keep, ctx.run, ctx.saved_ws = model, d, Q, ws, key, keep, run, save
+        ctx.cc, ctx.cm, ctx.wc = cc, cm, weight_class
+        model.last_losses = losses.detach()        # READ-ONLY for callers: it shares storage with the returned loss (no copy kernel)
+        model.last_ss_tokens = tok
+        return losses[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        from . import _native_ss as nss
+        if not ctx.saved_ws:
+            raise nv.XgError("backward without saved activations")
+        model = ctx.model
+        g, gs = model._grads_struct()
+        b, keep = model._batch(*ctx.keep)
+        wp, wn = _ws_ptr(ctx.ws)
+        run = _with_grad_event(model, ctx.run)
+        dl = dloss.detach().contiguous().float().to(keep[0].device)
+        nv.check(nss.lib().xgss_xe_loss_bwd(_stream(), C.byref(ctx.d), ctx.Q, C.byref(model._params_struct()), C.byref(gs), C.byref(b),
+                                            nv.ptr(ctx.cc), nv.ptr(ctx.cm), ctx.wc, nv.ptr(dl), C.byref(run), wp, wn),
+                 "xgss_xe_loss_bwd")
+        if ctx.Q == 0:
+            model._pool.give(ctx.d, keep[0].device, ctx.ws)
+        else:
+            model._ss_video_pool[(ctx.key, True)].append(ctx.ws)
+        model._last_ss_ws = ctx.ws                 # tests: the workspace the call ran in (valid until the next call reuses it)
+        ctx.ws = None
+        return (None,) * 14 + tuple(model._grad_views(g))
 
 
 class _RolloutVideoFunction(torch.autograd.Function):
