@@ -14,9 +14,10 @@ from .control import (pad_templates, caption_with_templates, caption_sampled, ca
                       beam_captions_following_templates, template_adherence, diverse_beam_captions_with_templates,
                       caption_beam_diverse, caption_truncated_with_templates, length_scale_table, repeated_ngrams,
                       beam_captions_ruled_with_templates)
+from .joint import JointTrainer  # noqa: F401,E402
 
 __all__ = ["SAModel", "LanguageModelCriterion", "ClassiferCriterion", "RewardCriterion", "PerVideoRewardCriterion", "make_opt", "XgError", "lib", "pad_templates",
            "caption_with_templates", "caption_sampled", "caption_beam", "first_occurrences", "beam_captions_with_templates",
            "score_captions_with_templates", "template_recovery", "allow_masks", "beam_captions_following_templates",
            "template_adherence", "diverse_beam_captions_with_templates", "caption_beam_diverse",
-           "caption_truncated_with_templates", "length_scale_table", "repeated_ngrams", "beam_captions_ruled_with_templates"]
+           "caption_truncated_with_templates", "length_scale_table", "repeated_ngrams", "beam_captions_ruled_with_templates", "JointTrainer"]

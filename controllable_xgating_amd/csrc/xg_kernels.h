@@ -115,6 +115,10 @@ int xgk_gate_fwd(hipStream_t st, float* pre_g, int ldp, const float* t, int ldt,
 int xgk_gate_bwd(hipStream_t st, const float* dy, int lddy, const float* g, int ldg, const float* t, int ldt, int t_mod,
                  float* dpre, int lddp, float* dt, int lddt, bool dt_accumulate, int rows, int R, XgDrop drop);
 
+// the gate's dt summed over the T steps of contiguous (T,rows,R) stacks: dt[r][j] = sum_t dy[t][r][j] (g[t][r][j] + 1), plain
+// stores, one writer per element, the terms in step order.  *width (may be null): 4 / 1, the kernel form that ran.
+int xgk_gate_dt_sum(hipStream_t st, const float* dy, const float* g, float* dt, int T, int rows, int R, int* width);
+
 // two gates of the same shape in ONE launch (the encoder's cross gates: forward, and backward with plain stores)
 int xgk_gate_fwd2(hipStream_t st, float* pre_g0, float* pre_g1, int ldp, const float* t0, const float* t1, int ldt, int t_mod, float* y0,
                   float* y1, int ldy, int rows, int R, XgDrop drop0, XgDrop drop1, int s_div, int s_mod, int b_div, int b_mod);

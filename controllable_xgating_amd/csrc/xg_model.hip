@@ -24,6 +24,7 @@
 #include "../../include/xgate_train_video.h"
 #include "../../include/xgate_scst_video.h"
 #include "../../include/xgate_ss.h"
+#include "../../include/xgate_joint.h"
 
 #include <new>
 #include <cstdlib>
@@ -2889,3 +2890,63 @@ extern "C" int xgss_xe_loss_bwd(void* stream, const XgDims* d, int32_t Q, const 
     XG_TRY(encoder_bwd(ss, o.de, *p, *g, *x, *run, *o.enc, o.enc->DV));
     return ss.join();
 }
+
+// ---- the caption loss's gradient with respect to pos_feats (include/xgate_joint.h): behind a fused-loss backward, the gate's dt
+// summed over the T steps from what that backward left -- DPOSG (wgrads_chain1: plain stores over the step ranges [0, T) between
+// them) and GP (the forward's gate values, after the gate's dropout).  Neither is written again by a backward: DPOSG's only writers
+// are wgrads_chain1 and the rollout workspaces' rollout_open_pair_videos, GP's the forward's gate product; the three carves (carve,
+// tv_carve, ssv_carve) give both their own blocks.  The backward's last ss.join() has put the caller's stream behind the side streams
+// that wrote DPOSG (chain2_into_aux: the auxiliary stream covers the second side chain).
+namespace { int g_xgj_width = 0; }
+
+extern "C" int xgj_version(void) { return XGJ_VERSION; }
+extern "C" int xgj_last_kernel_width(void) { return g_xgj_width; }
+
+extern "C" int xgj_caption_dpos(void* stream, const XgDims* d, int32_t Q, int32_t form, const XgBatch* x, const XgRun* run, void* ws,
+                                size_t ws_bytes, float* dpos) {
+    if (!dims_ok(d) || !x || !run || !ws || !dpos || (uintptr_t)ws % 256 != 0) return XG_EINVAL;
+    const Ws* r = nullptr;
+    Ws plain; TrainVideoWs v;
+    int M = d->B;
+    if (form == XGJ_FORM_XE || (form == XGJ_FORM_SS && Q == 0)) {
+        if (Q != 0 || d->B > (1 << 20)) return XG_EINVAL;
+        plain = carve(*d, ws);
+        if (ws_bytes < plain.core_bytes) return XG_EINVAL;      // (what check() asks: the bf16 mirror region is optional)
+        r = &plain;
+    } else if (form == XGJ_FORM_VIDEO || form == XGJ_FORM_SS) {
+        if (!cc_dims_ok(d, Q)) return XG_EINVAL;
+        v = form == XGJ_FORM_VIDEO ? tv_carve(*d, Q, ws) : ssv_carve(*d, Q, ws);
+        if (ws_bytes < v.bytes) return XG_EINVAL;
+        r = &v.row;
+        M = d->B * Q;
+    } else {
+        return XG_EINVAL;
+    }
+    return xgk_gate_dt_sum((hipStream_t)stream, r->DPOSG, r->GP, dpos, d->T, M, d->R, &g_xgj_width);
+}
+
+#ifdef XG_DIAG
+// diag library only, host only (no GPU): the two blocks xgj_caption_dpos reads, as byte offsets from the workspace's start, so that
+// a test can overwrite everything else.  out[0..4] = {offset, bytes} of DPOSG, {offset, bytes} of GP, the form's workspace size.
+extern "C" int xgj_debug_ranges(const XgDims* d, int32_t Q, int32_t form, uint64_t* out) {
+    if (!dims_ok(d) || !out) return XG_EINVAL;
+    char* const fake = reinterpret_cast<char*>(uintptr_t(1) << 40);       // never dereferenced: the carves only do arithmetic on it
+    auto off = [&](const void* p) { return (uint64_t)(static_cast<const char*>(p) - fake); };
+    uint64_t rows, total;
+    const float *dposg, *gp;
+    if (form == XGJ_FORM_XE || (form == XGJ_FORM_SS && Q == 0)) {
+        if (Q != 0) return XG_EINVAL;
+        const Ws w = carve(*d, fake);
+        rows = d->B; total = w.core_bytes; dposg = w.DPOSG; gp = w.GP;
+    } else if (form == XGJ_FORM_VIDEO || form == XGJ_FORM_SS) {
+        if (!cc_dims_ok(d, Q)) return XG_EINVAL;
+        const TrainVideoWs v = form == XGJ_FORM_VIDEO ? tv_carve(*d, Q, fake) : ssv_carve(*d, Q, fake);
+        rows = (uint64_t)d->B * Q; total = v.bytes; dposg = v.row.DPOSG; gp = v.row.GP;
+    } else {
+        return XG_EINVAL;
+    }
+    const uint64_t n = (uint64_t)d->T * rows * d->R * sizeof(float);
+    out[0] = off(dposg); out[1] = n; out[2] = off(gp); out[3] = n; out[4] = total;
+    return XG_OK;
+}
+#endif

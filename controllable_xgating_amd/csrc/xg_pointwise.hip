@@ -156,6 +156,24 @@ __global__ void gate_bwd_kernel(GateBwdP pa, GateBwdP pb, int rows, int R) {
     }
 }
 
+// The gate's dt summed over the T steps of a (T,n) stack: out[i] = sum_t dy[t n + i] (g[t n + i] + 1), i = m R + j.  One writer
+// per element, the T terms in step order (no atomics: the same bits every time); consecutive threads read consecutive columns.
+template <int NV>
+__global__ void gate_dt_sum_kernel(const float* __restrict__ dy, const float* __restrict__ g, float* __restrict__ out, int64_t n, int T) {
+    const int64_t i = ((int64_t)blockIdx.x * TPB + threadIdx.x) * NV;
+    if (i >= n) return;
+    float acc[NV], d[NV], gv[NV];
+#pragma unroll
+    for (int q = 0; q < NV; ++q) acc[q] = 0.f;
+    for (int t = 0; t < T; ++t) {
+        ldv<NV>(dy + (size_t)t * n + i, d);
+        ldv<NV>(g + (size_t)t * n + i, gv);
+#pragma unroll
+        for (int q = 0; q < NV; ++q) acc[q] += d[q] * (gv[q] + 1.0f);
+    }
+    stv<NV>(out + i, acc);
+}
+
 __global__ void relu_drop_fwd_kernel(float* x, int64_t n, XgDrop drop) {
     const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
     if (i < n) x[i] *= xg_keep(drop, (uint32_t)i);
@@ -456,6 +474,17 @@ int xgk_gate_bwd2(hipStream_t st, const float* dy0, const float* dy1, int lddy, 
                   XgDrop drop0, XgDrop drop1) {
     const GateBwdP a{dy0, lddy, g0, ldg, t0, ldt, 0, dpre0, lddp, dt0, lddt, 0, drop0}, b{dy1, lddy, g1, ldg, t1, ldt, 0, dpre1, lddp, dt1, lddt, 0, drop1};
     return gate_bwd_launch(st, a, b, 2, rows, R);
+}
+int xgk_gate_dt_sum(hipStream_t st, const float* dy, const float* g, float* dt, int T, int rows, int R, int* width) {
+    const int64_t n = (int64_t)rows * R;
+    if (T < 1 || n < 1) return XG_EINVAL;
+    // four-wide as gate_bwd_v4 decides: the (T,rows,R) stacks are contiguous, so R % 4 == 0 keeps every step's block 16-byte aligned
+    const bool v4 = R % 4 == 0 && ((uintptr_t)dy % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)dt % 16 == 0);
+    if (v4) hipLaunchKernelGGL((gate_dt_sum_kernel<4>), grid1(n / 4), dim3(TPB), 0, st, dy, g, dt, n, T);
+    else hipLaunchKernelGGL((gate_dt_sum_kernel<1>), grid1(n), dim3(TPB), 0, st, dy, g, dt, n, T);
+    XG_CHECK_LAUNCH();
+    if (width) *width = v4 ? 4 : 1;
+    return XG_OK;
 }
 int xgk_relu_drop_fwd(hipStream_t st, float* x, int64_t n, XgDrop drop) {
     if (drop.thresh == 0u || n <= 0) return XG_OK;

@@ -664,6 +664,7 @@ extern "C" int xgp_sample_greedy(void* stream, const XgpDims* d, const XgpParams
 // skinny job.  After the loop every weight gradient is one batched product over the T' B rows; then the encoder in reverse.
 // ==================================================================================================================================
 #include "../../include/xgate_pos_train.h"
+#include "../../include/xgate_pos_joint.h"
 
 namespace {
 
@@ -757,7 +758,7 @@ __global__ void __launch_bounds__(STEP_TPB) pos_cell_head_train_kernel(CellTrain
 
 struct CellBwdArgs {
     const float* lp;             // (B,C) saved log-probabilities of the step
-    const float* dlogp;          // (B,Tp,C) incoming gradient
+    const float* dlogp;          // (B,Tp,C) incoming gradient; null: all zero (nothing is read)
     const float* logit_w;        // (C,R)
     const float* gates;          // (B,4R) i,f,o,g
     const float *c_prev, *c_out; // (B,R)
@@ -779,8 +780,13 @@ __global__ void __launch_bounds__(STEP_TPB) pos_cell_head_bwd_kernel(CellBwdArgs
     const int b = blockIdx.x, tid = threadIdx.x, R = a.R, C = a.C, t = a.t;
     const int lane = tid & 63, wave = tid >> 6;
     const float* lpb = a.lp + (size_t)b * C;
-    const float* dlp = a.dlogp + ((size_t)b * a.Tp + t) * C;
-    if (wave == 0) {
+    const float* dlp = a.dlogp ? a.dlogp + ((size_t)b * a.Tp + t) * C : nullptr;
+    if (wave == 0 && !dlp) {                     // no gradient for the log-probabilities: dlogits = 0, the head sends nothing
+        for (int cc = lane; cc < C; cc += 64) {
+            dl[cc] = 0.f;
+            a.dlogits[(size_t)b * C + cc] = 0.f;
+        }
+    } else if (wave == 0) {
         float sd = 0.f;
         for (int c0 = 0; c0 < C; c0 += 64) sd += wave_sum(c0 + lane < C ? dlp[c0 + lane] : 0.f);
         for (int cc = lane; cc < C; cc += 64) {
@@ -1033,14 +1039,19 @@ int encoder_bwd(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgpP
 }
 
 int backward(hipStream_t st, const XgpDims* d, const XgpParams* p, const XgpParams* g, const XgptRun* run, const float* fr,
-             const float* fo, const float* fm, int Tp, const float* dlogp, const TWs& w) {
+             const float* fo, const float* fm, int Tp, const float* dlogp, const TWs& w, const float* dpos = nullptr) {
     const int B = d->B, K = d->K, R = d->R, A = d->A, E = d->E, C = d->C, T = d->T, BK = B * K, TB = Tp * B;
     const size_t BR = (size_t)B * R;
     pack_t(st, p->a2h_w, R, 4 * R, w.pkt_a2h);
     pack_t(st, p->h2h_w, R, 4 * R, w.pkt_h2h);
     pack_t(st, p->h2a_w, R, A, w.pkt_h2a);
     XG_CHECK_LAUNCH();
-    XG_TRY(xgk_fill(st, w.dH[0], 0.f, (int64_t)BR));
+    // the gradient of the state behind step Tp - 1: zero, or what its consumer sends (include/xgate_pos_joint.h)
+    if (dpos) {
+        if (hipMemcpyAsync(w.dH[0], dpos, sizeof(float) * BR, hipMemcpyDeviceToDevice, st) != hipSuccess) return XG_EHIP;
+    } else {
+        XG_TRY(xgk_fill(st, w.dH[0], 0.f, (int64_t)BR));
+    }
     XG_TRY(xgk_fill(st, w.dC, 0.f, (int64_t)BR));
     CellBwdArgs cb{};
     cb.dlogp = dlogp; cb.logit_w = p->logit_w; cb.new_mask = w.nm; cb.dc = w.dC;
@@ -1120,6 +1131,27 @@ extern "C" int xgpt_backward(void* stream, const XgpDims* d, const XgpParams* p,
     if (!dims_ok(d, true) || !params_ok(g) || !run_ok(run) || !dlogp || Tp < 1 || Tp > d->T || !tk_ok(Tp, d->K)) return XG_EINVAL;
     XG_TRY(args_gate(p, true, feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, tws_layout(d, nullptr).floats));   // (no running statistics)
     return backward((hipStream_t)stream, d, p, g, run, feats_rgb, feats_opfl, feat_mask, Tp, dlogp, tws_layout(d, ws));
+}
+
+// ---- joint training (include/xgate_pos_joint.h): the state the captioner consumes, and its gradient into the backward
+extern "C" int xgpj_version(void) { return XGPJ_VERSION; }
+
+extern "C" int xgpj_final_state(void* stream, const XgpDims* d, int32_t Tp, const void* ws, size_t ws_bytes, float* pos_feats) {
+    if (!dims_ok(d, true) || !tk_ok(d->T, d->K) || Tp < 1 || Tp > d->T || !ws || !pos_feats) return XG_EINVAL;
+    if (ws_bytes < tws_layout(d, nullptr).floats * sizeof(float)) return XG_EWORKSPACE;
+    const TWs w = tws_layout(d, const_cast<void*>(ws));
+    const size_t BR = (size_t)d->B * d->R;
+    return hipMemcpyAsync(pos_feats, w.Hst + (size_t)Tp * BR, sizeof(float) * BR, hipMemcpyDeviceToDevice, (hipStream_t)stream) ==
+                   hipSuccess ? XG_OK : XG_EHIP;
+}
+
+extern "C" int xgpj_backward(void* stream, const XgpDims* d, const XgpParams* p, const XgpParams* g, const XgptRun* run,
+                             const float* feats_rgb, const float* feats_opfl, const float* feat_mask, int32_t Tp, const float* dlogp,
+                             void* ws, size_t ws_bytes, const float* dpos) {
+    if (!dims_ok(d, true) || !params_ok(g) || !run_ok(run) || (!dlogp && !dpos) || Tp < 1 || Tp > d->T || !tk_ok(Tp, d->K))
+        return XG_EINVAL;
+    XG_TRY(args_gate(p, true, feats_rgb, feats_opfl, feat_mask, ws, ws_bytes, tws_layout(d, nullptr).floats));   // (no running statistics)
+    return backward((hipStream_t)stream, d, p, g, run, feats_rgb, feats_opfl, feat_mask, Tp, dlogp, tws_layout(d, ws), dpos);
 }
 
 // ==================================================================================================================================

@@ -369,7 +369,7 @@ class SAModel(FlatParams, nn.Module):
 
         It teacher-forces whatever ``ss_prob`` is: scheduled sampling on the fused path is ``xe_loss_ss``."""
         params = self._param_list()
-        save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        save = _wants_dpos(self, pos_feats, "xe_loss") or (torch.is_grad_enabled() and any(p.requires_grad for p in params))
         return _XELossFunction.apply(self, save, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes,
                                      class_mask, float(weight_class), *params)
 
@@ -410,7 +410,7 @@ class SAModel(FlatParams, nn.Module):
         if not 0.0 <= float(self.ss_prob) <= 1.0:
             raise ValueError("ss_prob in [0, 1] expected, got %r" % (self.ss_prob,))
         params = self._param_list()
-        save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        save = _wants_dpos(self, pos_feats, "xe_loss_ss") or (torch.is_grad_enabled() and any(p.requires_grad for p in params))
         u = self._ss_uniforms(int(seq.shape[1]), int(seq.shape[0]), seq.device)
         return _XELossSSFunction.apply(self, save, 0, float(self.ss_prob), u, feats_rgb, feats_opfl, feat_mask, pos_feats, seq,
                                        seq_mask, cap_classes, class_mask, float(weight_class), *params)
@@ -451,7 +451,7 @@ class SAModel(FlatParams, nn.Module):
             if t is not None and not t.is_cuda:
                 raise NotImplementedError("xe_loss_ss_per_video needs device tensors: there is no CPU path")
         params = self._param_list()
-        save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        save = _wants_dpos(self, pos_feats, "xe_loss_ss_per_video") or (torch.is_grad_enabled() and any(p.requires_grad for p in params))
         u = self._ss_uniforms(T, B * Q, seq.device)
         return _XELossSSFunction.apply(self, save, Q, float(self.ss_prob), u, feats_rgb, feats_opfl, feat_mask, pos_feats, seq,
                                        seq_mask, cap_classes, class_mask, float(weight_class), *params)
@@ -511,7 +511,7 @@ class SAModel(FlatParams, nn.Module):
             if t is not None and not t.is_cuda:
                 raise NotImplementedError("xe_loss_per_video needs device tensors: there is no CPU path")
         params = self._param_list()
-        save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        save = _wants_dpos(self, pos_feats, "xe_loss_per_video") or (torch.is_grad_enabled() and any(p.requires_grad for p in params))
         return _XELossVideoFunction.apply(self, save, feats_rgb, feats_opfl, feat_mask, pos_feats, seq, seq_mask, cap_classes,
                                           class_mask, float(weight_class), *params)
 
@@ -1162,6 +1162,30 @@ def _close_backward(ctx, g, k):
     return (None,) * k + tuple(ctx.model._grad_views(g))
 
 
+def _wants_dpos(model, pos_feats, name):
+    """Whether this call of a fused loss has to return the gradient of pos_feats (joint training, docs/JOINT_TRAINING.md)."""
+    if not (torch.is_tensor(pos_feats) and pos_feats.requires_grad and torch.is_grad_enabled()):
+        return False
+    if model.precision == "bf16":
+        raise NotImplementedError('%s: the gradient of pos_feats is not implemented under precision = "bf16" (fp32 and bf16x3 '
+                                  'are): detach pos_feats or choose another precision' % name)
+    return True
+
+
+def _caption_dpos(ctx, form, Q, d, b, run, wp, wn, pos_index, out):
+    """`out` (backward's result) with the gradient of pos_feats at `pos_index` when the forward's pos_feats required one:
+    xgj_caption_dpos behind the fused-loss backward that has just been enqueued on this stream and workspace.  Otherwise `out`
+    as it is, and nothing runs."""
+    if not ctx.needs_input_grad[pos_index]:
+        return out
+    from . import _native_joint as nj
+    shape, dtype = ctx.pos_meta
+    dpos = torch.empty(shape, dtype=torch.float32, device=ctx.keep[0].device)
+    nv.check(nj.lib().xgj_caption_dpos(_stream(), C.byref(d), Q, form, C.byref(b), C.byref(run), wp, wn, nv.ptr(dpos)),
+             "xgj_caption_dpos")
+    return out[:pos_index] + (dpos.to(dtype),) + out[pos_index + 1:]
+
+
 def _rollout_backward(ctx, dslp, k):
     """xg_rollout_bwd of the sampled rollout whose activations ctx.ws holds: backward of both rollout functions (k: the
     number of their non-parameter inputs)."""
@@ -1236,6 +1260,7 @@ class _XELossFunction(torch.autograd.Function):
             raise
         ctx.model, ctx.d, ctx.ws, ctx.keep, ctx.run, ctx.saved_ws = model, d, ws, keep, run, save
         ctx.cc, ctx.cm, ctx.wc = cc, cm, weight_class
+        ctx.pos_meta = (tuple(pos_feats.shape), pos_feats.dtype)
         model.last_losses = losses.detach()        # READ-ONLY for callers: it shares storage with the returned loss (no copy kernel)
         return losses[0]                           # (a view of the three-element result: no copy kernel)
 
@@ -1245,7 +1270,10 @@ class _XELossFunction(torch.autograd.Function):
         dl = dloss.detach().contiguous().float().to(keep[0].device)
         nv.check(nv.lib().xg_xe_loss_bwd(_stream(), C.byref(d), C.byref(ps), C.byref(gs), C.byref(b), nv.ptr(ctx.cc),
                                          nv.ptr(ctx.cm), ctx.wc, nv.ptr(dl), C.byref(run), wp, wn), "xg_xe_loss_bwd")
-        return _close_backward(ctx, g, 11)
+        # (before the workspace goes back to the pool: the sum reads what the backward left in it)
+        from . import _native_joint as nj
+        extra = _caption_dpos(ctx, nj.XGJ_FORM_XE, 0, d, b, run, wp, wn, 5, (None,) * 11)
+        return extra + _close_backward(ctx, g, 0)
 
 
 class _XELossVideoFunction(torch.autograd.Function):
@@ -1278,6 +1306,7 @@ class _XELossVideoFunction(torch.autograd.Function):
             raise
         ctx.model, ctx.d, ctx.Q, ctx.ws, ctx.key, ctx.keep, ctx.run, ctx.saved_ws = model, d, Q, ws, key, keep, run, save
         ctx.cc, ctx.cm, ctx.wc = cc, cm, weight_class
+        ctx.pos_meta = (tuple(pos_feats.shape), pos_feats.dtype)
         model.last_losses = losses.detach()        # READ-ONLY for callers: it shares storage with the returned loss (no copy kernel)
         return losses[0]
 
@@ -1295,10 +1324,12 @@ class _XELossVideoFunction(torch.autograd.Function):
         nv.check(ntv.lib().xgtv_xe_loss_bwd(_stream(), C.byref(ctx.d), ctx.Q, C.byref(model._params_struct()), C.byref(gs), C.byref(b),
                                             nv.ptr(ctx.cc), nv.ptr(ctx.cm), ctx.wc, nv.ptr(dl), C.byref(run), wp, wn),
                  "xgtv_xe_loss_bwd")
+        from . import _native_joint as nj
+        extra = _caption_dpos(ctx, nj.XGJ_FORM_VIDEO, ctx.Q, ctx.d, b, run, wp, wn, 5, (None,) * 11)
         model._video_pool[(ctx.key, True)].append(ctx.ws)
         model._last_video_ws = (ctx.d, ctx.Q, ctx.ws)      # tests / tools: what xgtv_video_grads reads (valid until the next call reuses it)
         ctx.ws = None
-        return (None,) * 11 + tuple(model._grad_views(g))
+        return extra + tuple(model._grad_views(g))
 
 
 class _XELossSSFunction(torch.autograd.Function):
@@ -1345,6 +1376,7 @@ class _XELossSSFunction(torch.autograd.Function):
             raise
         ctx.model, ctx.d, ctx.Q, ctx.ws, ctx.key, ctx.keep, ctx.run, ctx.saved_ws = model, d, Q, ws, key, keep, run, save
         ctx.cc, ctx.cm, ctx.wc = cc, cm, weight_class
+        ctx.pos_meta = (tuple(pos_feats.shape), pos_feats.dtype)
         model.last_losses = losses.detach()        # READ-ONLY for callers: it shares storage with the returned loss (no copy kernel)
         model.last_ss_tokens = tok
         return losses[0]
@@ -1363,13 +1395,15 @@ class _XELossSSFunction(torch.autograd.Function):
         nv.check(nss.lib().xgss_xe_loss_bwd(_stream(), C.byref(ctx.d), ctx.Q, C.byref(model._params_struct()), C.byref(gs), C.byref(b),
                                             nv.ptr(ctx.cc), nv.ptr(ctx.cm), ctx.wc, nv.ptr(dl), C.byref(run), wp, wn),
                  "xgss_xe_loss_bwd")
+        from . import _native_joint as nj
+        extra = _caption_dpos(ctx, nj.XGJ_FORM_SS, ctx.Q, ctx.d, b, run, wp, wn, 8, (None,) * 14)
         if ctx.Q == 0:
             model._pool.give(ctx.d, keep[0].device, ctx.ws)
         else:
             model._ss_video_pool[(ctx.key, True)].append(ctx.ws)
         model._last_ss_ws = ctx.ws                 # tests: the workspace the call ran in (valid until the next call reuses it)
         ctx.ws = None
-        return (None,) * 14 + tuple(model._grad_views(g))
+        return extra + tuple(model._grad_views(g))
 
 
 class _RolloutVideoFunction(torch.autograd.Function):

@@ -200,11 +200,19 @@ class PosModel(FlatParams, nn.Module):
                                             fm.data_ptr(), V.data_ptr(), ws.data_ptr(), ws.numel()), "xgp_encoder_fwd")
         return V
 
-    def forward(self, feats_rgb, feats_opfl, feat_mask, seq, seq_mask, cap_classes, new_mask):
+    def forward(self, feats_rgb, feats_opfl, feat_mask, seq, seq_mask, cap_classes, new_mask, return_pos_feats=False):
         """SAModel.py:62-90: teacher-forced log-probabilities (B, T', C) over the already rolled `cap_classes` / `new_mask`
         (prepare_pos_targets); the loop stops at the first i >= 1 whose category column is all zero.  `seq` / `seq_mask` are
         unused, as in the reference.  In train mode: BatchNorm over the batch (running statistics and num_batches_tracked
-        updated), dropout, and a result that carries a gradient."""
+        updated), dropout, and a result that carries a gradient.
+
+        `return_pos_feats` (train mode only; joint training, docs/JOINT_TRAINING.md): returns (logp, pos_feats), pos_feats (B,R)
+        the state behind step T' - 1 -- the vector the captioner consumes (caption_src/data_io.py:215-216) -- with a graph of
+        its own: a gradient sent into it reaches the generator's parameters through the same HIP backward.  Under dropout it is
+        the state after the step's mask, as the loop carries it.  In eval mode `sample_forced` yields the vector."""
+        if return_pos_feats and not self.training:
+            raise NotImplementedError("return_pos_feats is the train-mode forward's output: in eval mode sample_forced returns "
+                                      "pos_feats for the same tags")
         if self.training:
             for t in (feats_rgb, feats_opfl, feat_mask, cap_classes, new_mask):
                 if not t.is_cuda:
@@ -216,7 +224,7 @@ class PosModel(FlatParams, nn.Module):
             nm = new_mask.detach().float().contiguous()
             if cap.shape[0] != fm.shape[0] or tuple(nm.shape) != tuple(cap.shape):
                 raise nv.XgError("cap_classes / new_mask (B,T) expected")
-            return _PosTrainFunction.apply(self, fr.detach(), fo.detach(), fm.detach(), cap, nm, *self._plist())
+            return _PosTrainFunction.apply(self, bool(return_pos_feats), fr.detach(), fo.detach(), fm.detach(), cap, nm, *self._plist())
         self._check_eval(feats_rgb, feats_opfl, feat_mask, cap_classes, new_mask)
         fr, fo, fm = self._feats(feats_rgb, feats_opfl, feat_mask)
         cap = cap_classes.long().contiguous()
@@ -428,7 +436,7 @@ class PosModel(FlatParams, nn.Module):
 
 class _PosTrainFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, fr, fo, fm, cap, nm, *params):
+    def forward(ctx, model, want_pos, fr, fo, fm, cap, nm, *params):
         B, K = fm.shape
         T = cap.shape[1]
         dev = fr.device
@@ -445,10 +453,18 @@ class _PosTrainFunction(torch.autograd.Function):
         model._train_gen += 1
         Tp = int(t_out.item())                      # the one host synchronisation of the iteration
         ctx.model, ctx.dims, ctx.run, ctx.Tp, ctx.gen, ctx.keep = model, dims, run, Tp, model._train_gen, (fr, fo, fm)
-        return logp if Tp == T else logp[:, :Tp].contiguous()
+        out = logp if Tp == T else logp[:, :Tp].contiguous()
+        if not want_pos:
+            return out
+        from . import _native_pos_joint as npj
+        pos = torch.empty(B, model.rnn_size, device=dev)
+        nv.check(npj.lib().xgpj_final_state(_stream(), C.byref(dims), Tp, ws.data_ptr(), ws.numel(), pos.data_ptr()),
+                 "xgpj_final_state")
+        ctx.set_materialize_grads(False)            # an output nobody differentiates sends None, not a zero tensor
+        return out, pos
 
     @staticmethod
-    def backward(ctx, dlogp):
+    def backward(ctx, dlogp, dpos=None):
         model = ctx.model
         if model._train_gen != ctx.gen or model._tws is None:
             raise nv.XgError("PosModel backward: a later train-mode forward has overwritten this forward's saved activations "
@@ -456,12 +472,21 @@ class _PosTrainFunction(torch.autograd.Function):
         fr, fo, fm = ctx.keep
         ws = model._tws
         g, gs = model._grads_struct()
-        dl = dlogp.detach().float().contiguous()
         run = ctx.run
-        nv.check(npt.lib().xgpt_backward(_stream(), C.byref(ctx.dims), C.byref(model._params()), C.byref(gs), C.byref(run),
-                                         fr.data_ptr(), fo.data_ptr(), fm.data_ptr(), ctx.Tp, dl.data_ptr(), ws.data_ptr(),
-                                         ws.numel()), "xgpt_backward")
-        return (None,) * 6 + tuple(model._grad_views(g))
+        if dlogp is None and dpos is None:
+            return (None,) * (7 + len(npos.PARAM_NAMES))
+        dl = None if dlogp is None else dlogp.detach().float().contiguous()
+        if dpos is None:
+            nv.check(npt.lib().xgpt_backward(_stream(), C.byref(ctx.dims), C.byref(model._params()), C.byref(gs), C.byref(run),
+                                             fr.data_ptr(), fo.data_ptr(), fm.data_ptr(), ctx.Tp, dl.data_ptr(), ws.data_ptr(),
+                                             ws.numel()), "xgpt_backward")
+        else:
+            from . import _native_pos_joint as npj
+            dp = dpos.detach().float().contiguous()
+            nv.check(npj.lib().xgpj_backward(_stream(), C.byref(ctx.dims), C.byref(model._params()), C.byref(gs), C.byref(run),
+                                             fr.data_ptr(), fo.data_ptr(), fm.data_ptr(), ctx.Tp, None if dl is None else dl.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), dp.data_ptr()), "xgpj_backward")
+        return (None,) * 7 + tuple(model._grad_views(g))
 
 
 class ClassiferCriterion(nn.Module):
